@@ -36,15 +36,25 @@ rank 0's line and the exit code (compairr_amd.dist.spawn_ranks).  The reference 
 The only collective of the default split is one all-reduce (sum, int64) of the R1 x R2
 matrix per step; it runs on a second stream, ordered by events, so that the all-reduce of a
 step overlaps the work of the next (two matrices).  In strong mode the reduced matrix is
-the N = 1 matrix; it is compared, at every N, with the matrix the reference binary printed
+the N = 1 matrix; `--full` compares it, at every N, with the matrix the reference binary printed
 for the same workload (tests/golden/full_size.json, "parity_vs_reference_full_size"); a
 mismatch there or on the CPU sample ends the run with exit status 1.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description), with
-`roofline` (the dominant kernel against its binding unit, from the committed
-rocprofv3 counters and the live HIP-event time) and `cpu_baseline` (the
-reference program timed on this box's host cores on a bounded sample of the same
-workload).
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (the wall time of one timed step) and the workload's `config`.  A plain run does
+only that: it sets up, warms up, times the K steps and prints the line.  `--full` adds what the
+headline does not need: HIP events around the layout's kernels inside the timed steps
+(`step_kernels_ms`, ~25 us per step), the query set laid out from HOST buffers
+(`value_incl_layout`), the launches alone (`value_resident_step`), the synchronous call
+(`device_resident_inputs`), `roofline` (the dominant kernel against its binding unit, from the
+committed rocprofv3 counters and the live HIP-event time), `cpu_baseline` (the reference program
+timed on all host cores on a bounded sample of the same workload) and the parity checks
+above, whose failure ends the run with exit status 1.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the R1 x R2
+matrix a caller of cmpr_overlap_matrix_device receives (the all-reduced one at N > 1) -- as
+DIR/matrix.npy (float64) on rank 0.  The workload is seeded: the same arguments give the same
+inputs in every run.
 """
 
 import argparse
@@ -121,6 +131,12 @@ def parse_args():
                    help="auto: `--gpus N` with N > 1 and no RANK in the environment starts its N ranks itself "
                         "(torch.distributed.run as a child process, before anything touches the GPU); always: "
                         "also at N = 1 (the RCCL path at world size 1); never: expect a launcher around it")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline does not need (see the module docstring): "
+                        "per-kernel times, rooflines, the layout from host buffers, the launches alone, the CPU "
+                        "baseline and the parity checks against the reference")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the matrix of the last step as DIR/matrix.npy (float64)")
     return p.parse_args()
 
 
@@ -434,9 +450,12 @@ def main():
             dist.all_reduce(x, op=dist.ReduceOp.MAX)
             dt = float(x.item())
         return dt, m
-    skip_host = args.skip_host_layout and not routed
+    # (a plain run lays out no set from host buffers: those times are --full's)
+    skip_host = not args.full or (args.skip_host_layout and not routed)
     t_layout_first, _ = (None, None) if skip_host else timed_layout()
     t_layout, moved = (None, None) if skip_host else timed_layout()
+    if skip_host and routed:
+        lay_out()                                          # (the first call allocates; the shape below is its)
     layout_ms = None if skip_host else {
                  "total": t_layout * 1e3,
                  "library_call_total": h.get_tunable("layout_total_us") / 1e3,
@@ -452,7 +471,8 @@ def main():
     view = keep = None
     if not routed:
         view, keep = h.device_view(qry)
-        h.set_tunable("layout_timing", 1)                  # (events around the layout's kernels: ~25 us per call)
+        if args.full:
+            h.set_tunable("layout_timing", 1)              # (events around the layout's kernels: ~25 us per call)
         h.set_queries_device(view)                         # (warm: allocations kept)
         torch.cuda.synchronize()
     R1, R2 = h.shape
@@ -527,35 +547,39 @@ def main():
                 # (a positives buffer that the first launch overflowed grows when a later launch finds that
                 # launch finished: let that be the second warm-up launch, not the first timed step)
                 torch.cuda.synchronize()
-        elapsed = timed(lambda: step(True), args.steps)
+        elapsed = timed(lambda: step(args.full), args.steps)
         matrix = mats[(nstep[0] - 1) & 1]
+        # (the matrix of the last timed step, before any later launch reuses its buffer)
+        result_matrix = matrix.cpu().numpy().astype(np.uint64).reshape(R1, R2)
         st = h.stats()
-        # HIP events recorded by the library on the kernels' stream, one set per step of
-        # the timed region (ring of the last 64 launches: no synchronisation inside the loop)
-        kernel_ms, probe_ms = h.kernel_times(args.steps)
-        # the launches alone over the resident layout (the headline of rounds 1-5)
-        for _ in range(2):
-            launch()
-        resident_steps = max(args.steps, 10)
-        elapsed_resident = elapsed if not per_set else timed(launch, resident_steps)
-        if per_set:
-            matrix_resident = mats[(nstep[0] - 1) & 1]
-            same_resident = bool(torch.equal(matrix_resident, matrix))
-        else:
-            same_resident = True
+        if args.full:
+            # HIP events recorded by the library on the kernels' stream, one set per step of
+            # the timed region (ring of the last 64 launches: no synchronisation inside the loop)
+            kernel_ms, probe_ms = h.kernel_times(args.steps)
+            k_avg_ms = float(np.mean(kernel_ms))
+            p_avg_ms = float(np.mean(probe_ms))
+            # the launches alone over the resident layout (the headline of rounds 1-5)
+            for _ in range(2):
+                launch()
+            resident_steps = max(args.steps, 10)
+            elapsed_resident = elapsed if not per_set else timed(launch, resident_steps)
+            if per_set:
+                matrix_resident = mats[(nstep[0] - 1) & 1]
+                same_resident = bool(torch.equal(matrix_resident, matrix))
+            else:
+                same_resident = True
 
     total_queries = args.queries if strong else args.queries * world
     value = total_queries * args.steps / elapsed
-    k_avg_ms = float(np.mean(kernel_ms))
-    p_avg_ms = float(np.mean(probe_ms))
-
-    result_matrix = matrix.cpu().numpy().astype(np.uint64).reshape(R1, R2)
     checksum = synth.checksum(result_matrix)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "matrix.npy"), result_matrix.astype(np.float64))
 
     # One more rate of the same workload (one GPU): the launch as a synchronous call that ends with
     # the matrix in host memory, and the layout call on its own.
     device_soa = None
-    if world == 1 and not use_dist and view is not None:
+    if args.full and world == 1 and not use_dist and view is not None:
         torch.cuda.synchronize()
         t = time.perf_counter()
         h.set_queries_device(view)
@@ -578,57 +602,6 @@ def main():
     failed = []
     if rank == 0:
         wl = workload_name(args)
-        baseline = None
-        parity = None
-        if world == 1 and args.cpu_sample >= 0:
-            # ~10-30 s of CPU work: single-core rates of the reference loop
-            per_q = {0: 3e7, 1: 2.3e5, 2: 2.6e3}[args.differences] / (2 if args.indels else 1)
-            sample = args.cpu_sample or int(min(args.queries, max(1000, per_q * 20)))
-            baseline, want, q, fmt, ref_used = cpu_baseline(ref, qry, opt, sample, args)
-            # the same sample on the GPU must give the same cells: bit for bit against
-            # the port, digit for digit (the reference prints %.10lg) against the binary
-            if ref_used is not ref:
-                h.set_reference(ref_used, full.longest)    # (a bounded reference sample: --cpu-refs)
-            h.set_queries(q)
-            got = h.overlap_matrix().astype(np.float64)
-            if fmt:
-                got = np.vectorize(lambda x: float(fmt % x))(got)
-            parity = bool(np.array_equal(got, want))
-            if not parity:
-                print("PARITY FAILURE: HIP matrix differs from the CPU %s on the sample"
-                      % baseline["kind"], file=sys.stderr)
-                failed.append("parity_on_cpu_sample")
-        rec = recorded_workload(args)
-        parity_full = None
-        if rec is not None:
-            import _full_size
-            why = _full_size.mismatch(rec, result_matrix)
-            parity_full = why is None
-            if why:
-                print("PARITY FAILURE: the (reduced) matrix differs from the reference's "
-                      "(tests/golden/full_size.json %s): %s" % (rec["name"], why), file=sys.stderr)
-                failed.append("parity_vs_reference_full_size")
-        if not same_resident:
-            print("PARITY FAILURE: the launches over the resident layout give another matrix than the "
-                  "timed steps", file=sys.stderr)
-            failed.append("same_matrix_resident")
-        if device_soa and not device_soa["same_matrix"]:
-            print("PARITY FAILURE: the synchronous call gives another matrix than the timed steps",
-                  file=sys.stderr)
-            failed.append("same_matrix_sync")
-        # every kernel that is a tenth of the step or more against its roofline; `roofline` = the one that
-        # takes the longest (the dominant kernel of the timed step)
-        step_ms = dict({k: float(np.mean([x[k] for x in layout_kernels])) for k in LAYOUT_PARTS}
-                       if layout_kernels else {})
-        if rec_tiles:
-            step_ms.pop("tiles", None)             # (record tiles: fill_tiles_kernel does not run -- an empty interval)
-        roofs = layout_rooflines(wl, int(st.queries), int(qry.offsets[-1]) if qry.n else 0,
-                                 int(layout["query_slots"]), int(h_items), args.indels, step_ms) if per_set else {}
-        roofs["probe"] = roofline(wl, st, p_avg_ms, k_avg_ms,
-                                  "probe_pairs2_kernel" if layout.get("d2_pairs") else
-                                  {0: "probe_kernel", 1: "probe_sliced_kernel", 2: "probe_rows_kernel"}[layout["variant"]])
-        dominant = max(roofs, key=lambda k: roofs[k]["kernel_ms"])
-        roof = dict(roofs[dominant], dominant_of=sorted(roofs))
         out = {
             "metric": "query sequences/sec for --matrix d=%d%s, %s-vs-%s %s" % (
                 args.differences, " --indels" if args.indels else "",
@@ -665,43 +638,98 @@ def main():
                                        else "queries sharded", world)) if world > 1 else "single GPU",
                        "matrix_checksum": checksum,
                        "layout": layout,
-                       "setup_seconds": {"generate": round(t_gen, 2), "index_build+upload": round(t_index, 3),
-                                         "query_layout+upload": None if skip_host else round(t_layout, 4),
-                                         "query_layout+upload_first_call": None if skip_host else round(t_layout_first, 4)},
-                       # cmpr_set_queries, warm context: upload of the caller's arrays in ranges
-                       # (the keys kernel of a range runs under the copy of the next), then what
-                       # the upload cannot hide (sizes, scatter, tiles, items, chunk order)
-                       "query_layout_ms": layout_ms},
-            # from cmpr_set_view in host memory to the matrix: upload + device-side layout
-            # of the queries (once per query set) + one step
-            # (warm: a context that has laid out a set of this size before and keeps its
-            #  allocations; cold: the first call of a context, allocations included -- the
-            #  definition BENCH_r01 / r02 used for "value_incl_layout")
-            "value_incl_layout": None if skip_host else total_queries / (t_layout + elapsed_resident / resident_steps),
-            "value_incl_layout_cold": None if skip_host else
-                                      total_queries / (t_layout_first + elapsed_resident / resident_steps),
-            # the launches alone over one laid-out query set (what rounds 1-5 reported as `value`)
-            "value_resident_step": total_queries * resident_steps / elapsed_resident,
-            "resident_step_ms": elapsed_resident / resident_steps * 1e3,
-            "resident_steps_same_matrix": same_resident,
-            # HIP-event times inside the timed steps (means): the layout's kernels, then probe and resolve
-            "step_kernels_ms": dict(
-                {k: float(np.mean([x[k] for x in layout_kernels])) for k in LAYOUT_PARTS
-                 if not (rec_tiles and k == "tiles")} if layout_kernels else {},
-                probe=p_avg_ms, resolve=k_avg_ms - p_avg_ms),
-            # from DEVICE arrays to the matrix (no PCIe), and the synchronous step that ends
-            # with the matrix on the host
-            "value_from_device_soa": device_soa and device_soa["value_from_device_soa"],
-            "step_ms_incl_d2h": device_soa and device_soa["step_ms_incl_d2h"],
-            "device_resident_inputs": device_soa,
-            # the whole result of the timed steps against the matrix the reference binary
-            # printed for this very workload (tests/golden/full_size.json), at every N
-            "parity_vs_reference_full_size": parity_full,
-            "roofline": roof,
-            "roofline_kernels": roofs,
-            "cpu_baseline": baseline,
-            "parity_on_cpu_sample": parity,
+                       "setup_seconds": {"generate": round(t_gen, 2), "index_build+upload": round(t_index, 3)}},
         }
+        if args.full:
+            baseline = None
+            parity = None
+            if world == 1 and args.cpu_sample >= 0:
+                # ~10-30 s of CPU work: single-core rates of the reference loop
+                per_q = {0: 3e7, 1: 2.3e5, 2: 2.6e3}[args.differences] / (2 if args.indels else 1)
+                sample = args.cpu_sample or int(min(args.queries, max(1000, per_q * 20)))
+                baseline, want, q, fmt, ref_used = cpu_baseline(ref, qry, opt, sample, args)
+                # the same sample on the GPU must give the same cells: bit for bit against
+                # the port, digit for digit (the reference prints %.10lg) against the binary
+                if ref_used is not ref:
+                    h.set_reference(ref_used, full.longest)    # (a bounded reference sample: --cpu-refs)
+                h.set_queries(q)
+                got = h.overlap_matrix().astype(np.float64)
+                if fmt:
+                    got = np.vectorize(lambda x: float(fmt % x))(got)
+                parity = bool(np.array_equal(got, want))
+                if not parity:
+                    print("PARITY FAILURE: HIP matrix differs from the CPU %s on the sample"
+                          % baseline["kind"], file=sys.stderr)
+                    failed.append("parity_on_cpu_sample")
+            rec = recorded_workload(args)
+            parity_full = None
+            if rec is not None:
+                import _full_size
+                why = _full_size.mismatch(rec, result_matrix)
+                parity_full = why is None
+                if why:
+                    print("PARITY FAILURE: the (reduced) matrix differs from the reference's "
+                          "(tests/golden/full_size.json %s): %s" % (rec["name"], why), file=sys.stderr)
+                    failed.append("parity_vs_reference_full_size")
+            if not same_resident:
+                print("PARITY FAILURE: the launches over the resident layout give another matrix than the "
+                      "timed steps", file=sys.stderr)
+                failed.append("same_matrix_resident")
+            if device_soa and not device_soa["same_matrix"]:
+                print("PARITY FAILURE: the synchronous call gives another matrix than the timed steps",
+                      file=sys.stderr)
+                failed.append("same_matrix_sync")
+            # every kernel that is a tenth of the step or more against its roofline; `roofline` = the one that
+            # takes the longest (the dominant kernel of the timed step)
+            step_ms = dict({k: float(np.mean([x[k] for x in layout_kernels])) for k in LAYOUT_PARTS}
+                           if layout_kernels else {})
+            if rec_tiles:
+                step_ms.pop("tiles", None)             # (record tiles: fill_tiles_kernel does not run -- an empty interval)
+            roofs = layout_rooflines(wl, int(st.queries), int(qry.offsets[-1]) if qry.n else 0,
+                                     int(layout["query_slots"]), int(h_items), args.indels, step_ms) if per_set else {}
+            roofs["probe"] = roofline(wl, st, p_avg_ms, k_avg_ms,
+                                      "probe_pairs2_kernel" if layout.get("d2_pairs") else
+                                      {0: "probe_kernel", 1: "probe_sliced_kernel", 2: "probe_rows_kernel"}[layout["variant"]])
+            dominant = max(roofs, key=lambda k: roofs[k]["kernel_ms"])
+            roof = dict(roofs[dominant], dominant_of=sorted(roofs))
+            out["config"]["setup_seconds"].update({
+                "query_layout+upload": None if skip_host else round(t_layout, 4),
+                "query_layout+upload_first_call": None if skip_host else round(t_layout_first, 4)})
+            # cmpr_set_queries, warm context: upload of the caller's arrays in ranges
+            # (the keys kernel of a range runs under the copy of the next), then what
+            # the upload cannot hide (sizes, scatter, tiles, items, chunk order)
+            out["config"]["query_layout_ms"] = layout_ms
+            out.update({
+                # from cmpr_set_view in host memory to the matrix: upload + device-side layout
+                # of the queries (once per query set) + one step
+                # (warm: a context that has laid out a set of this size before and keeps its
+                #  allocations; cold: the first call of a context, allocations included -- the
+                #  definition BENCH_r01 / r02 used for "value_incl_layout")
+                "value_incl_layout": None if skip_host else total_queries / (t_layout + elapsed_resident / resident_steps),
+                "value_incl_layout_cold": None if skip_host else
+                                          total_queries / (t_layout_first + elapsed_resident / resident_steps),
+                # the launches alone over one laid-out query set (what rounds 1-5 reported as `value`)
+                "value_resident_step": total_queries * resident_steps / elapsed_resident,
+                "resident_step_ms": elapsed_resident / resident_steps * 1e3,
+                "resident_steps_same_matrix": same_resident,
+                # HIP-event times inside the timed steps (means): the layout's kernels, then probe and resolve
+                "step_kernels_ms": dict(
+                    {k: float(np.mean([x[k] for x in layout_kernels])) for k in LAYOUT_PARTS
+                     if not (rec_tiles and k == "tiles")} if layout_kernels else {},
+                    probe=p_avg_ms, resolve=k_avg_ms - p_avg_ms),
+                # from DEVICE arrays to the matrix (no PCIe), and the synchronous step that ends
+                # with the matrix on the host
+                "value_from_device_soa": device_soa and device_soa["value_from_device_soa"],
+                "step_ms_incl_d2h": device_soa and device_soa["step_ms_incl_d2h"],
+                "device_resident_inputs": device_soa,
+                # the whole result of the timed steps against the matrix the reference binary
+                # printed for this very workload (tests/golden/full_size.json), at every N
+                "parity_vs_reference_full_size": parity_full,
+                "roofline": roof,
+                "roofline_kernels": roofs,
+                "cpu_baseline": baseline,
+                "parity_on_cpu_sample": parity,
+            })
         print(json.dumps(out), flush=True)
     h.close()
     if use_dist:

@@ -33,6 +33,13 @@ def test_bench_refuses_to_run_without_a_gpu():
     assert "no CPU fallback" in p.stderr.decode() + p.stdout.decode()
 
 
+def test_bench_offers_full_and_dump_outputs():
+    p = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 0
+    assert b"--full" in p.stdout and b"--dump-outputs DIR" in p.stdout
+
+
 def test_layout_rooflines_are_algorithmic_bytes_over_time_against_8_tb_s():
     b = _bench()
     n, residues, slots, items = 10_000_000, 150_000_000, 10_100_000, 9_000_000

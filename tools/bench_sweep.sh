@@ -5,7 +5,7 @@ O=gpurun_out/$1; shift; mkdir -p $O
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  timeout 900 python bench.py --cpu-sample -1 $cfg > $O/run$i.json 2>$O/run$i.err
+  timeout 900 python bench.py --full --cpu-sample -1 $cfg > $O/run$i.json 2>$O/run$i.err
   python - "$cfg" $O/run$i.json <<'PY'
 import json,sys
 try:

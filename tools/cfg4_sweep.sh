@@ -6,7 +6,7 @@ out=gpurun_out/cfg4_sweep.txt
 : > $out
 run() {
   tag=$1; shift
-  timeout 300 python bench.py --indels --steps 20 --warmup 5 --cpu-sample -1 "$@" > gpurun_out/cfg4_sweep/$tag.json 2>/dev/null
+  timeout 300 python bench.py --indels --steps 20 --warmup 5 --full --cpu-sample -1 "$@" > ${out%.txt}/$tag.json 2>/dev/null
   python - gpurun_out/cfg4_sweep/$tag.json "$tag" >> $out <<'PY'
 import json, sys
 try:

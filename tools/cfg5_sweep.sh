@@ -1,7 +1,7 @@
 #!/bin/bash
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r03q
-A="--cpu-sample -1 --nucleotides --ignore-genes --differences 2 --refs 100000000 --queries 12500000 --steps 2 --warmup 1"
+A="--full --cpu-sample -1 --nucleotides --ignore-genes --differences 2 --refs 100000000 --queries 12500000 --steps 2 --warmup 1"
 run() { name=$1; shift; timeout 400 python bench.py $A "$@" > gpurun_out/r03q/$name.json 2>gpurun_out/r03q/$name.err; python - gpurun_out/r03q/$name.json $name <<'PY'
 import json,sys
 try:

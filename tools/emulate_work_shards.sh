@@ -6,7 +6,7 @@
 cd "$(dirname "$0")/.." || exit 1
 O=${1:-gpurun_out/work_shards}; shift; mkdir -p $O
 for n in 1 2 4 8; do
-  python3 bench.py --steps 20 --warmup 5 --cpu-sample -1 --tunable work_shard_count=$n --tunable work_shard_index=0 "$@" > $O/w$n.json 2> $O/w$n.err
+  python3 bench.py --full --steps 20 --warmup 5 --cpu-sample -1 --tunable work_shard_count=$n --tunable work_shard_index=0 "$@" > $O/w$n.json 2> $O/w$n.err
   python3 - $O/w$n.json $n <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # usage (GPU box): tools/nt_quick.sh <tag>  -- the nucleotide workloads that fit a quick run
 cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/$1; mkdir -p $O
-run() { name=$1; shift; timeout 600 python bench.py --cpu-sample -1 "$@" > $O/$name.json 2>$O/$name.err; python - $O/$name.json $name <<'PY'
+run() { name=$1; shift; timeout 600 python bench.py --full --cpu-sample -1 "$@" > $O/$name.json 2>$O/$name.err; python - $O/$name.json $name <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d["roofline"]

@@ -14,7 +14,7 @@ for ctrs in "SQ_ACTIVE_INST_VALU SQ_INST_CYCLES_VALU SQ_ACTIVE_INST_SCA SQ_ACTIV
             "SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_LDS_MEM_VIOLATIONS SQ_LDS_ATOMIC_RETURN"; do
   i=$((i+1))
   timeout 300 rocprofv3 --pmc $ctrs -d $O/pmcx_$i -o p --output-format csv -- \
-      python3 $R/bench.py --cpu-sample -1 --steps 3 --warmup 1 "$@" > $O/pmcx_$i.log 2>&1
+      python3 $R/bench.py --full --cpu-sample -1 --steps 3 --warmup 1 "$@" > $O/pmcx_$i.log 2>&1
 done
 python3 - $O <<'PY'
 import csv,glob,sys,collections

@@ -6,10 +6,10 @@ O=$R/gpurun_out/$tag; mkdir -p $O
 cd $R
 timeout 900 python3 -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "$K" > $O/pytest_subset.log 2>&1
 tail -3 $O/pytest_subset.log
-timeout 600 python3 bench.py --cpu-sample -1 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
-timeout 600 python3 bench.py --cpu-sample -1 --indels > $O/bench_cfg4.json 2> $O/bench_cfg4.err
-timeout 600 python3 bench.py --cpu-sample -1 --refs 1000000 --queries 1000000 -d 0 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
-timeout 600 python3 bench.py --cpu-sample -1 --law cdr3 > $O/bench_cdr3.json 2> $O/bench_cdr3.err
+timeout 600 python3 bench.py --full --cpu-sample -1 > $O/bench_cfg3.json 2> $O/bench_cfg3.err
+timeout 600 python3 bench.py --full --cpu-sample -1 --indels > $O/bench_cfg4.json 2> $O/bench_cfg4.err
+timeout 600 python3 bench.py --full --cpu-sample -1 --refs 1000000 --queries 1000000 -d 0 > $O/bench_cfg2.json 2> $O/bench_cfg2.err
+timeout 600 python3 bench.py --full --cpu-sample -1 --law cdr3 > $O/bench_cdr3.json 2> $O/bench_cdr3.err
 for f in $O/bench_*.json; do echo $f; python3 - $f <<'PY'
 import json,sys
 try:

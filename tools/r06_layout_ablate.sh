@@ -9,7 +9,7 @@ cd $R
 NOITEMS=$((131072+8388608))
 for dbg in 0 65536 $NOITEMS $((NOITEMS+65536)) $((NOITEMS+262144)) $((NOITEMS+524288)) $((NOITEMS+1048576)) $((NOITEMS+2097152)) $((NOITEMS+4128768-131072)) \
            4194304 8388608 16777216 33554432 67108864 $((4194304+8388608)) $((4194304+8388608+67108864)); do
-  timeout 300 python3 bench.py --cpu-sample -1 --steps 5 --warmup 2 --tunable debug=$dbg "$@" > $O/b.json 2> $O/b.err
+  timeout 300 python3 bench.py --full --cpu-sample -1 --steps 5 --warmup 2 --tunable debug=$dbg "$@" > $O/b.json 2> $O/b.err
   python3 - $O/b.json $dbg <<'PY'
 import json,sys
 names={65536:"NO_RANK",131072:"NO_ITEM_COUNT",262144:"NO_HASH",524288:"NO_TOTALS",1048576:"NO_CLASSKEY",2097152:"NO_TMP_WRITES",

@@ -14,7 +14,7 @@ for ctrs in "FETCH_SIZE" "WRITE_SIZE" \
             "TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum TCP_TCC_ATOMIC_WITH_RET_REQ_sum TCC_EA0_ATOMIC_sum"; do
   i=$((i+1))
   timeout 600 rocprofv3 --pmc $ctrs -d $O/pmc_$i -o p --output-format csv -- \
-      python3 $R/bench.py --cpu-sample -1 --steps 3 --warmup 1 "$@" > $O/pmc_$i.log 2>&1
+      python3 $R/bench.py --full --cpu-sample -1 --steps 3 --warmup 1 "$@" > $O/pmc_$i.log 2>&1
 done
 python3 - $O <<'PY'
 import csv,glob,sys,collections

@@ -4,7 +4,7 @@
 tag=${1:-r06_rh}
 O=gpurun_out/$tag; mkdir -p $O
 timeout 1200 python3 -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "adversarial or synthetic_aa or d0 or ragged or long_seq or existence or pairs_list or work_shards or routed or device_resident or full_size_matches or repeated_launches or wrap or golden" > $O/pytest.log 2>&1; tail -3 $O/pytest.log
-B="timeout 600 python3 bench.py --cpu-sample -1"
+B="timeout 600 python3 bench.py --full --cpu-sample -1"
 for rt in 1 2 0; do
   $B --tunable record_tiles=$rt > $O/cfg3_rt$rt.json 2> $O/cfg3_rt$rt.err
   $B --indels --tunable record_tiles=$rt > $O/cfg4_rt$rt.json 2> $O/cfg4_rt$rt.err

@@ -13,10 +13,11 @@ tools/profile_all.sh $t > /dev/null 2>&1
 tools/summarise_round.sh $t > gpurun_out/${t}_cal/summarise.txt 2>&1
 tail -6 gpurun_out/${t}_cal/summarise.txt
 for w in cfg3 cfg2 cfg4 cfg5; do mkdir -p gpurun_out/${t}_$w; done
-timeout 900 python3 bench.py > gpurun_out/${t}_cfg3/bench.json 2> gpurun_out/${t}_cfg3/bench.err
-timeout 900 python3 bench.py --refs 1000000 --queries 1000000 --differences 0 > gpurun_out/${t}_cfg2/bench.json 2> gpurun_out/${t}_cfg2/bench.err
-timeout 900 python3 bench.py --indels > gpurun_out/${t}_cfg4/bench.json 2> gpurun_out/${t}_cfg4/bench.err
-timeout 1800 python3 bench.py --nucleotides --ignore-genes --differences 2 --refs 100000000 --queries 12500000 --steps 2 --warmup 1 --cpu-refs 10000000 --cpu-sample 20000 > gpurun_out/${t}_cfg5/bench.json 2> gpurun_out/${t}_cfg5/bench.err
+BENCH_ONLY=1 tools/profile_round.sh ${t}_cfg3 > /dev/null 2>&1
+BENCH_ONLY=1 tools/profile_round.sh ${t}_cfg2 --refs 1000000 --queries 1000000 --differences 0 > /dev/null 2>&1
+BENCH_ONLY=1 tools/profile_round.sh ${t}_cfg4 --indels > /dev/null 2>&1
+BENCH_ONLY=1 BENCH_TIMEOUT=1800 tools/profile_round.sh ${t}_cfg5 --nucleotides --ignore-genes --differences 2 --refs 100000000 --queries 12500000 \
+    --steps 2 --warmup 1 --cpu-refs 10000000 --cpu-sample 20000 > /dev/null 2>&1
 line() {
 python3 - $1 "$2" <<'PY'
 import json,sys
@@ -35,7 +36,7 @@ PY
 for w in cfg3 cfg2 cfg4 cfg5; do line gpurun_out/${t}_$w/bench.json $w; done
 echo "elapsed $SECONDS s"
 O=gpurun_out/${t}_extra
-B="timeout 1500 python3 bench.py"
+B="timeout 1500 python3 bench.py --full"
 $B --self > $O/self.json 2> $O/self.err; line $O/self.json "self 10M d=1"
 $B --law cdr3 > $O/cdr3_d1.json 2> $O/cdr3_d1.err; line $O/cdr3_d1.json "cdr3 d=1"
 $B --law cdr3 --indels > $O/cdr3_d1i.json 2> $O/cdr3_d1i.err; line $O/cdr3_d1i.json "cdr3 d=1 -i"

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/$1; mkdir -p $O
 run() {  # name, bench args...
   local name=$1; shift
-  timeout 1500 python bench.py --cpu-sample -1 "$@" > $O/$name.json 2> $O/$name.err
+  timeout 1500 python bench.py --full --cpu-sample -1 "$@" > $O/$name.json 2> $O/$name.err
   python - $O/$name.json $name <<'PY'
 import json,sys
 try:

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace -d $O/tr -o p --output-format csv -- \
-  python3 $R/bench.py --cpu-sample -1 --steps 10 --warmup 3 "$@" > $O/bench.json 2> $O/err.log
+  python3 $R/bench.py --full --cpu-sample -1 --steps 10 --warmup 3 "$@" > $O/bench.json 2> $O/err.log
 python3 - $O/tr <<'PY'
 import csv,glob,sys
 rows=[]

@@ -9,7 +9,7 @@ for cfg in "$@"; do
   for kv in $cfg; do
     case "$kv" in --*) args="$args $kv";; *) args="$args --tunable $kv";; esac
   done
-  timeout 300 python bench.py --steps 10 --warmup 3 --cpu-sample -1 $args > $O/run$i.json 2>$O/run$i.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --cpu-sample -1 $args > $O/run$i.json 2>$O/run$i.err
   python - "$cfg" $O/run$i.json <<'PY'
 import json,sys
 try:

@@ -236,6 +236,11 @@ extern "C" int cmpr_create(const cmpr_options *options, cmpr_context **out)
     if (v >= 1 && v <= 13)
       c->slice_words_log2 = v;
   }
+  if (const char *e = getenv("COMPAIRR_HIP_PART_BUCKETS_LOG2")) {
+    int v = atoi(e);
+    if (v >= 2 && v <= 30)
+      c->part_buckets_log2 = v;
+  }
   if (const char *e = getenv("COMPAIRR_HIP_CLASS_RESIDUES")) {
     int v = atoi(e);
     if (v >= -1 && v <= (int)max_class_res((uint32_t)c->opt.alphabet_size))
@@ -259,6 +264,10 @@ extern "C" void cmpr_destroy(cmpr_context *c)
   c->page_tab.release();
   c->bloom.release(); c->v2.release(); c->j2.release(); c->rep2.release();
   c->rec2.release(); c->voff2.release(); c->bmap2.release();
+  for (RefPart &p : c->xparts)
+    p.release();
+  c->xparts.clear();
+  c->stats_acc.release();
   c->tiles.release(); c->qres.release(); c->qv.release(); c->qj.release(); c->qgh.release();
   c->qlen.release(); c->qck.release();
   c->qhins.release(); c->qhdel.release(); c->items.release(); c->cpk.release(); c->qpk.release(); c->slice_items.release(); c->qrec.release();
@@ -373,6 +382,12 @@ static int set_tunable_value(cmpr_context *c, const std::string &n, int64_t valu
     if (c->have_ref)
       return fail(c, CMPR_ESTATE, "set table_log2_delta before cmpr_set_reference");
     c->table_log2_delta = value;
+  } else if (n == "part_buckets_log2") {
+    if (value < 2 || value > 30)
+      return fail(c, CMPR_EINVAL, "part_buckets_log2 must be 2..30");
+    if (c->have_ref)
+      return fail(c, CMPR_ESTATE, "set part_buckets_log2 before cmpr_set_reference");
+    c->part_buckets_log2 = value;
   } else if (n == "deferred_resolve") {
     if (value < 0 || value > 1)
       return fail(c, CMPR_EINVAL, "deferred_resolve must be 0 or 1");
@@ -563,6 +578,8 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "class_rows_unstaged") *value = c->class_rows_unstaged;
   else if (n == "deferred_resolve") *value = c->deferred_resolve;
   else if (n == "table_log2_delta") *value = c->table_log2_delta;
+  else if (n == "part_buckets_log2") *value = c->part_buckets_log2;
+  else if (n == "reference_parts") *value = c->have_ref ? (int64_t)c->nparts : 0;
   else if (n == "row_filter_x16") *value = c->row_filter_x16;
   else if (n == "fill_slices") *value = c->fill_slices;
   else if (n == "direct_slices_log2") *value = c->direct_slices_log2;
@@ -588,6 +605,37 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
 #endif
   else
     return fail(c, CMPR_EINVAL, "unknown tunable: " + n);
+  return CMPR_OK;
+}
+
+/* duplicates of a set in parts: part p's entries against the tables of parts 0 .. p (kernels.h
+   count_duplicates_parts_kernel); D names the set (global arrays) and the counter, cleared */
+static int count_duplicates_in_parts(cmpr_context *c, const DupParams &D, const std::vector<DupTable> &tabs,
+                                     const std::vector<uint64_t> &first, uint64_t *out)
+{
+  int rc;
+  DevBuf<DupTable> d_tabs;
+  struct Tc { DevBuf<DupTable> &t; ~Tc() { t.release(); } } tclean{d_tabs};
+  if ((rc = dev_upload(c, d_tabs, tabs.data(), tabs.size()))) return rc;
+  DupPartsParams B{};
+  B.zob = D.zob; B.A = D.A; B.zpos = D.zpos; B.n_v = D.n_v; B.use_genes = D.use_genes;
+  B.res = D.res; B.off = D.off; B.v = D.v; B.j = D.j; B.rep = D.rep;
+  B.tables = d_tabs.p;
+  B.count = D.count;
+  for (size_t p = 0; p < tabs.size(); p++) {
+    B.first = first[p];
+    B.n = first[p + 1] - first[p];
+    B.ntables = (uint32_t)p + 1;
+    if (B.n) {
+      hipLaunchKernelGGL(count_duplicates_parts_kernel, dim3((uint32_t)((B.n + BLOCK_THREADS - 1) / BLOCK_THREADS)),
+                         dim3(BLOCK_THREADS), 0, c->stream, B);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  unsigned long long hc = 0;
+  HIP_TRY(c, hipMemcpyAsync(&hc, D.count, sizeof hc, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *out = hc;
   return CMPR_OK;
 }
 
@@ -628,6 +676,21 @@ static int cmpr_count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, u
     D.n = c->n2;
     D.rec = c->rec2.p;
     D.dir_mask = (uint32_t)(c->slots - 1);
+    if (c->nparts > 1) {
+      /* set 2 in parts: each part's entries looked up in the record tables of it and of the parts before */
+      std::vector<DupTable> tabs(c->nparts);
+      std::vector<uint64_t> first(c->nparts + 1);
+      tabs[0] = DupTable{c->rec2.p, c->slots - 1, 0, 1u, 0u};
+      first[0] = 0;
+      for (uint32_t k = 1; k < c->nparts; k++) {
+        const RefPart &rp = c->xparts[k - 1];
+        tabs[k] = DupTable{rp.rec.p, rp.slots - 1, 0, 1u, 0u};
+        first[k] = rp.first;
+      }
+      first[c->nparts] = c->n2;
+      if ((rc = count_duplicates_in_parts(c, D, tabs, first, out))) return rc;
+      return CMPR_OK;
+    }
   } else {
     std::string why;
     if ((rc = validate_view(c->opt, s, why)))
@@ -654,6 +717,44 @@ static int cmpr_count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, u
       if ((rc = dev_upload(c, zob_own, z.data(), z.size()))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
       zob = zob_own.p;
+    }
+    D.zob = zob; D.zpos = zpos;
+    D.res = res.p; D.off = off.p; D.v = v.p; D.j = j.p; D.rep = rep.p;
+    D.n = s->n;
+    /* a set larger than one table of at most 2^part_buckets_log2 slots: a table per contiguous part */
+    const uint64_t per_part = (uint64_t)FILL_PERCENT * (1ull << c->part_buckets_log2) / 100;
+    const uint64_t nparts = s->n > per_part ? (s->n + per_part - 1) / per_part : 1;
+    if (nparts > 65536)
+      return fail(c, CMPR_EUNSUPPORTED, "set needs more than 65536 parts (part_buckets_log2)");
+    if (nparts > 1) {
+      std::vector<DevBuf<Slot>> tables((size_t)nparts);
+      struct Tt { std::vector<DevBuf<Slot>> &t; ~Tt() { for (auto &x : t) x.release(); } } ttclean{tables};
+      std::vector<DupTable> tabs((size_t)nparts);
+      std::vector<uint64_t> first((size_t)nparts + 1);
+      const uint64_t q = s->n / nparts, r = s->n % nparts;
+      for (uint64_t p = 0; p <= nparts; p++)
+        first[(size_t)p] = p * q + std::min(p, r);
+      for (uint64_t p = 0; p < nparts; p++) {
+        const uint64_t f = first[(size_t)p], n = first[(size_t)p + 1] - f;
+        uint64_t ps = 1;
+        while (FILL_PERCENT * ps < 100 * n)
+          ps <<= 1;
+        ps = std::max<uint64_t>(ps, 4);
+        if ((rc = dev_alloc(c, tables[(size_t)p], (size_t)ps))) return rc;
+        HIP_TRY(c, hipMemsetAsync(tables[(size_t)p].p, 0xff, ps * sizeof(Slot), c->stream));
+        BuildParams B{};
+        B.zob = zob; B.A = A; B.zpos = zpos; B.n_v = n_v; B.use_genes = D.use_genes;
+        B.res = res.p; B.off = off.p + f; B.v = v.p ? v.p + f : nullptr; B.j = j.p ? j.p + f : nullptr; B.n = n;
+        B.table = tables[(size_t)p].p; B.slot_mask = ps - 1;
+        B.bloom = nullptr; B.bloom_byte_mask = 0; B.sliced = 0;   /* table only */
+        if (n) {
+          hipLaunchKernelGGL(build_index_kernel, dim3((uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS)),
+                             dim3(BLOCK_THREADS), 0, c->stream, B);
+          HIP_TRY(c, hipGetLastError());
+        }
+        tabs[(size_t)p] = DupTable{tables[(size_t)p].p, ps - 1, f, 0u, 0u};
+      }
+      return count_duplicates_in_parts(c, D, tabs, first, out);
     }
     uint64_t slots = 1;
     while (FILL_PERCENT * slots < 100 * s->n)
@@ -814,6 +915,17 @@ static int cmpr_set_queries_impl(cmpr_context *c, const LayoutSource &src_in)
 /* the per-query loop                                                    */
 /* ------------------------------------------------------------------ */
 
+/* set 2 in parts: the counters of one part's pass added to the step's (those of the redo pass where it did
+   the pass, as cmpr_get_stats reads them) */
+static __global__ void __launch_bounds__(WAVE)
+sum_part_stats_kernel(const unsigned long long *stats, const unsigned long long *overflow,
+                      const unsigned long long *stats2, unsigned long long *acc)
+{
+  const uint32_t k = threadIdx.x;
+  if (k < STAT_COUNT)
+    acc[k] += (overflow && *overflow) ? stats2[k] : stats[k];
+}
+
 namespace {
 
 /* the counter block a launch works with (block 0 or 1 of pos_ctr's allocation) */
@@ -852,7 +964,8 @@ int make_plan(cmpr_context *c)
   /* (variant 2 resolving inline adds to the matrix where it lies: cleared before, not
      written by the reduce kernel) */
   const bool rows_inline = c->rows && !c->d2pairs && !S.deferred;
-  S.reduce_writes = S.will_launch && cells <= 2048 && !is_f64_score(c->opt) && !rows_inline;
+  /* (set 2 in parts: every part's pass adds to the matrix cleared before the first) */
+  S.reduce_writes = S.will_launch && cells <= 2048 && !is_f64_score(c->opt) && !rows_inline && c->nparts == 1;
   /* (kernels_pairs2.h resolves what does not fit its buffer inline: no redo launch) */
   S.redo_kind = c->rows && !c->d2pairs && S.deferred && !(c->debug & DBG_SKIP_RESOLVE);
   S.nw = c->sliced ? (uint32_t)c->waves_per_block : WAVES_PER_BLOCK;
@@ -1068,72 +1181,98 @@ int issue_step(cmpr_context *c, const StepArgs &a, hipStream_t st, hipEvent_t ev
   }
   if (!S.will_launch) {                       /* (nobody will clear the other block) */
     HIP_TRY(c, hipMemsetAsync(c->ctr_other, 0, S.ctr_blk * sizeof(unsigned long long), st));
+    if (c->nparts > 1)                        /* (what cmpr_get_stats reads of a step in parts) */
+      HIP_TRY(c, hipMemsetAsync(c->stats_acc.p, 0, STAT_COUNT * sizeof(unsigned long long), st));
     if (ev_km)
       HIP_TRY(c, hipEventRecord(ev_km, st));
     c->launches = 0;
     return CMPR_OK;
   }
-  ProbeParams P = S.P;
-  P.matrix = a.d_out;
-  P.tile_counter = c->d_tile_counter;
-  P.deal_ctr = c->d_deal;
-  P.stats = c->d_stats;
-  P.pair_q = c->pair_q;
-  P.pair_h = c->pair_h;
-  P.pair_count = c->pair_count;
-  P.pair_cap = c->pair_cap;
-  if (S.deferred)
-    P.pos_ctr = c->ctr_cur;
-  if (c->rows && S.deferred)
-    P.overflow = c->d_overflow;
+  /* Set 2 in parts (ref_index.hip): one pass of the same kernels per part, each on a counter block of its
+     own (the one the previous pass's reduce kernel cleared), adding to the matrix; the counters of the
+     passes are summed into stats_acc. */
+  const uint32_t np = c->nparts;
+  if (np > 1)
+    HIP_TRY(c, hipMemsetAsync(c->stats_acc.p, 0, STAT_COUNT * sizeof(unsigned long long), st));
+  const bool resolve_pass = S.deferred && !(c->debug & DBG_SKIP_RESOLVE);
   /* a launch of variant 2 without redo pass leaves word of an overflow behind */
   unsigned long long *sticky = (S.redo_kind && !a.with_redo) ? c->d_usage + 1 : nullptr;
-  hipLaunchKernelGGL(S.fn, dim3(S.grid), dim3(S.nw * WAVE), S.lds, st, P);
-  HIP_TRY(c, hipGetLastError());
-  c->launches = 1;
-  if (ev_km)
-    HIP_TRY(c, hipEventRecord(ev_km, st));
-  if (a.track_usage)
-    HIP_TRY(c, hipMemsetAsync(c->d_usage, 0, sizeof(unsigned long long), st));
-  auto reduce_partials = [&]() {
-    hipLaunchKernelGGL(reduce_partials_kernel, dim3(P.part_stride), dim3(NPART), 0, st, P,
-                       P.part_cells, S.reduce_writes ? 1u : 0u, c->ctr_other,
-                       (uint32_t)S.ctr_blk, a.track_usage ? c->d_usage : nullptr, sticky);
-  };
-  const bool resolve_pass = S.deferred && !(c->debug & DBG_SKIP_RESOLVE);
-  if (!resolve_pass) {
-    reduce_partials();
+  uint32_t launches = 0;
+  for (uint32_t k = 0; k < np; k++) {
+    ProbeParams P = S.P;
+    if (k > 0) {
+      use_counter_block(c, c->ctr_cur == c->pos_ctr.p ? 1 : 0);
+      const RefPart &rp = c->xparts[k - 1];
+      P.bloom = rp.bloom.p;
+      P.dir_mask = (uint32_t)(rp.slots - 1);
+      P.bmap = S.P.bmap ? rp.bmap.p : nullptr;
+      P.rec2 = rp.rec.p;
+    }
+    P.matrix = a.d_out;
+    P.tile_counter = c->d_tile_counter;
+    P.deal_ctr = c->d_deal;
+    P.stats = c->d_stats;
+    P.pair_q = c->pair_q;
+    P.pair_h = c->pair_h;
+    P.pair_count = c->pair_count;
+    P.pair_cap = c->pair_cap;
+    if (S.deferred)
+      P.pos_ctr = c->ctr_cur;
+    if (c->rows && S.deferred)
+      P.overflow = c->d_overflow;
+    hipLaunchKernelGGL(S.fn, dim3(S.grid), dim3(S.nw * WAVE), S.lds, st, P);
     HIP_TRY(c, hipGetLastError());
-    return CMPR_OK;
+    launches += 1;
+    if (ev_km && k + 1 == np)
+      HIP_TRY(c, hipEventRecord(ev_km, st));
+    /* (the fullest segment of any part's pass: every pass has the whole buffer) */
+    if (a.track_usage && k == 0)
+      HIP_TRY(c, hipMemsetAsync(c->d_usage, 0, sizeof(unsigned long long), st));
+    auto reduce_partials = [&]() {
+      hipLaunchKernelGGL(reduce_partials_kernel, dim3(P.part_stride), dim3(NPART), 0, st, P,
+                         P.part_cells, S.reduce_writes ? 1u : 0u, c->ctr_other,
+                         (uint32_t)S.ctr_blk, a.track_usage ? c->d_usage : nullptr, sticky);
+    };
+    if (!resolve_pass) {
+      reduce_partials();
+      HIP_TRY(c, hipGetLastError());
+    } else {
+      hipLaunchKernelGGL(S.rfn, dim3(S.rgrid), dim3(BLOCK_THREADS), S.rlds, st, P);
+      reduce_partials();
+      HIP_TRY(c, hipGetLastError());
+      launches += 1;
+      if (a.track_usage && k + 1 == np) {
+        HIP_TRY(c, hipMemcpyAsync(c->h_usage, c->d_usage, sizeof(unsigned long long),
+                                  hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipEventRecord(c->ev_usage, st));
+        c->usage_pending = true;
+        c->usage_grid = S.grid;
+        c->usage_nw = S.nw;
+      }
+      if (a.with_redo) {
+        /* Redo pass: if the positives of the fast launch did not fit their buffer
+           (flag set: resolve_kernel then did nothing), the same step with every
+           positive resolved inline; otherwise its workgroups return at once.
+           Capacity is therefore never a limit, and nothing here waits for the host. */
+        ProbeParams P2 = P;
+        P2.pos_buf = nullptr;
+        P2.part = nullptr;                  /* (straight into matrix and stats2) */
+        P2.redo = 1;
+        P2.stats = c->d_stats2;
+        P2.tile_counter = c->d_tile_counter2;
+          P2.deal_ctr = c->d_deal + DEAL_WORDS / 2;
+        hipLaunchKernelGGL(S.fn2, dim3(S.grid), dim3(S.nw * WAVE), S.lds, st, P2);
+        HIP_TRY(c, hipGetLastError());
+        launches += 1;
+      }
+    }
+    if (np > 1) {
+      hipLaunchKernelGGL(sum_part_stats_kernel, dim3(1), dim3(WAVE), 0, st, c->d_stats,
+                         S.redo_kind ? c->d_overflow : nullptr, c->d_stats2, c->stats_acc.p);
+      HIP_TRY(c, hipGetLastError());
+    }
   }
-  hipLaunchKernelGGL(S.rfn, dim3(S.rgrid), dim3(BLOCK_THREADS), S.rlds, st, P);
-  reduce_partials();
-  HIP_TRY(c, hipGetLastError());
-  c->launches = 2;
-  if (a.track_usage) {
-    HIP_TRY(c, hipMemcpyAsync(c->h_usage, c->d_usage, sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, st));
-    HIP_TRY(c, hipEventRecord(c->ev_usage, st));
-    c->usage_pending = true;
-    c->usage_grid = S.grid;
-    c->usage_nw = S.nw;
-  }
-  if (a.with_redo) {
-    /* Redo pass: if the positives of the fast launch did not fit their buffer
-       (flag set: resolve_kernel then did nothing), the same step with every
-       positive resolved inline; otherwise its workgroups return at once.
-       Capacity is therefore never a limit, and nothing here waits for the host. */
-    ProbeParams P2 = P;
-    P2.pos_buf = nullptr;
-    P2.part = nullptr;                  /* (straight into matrix and stats2) */
-    P2.redo = 1;
-    P2.stats = c->d_stats2;
-    P2.tile_counter = c->d_tile_counter2;
-      P2.deal_ctr = c->d_deal + DEAL_WORDS / 2;
-    hipLaunchKernelGGL(S.fn2, dim3(S.grid), dim3(S.nw * WAVE), S.lds, st, P2);
-    HIP_TRY(c, hipGetLastError());
-    c->launches = 3;
-  }
+  c->launches = launches;
   return CMPR_OK;
 }
 
@@ -1491,7 +1630,9 @@ extern "C" int cmpr_get_stats(cmpr_context *c, cmpr_stats *out)
     return fail(c, CMPR_ESTATE, "positives buffer overflowed in a launch without redo pass: result invalid, "
                                 "repeat the call");
   }
-  if (ovf)       /* the positives buffer overflowed: the redo pass did the step */
+  if (c->nparts > 1)    /* set 2 in parts: the sum over the passes (issue_step) */
+    HIP_TRY(c, hipMemcpy(st, c->stats_acc.p, sizeof st, hipMemcpyDeviceToHost));
+  else if (ovf)  /* the positives buffer overflowed: the redo pass did the step */
     HIP_TRY(c, hipMemcpy(st, c->d_stats2, sizeof st, hipMemcpyDeviceToHost));
   float k_ms = 0, t_ms = 0;
   HIP_TRY(c, hipEventElapsedTime(&k_ms, c->ev_k0, c->ev_k1));

@@ -111,6 +111,23 @@ struct RouteState {
   unsigned long long *dest = nullptr;    /* [64] counts | [64] fill cursors */
 };
 
+/* A part of set 2 beyond the first (ref_index.hip): its own filter words, record table and bucket bitmap
+   over the sequences first .. first + n - 1, built with the geometry of the whole set; RefRec::idx holds
+   the global sequence number.  Part 0 lives in cmpr_context's own bloom / rec2 / bmap2 / slots. */
+struct RefPart {
+  uint64_t              first = 0, n = 0;
+  uint64_t              slots = 0;      /* buckets of its record table (a power of two) */
+  DevBuf<uint64_t>      bloom;
+  DevBuf<unsigned char> rec;
+  DevBuf<uint32_t>      bmap;
+  void release()
+  {
+    bloom.release();
+    rec.release();
+    bmap.release();
+  }
+};
+
 struct cmpr_context {
   cmpr_options opt{};
   int          device = 0;
@@ -201,6 +218,13 @@ struct cmpr_context {
   DevBuf<unsigned char> rec2;      /* the record table (layout.h RefRec; ref_index.hip) */
   DevBuf<uint32_t>  voff2;          /* slot of sequence i in it */
   uint64_t          slots = 0, bloom_words = 0;     /* slots: buckets of the record table (a power of two) */
+  /* set 2 in parts (ref_index.hip): when one record table cannot hold it, contiguous sequence ranges, each
+     with its own filter words, records and bitmap; everything the query layout reads is shared */
+  int64_t           part_buckets_log2 = 30;   /* tunable: the most buckets of one part's record table */
+  uint32_t          nparts = 1;
+  uint64_t          part0_n = 0;              /* sequences of part 0 (first 0) */
+  std::vector<RefPart> xparts;                /* parts 1 .. nparts - 1 */
+  DevBuf<unsigned long long> stats_acc;       /* nparts > 1: the counters of a step, summed over its parts */
 
   /* set 1 tiles */
   bool              have_q = false;

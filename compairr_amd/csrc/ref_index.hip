@@ -181,6 +181,58 @@ struct WidenU32 {
   __host__ __device__ unsigned long long operator()(const uint32_t &x) const { return x; }
 };
 
+/* buckets of the record table of n sequences: the smallest power of two that is at most 70 % full
+   (hash_init, hashtable.cc:24, 36-38), x 2^delta, at least 4 */
+uint64_t table_buckets(uint64_t n, int64_t delta)
+{
+  uint64_t s = 1;
+  while (FILL_PERCENT * s < 100 * n)
+    s <<= 1;
+  return std::max<uint64_t>(s << delta, 4);
+}
+
+/* the most sequences one part may hold when its table may have at most 2^log2 buckets (0: none);
+   at most 2^31 - 1, because hipCUB's item counts are int */
+uint64_t part_capacity(int64_t log2, int64_t delta)
+{
+  if (log2 < 2 || log2 < delta)
+    return 0;
+  const uint64_t s = 1ull << (log2 - delta);
+  return std::min<uint64_t>(FILL_PERCENT * s / 100, 0x7fffffffull);
+}
+
+constexpr uint64_t MAX_PARTS = 65536;
+
+/* Parts of a set of n sequences (1: it fits one table; 0: part_buckets_log2 holds no sequence; MAX_PARTS + 1:
+   more parts than that).  Beyond one, the count with the fewest table bytes in all: tables are powers of
+   two, so three parts may need less than two. */
+uint64_t choose_parts(uint64_t n, int64_t log2, int64_t delta)
+{
+  const uint64_t m0 = part_capacity(log2, delta);
+  if (m0 == 0)
+    return 0;
+  if (n <= m0)
+    return 1;
+  uint64_t best = 0, best_total = 0;
+  for (int64_t k = 0; k < 4; k++) {
+    const uint64_t m = part_capacity(log2 - k, delta);
+    if (m == 0)
+      break;
+    const uint64_t P = (n + m - 1) / m;
+    if (P > MAX_PARTS) {
+      if (k == 0)
+        return MAX_PARTS + 1;
+      break;
+    }
+    const uint64_t total = P * table_buckets((n + P - 1) / P, delta);
+    if (best == 0 || total < best_total) {
+      best = P;
+      best_total = total;
+    }
+  }
+  return best;
+}
+
 }  // namespace
 
 int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longest_query, bool on_device)
@@ -197,8 +249,20 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
     HIP_TRY(c, hipEventSynchronize(c->ev_k1));
   c->have_ref = false;
   c->have_q = false;
-  if (s->n > 0x7fffffffull)                               /* (hipCUB item counts are int) */
-    return fail(c, CMPR_EUNSUPPORTED, "more than 2^31-1 sequences in one set");
+  for (RefPart &p : c->xparts)
+    p.release();
+  c->xparts.clear();
+  c->nparts = 1;
+  c->part0_n = 0;
+  c->stats_acc.release();
+  if (s->n > 0xffffffffull - 63)                          /* (pair lists hold uint32 sequence numbers) */
+    return fail(c, CMPR_EUNSUPPORTED, "more than 2^32-64 sequences in one set");
+  /* set 2 in parts: contiguous ranges, each within one record table (choose_parts) */
+  const uint64_t nparts = choose_parts(s->n, c->part_buckets_log2, c->table_log2_delta);
+  if (nparts == 0)
+    return fail(c, CMPR_EINVAL, "part_buckets_log2 below table_log2_delta");
+  if (nparts > MAX_PARTS)
+    return fail(c, CMPR_EUNSUPPORTED, "reference set needs more than 65536 parts (part_buckets_log2)");
   /* residues in all: offsets[n], which a device view keeps on the device */
   uint64_t residues2 = 0;
   if (s->n && !on_device) {
@@ -382,6 +446,10 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
       bloom_bytes <<= delta;
     else if (delta < 0)
       bloom_bytes = std::max<uint64_t>(bloom_bytes >> (-delta), 8);
+    /* (set 2 in parts: every part's filter is this size and holds only its part; a filter at the 32-bit byte
+       mask is denser than asked for, never wrong -- every hit is verified) */
+    if (nparts > 1)
+      bloom_bytes = std::min<uint64_t>(bloom_bytes, 1ull << 32);
     if (bloom_bytes > (1ull << 32))
       return fail(c, CMPR_EUNSUPPORTED, "Bloom filter larger than 4 GiB");
     c->bloom_words = bloom_bytes / 8;
@@ -651,124 +719,156 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
     }
     c->bloom_words = (nsl + c->page_slices) * c->geom.rw_words * (ROW_WORD_BYTES / 8);
   }
-  if (c->slots > (1ull << 30))
-    return fail(c, CMPR_EUNSUPPORTED, "reference set too large for a 32-bit record table");
   /* d = 0 on the un-sliced kernel looks every query up where its bucket lies (kernels.h probe_kernel, D == 0):
      no filter is read, none is built (it was sized, cleared and filled for nothing) */
   const bool no_filter = !c->sliced && c->opt.differences == 0;
   if (no_filter)
     c->bloom_words = 1;
-  if ((rc = dev_alloc(c, c->bloom, (size_t)c->bloom_words))) return rc;
-  /* inverted polarity (bloompat.cc:54-57) for variants 0, 1; the row filter sets bits */
-  HIP_TRY(c, hipMemsetAsync(c->bloom.p, c->rows ? 0 : 0xff, c->bloom_words * sizeof(uint64_t), c->stream));
 
-  BuildParams B{};
-  B.zob = c->zob.p;
-  B.A = A;
-  B.zpos = c->zpos;
-  B.n_v = n_v;
-  B.use_genes = c->opt.ignore_genes ? 0u : 1u;
-  B.res = c->res2.p;
-  B.off = c->off2.p;
-  B.v = c->v2.p;
-  B.j = c->j2.p;
-  B.n = s->n;
-  Tmp<uint32_t> tags, buckets, more;
-  {
-    /* The record table (see ref_keys_kernel): bucket and tag of every sequence, a stable radix sort of
-       the sequence numbers by bucket, the prefix maximum that places the records, the table itself. */
-    Tmp<uint32_t> seq, bkt_sorted, perm, last;
-    Tmp<int32_t> lead, lead_max;
-    Tmp<char> tmp;
-    uint64_t nslots = c->slots + 1;             /* (a lookup may start at any bucket; one empty slot behind the last) */
-    if ((rc = dev_alloc(c, c->voff2, std::max<size_t>((size_t)s->n, 1)))) return rc;
-    if (s->n) {
-      const size_t n = (size_t)s->n;
-      if ((rc = dev_alloc(c, buckets.b, n))) return rc;
-      if ((rc = dev_alloc(c, seq.b, n))) return rc;
-      if ((rc = dev_alloc(c, tags.b, n))) return rc;
-      if ((rc = dev_alloc(c, more.b, n))) return rc;
-      if ((rc = dev_alloc(c, bkt_sorted.b, n))) return rc;
-      if ((rc = dev_alloc(c, perm.b, n))) return rc;
-      if ((rc = dev_alloc(c, last.b, 1))) return rc;
-      hipLaunchKernelGGL(ref_keys_kernel, dim3(blocks_for(s->n)), dim3(256), 0, c->stream, B,
-                         (uint32_t)(c->slots - 1), buckets.b.p, tags.b.p, seq.b.p);
-      HIP_TRY(c, hipGetLastError());
-      int bits = 0;
-      while ((1ull << bits) < c->slots)
-        bits++;
-      size_t tb = 0;
-      (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, buckets.b.p, bkt_sorted.b.p, seq.b.p, perm.b.p, (int)s->n,
-                                               0, std::max(bits, 1), c->stream);
-      if ((rc = dev_alloc(c, tmp.b, tb))) return rc;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(tmp.b.p, tb, buckets.b.p, bkt_sorted.b.p, seq.b.p, perm.b.p,
-                                                    (int)s->n, 0, std::max(bits, 1), c->stream));
-      if ((rc = dev_alloc(c, lead.b, n))) return rc;
-      if ((rc = dev_alloc(c, lead_max.b, n))) return rc;
-      hipLaunchKernelGGL(bucket_lead_kernel, dim3(blocks_for(s->n)), dim3(256), 0, c->stream, bkt_sorted.b.p,
-                         s->n, lead.b.p);
-      HIP_TRY(c, hipGetLastError());
-      size_t tb1 = 0;
-      (void)hipcub::DeviceScan::InclusiveScan(nullptr, tb1, lead.b.p, lead_max.b.p, MaxI32(), (int)s->n, c->stream);
-      if (tb1 > tb) {
-        if ((rc = dev_alloc(c, tmp.b, tb1))) return rc;
-        tb = tb1;
+  /* The index of the sequences first .. first + n - 1: filter words (the geometry above is the whole
+     set's, so one query layout serves every part), record table and bucket bitmap.  RefRec::idx holds
+     the global sequence number, so resolving a hit needs nothing of the part. */
+  auto build_part = [&](uint64_t first, uint64_t n, uint64_t slots, DevBuf<uint64_t> &bloom,
+                        DevBuf<unsigned char> &rec2, DevBuf<uint32_t> &bmap2, DevBuf<uint32_t> &voff2) -> int {
+    if (slots > (1ull << 30))
+      return fail(c, CMPR_EUNSUPPORTED, "reference set too large for a 32-bit record table");
+    if ((rc = dev_alloc(c, bloom, (size_t)c->bloom_words))) return rc;
+    /* inverted polarity (bloompat.cc:54-57) for variants 0, 1; the row filter sets bits */
+    HIP_TRY(c, hipMemsetAsync(bloom.p, c->rows ? 0 : 0xff, c->bloom_words * sizeof(uint64_t), c->stream));
+
+    BuildParams B{};
+    B.zob = c->zob.p;
+    B.A = A;
+    B.zpos = c->zpos;
+    B.n_v = n_v;
+    B.use_genes = c->opt.ignore_genes ? 0u : 1u;
+    B.res = c->res2.p;
+    B.off = c->off2.p + first;
+    B.v = c->v2.p ? c->v2.p + first : nullptr;
+    B.j = c->j2.p ? c->j2.p + first : nullptr;
+    B.n = n;
+    Tmp<uint32_t> tags, buckets, more;
+    {
+      /* The record table (see ref_keys_kernel): bucket and tag of every sequence, a stable radix sort of
+         the sequence numbers by bucket, the prefix maximum that places the records, the table itself. */
+      Tmp<uint32_t> seq, bkt_sorted, perm, last;
+      Tmp<int32_t> lead, lead_max;
+      Tmp<char> tmp;
+      uint64_t nslots = slots + 1;              /* (a lookup may start at any bucket; one empty slot behind the last) */
+      if ((rc = dev_alloc(c, voff2, std::max<size_t>((size_t)n, 1)))) return rc;
+      if (n) {
+        const size_t nn = (size_t)n;
+        if ((rc = dev_alloc(c, buckets.b, nn))) return rc;
+        if ((rc = dev_alloc(c, seq.b, nn))) return rc;
+        if ((rc = dev_alloc(c, tags.b, nn))) return rc;
+        if ((rc = dev_alloc(c, more.b, nn))) return rc;
+        if ((rc = dev_alloc(c, bkt_sorted.b, nn))) return rc;
+        if ((rc = dev_alloc(c, perm.b, nn))) return rc;
+        if ((rc = dev_alloc(c, last.b, 1))) return rc;
+        hipLaunchKernelGGL(ref_keys_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, B,
+                           (uint32_t)(slots - 1), buckets.b.p, tags.b.p, seq.b.p);
+        HIP_TRY(c, hipGetLastError());
+        int bits = 0;
+        while ((1ull << bits) < slots)
+          bits++;
+        size_t tb = 0;
+        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, tb, buckets.b.p, bkt_sorted.b.p, seq.b.p, perm.b.p, (int)n,
+                                                 0, std::max(bits, 1), c->stream);
+        if ((rc = dev_alloc(c, tmp.b, tb))) return rc;
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(tmp.b.p, tb, buckets.b.p, bkt_sorted.b.p, seq.b.p, perm.b.p,
+                                                      (int)n, 0, std::max(bits, 1), c->stream));
+        if ((rc = dev_alloc(c, lead.b, nn))) return rc;
+        if ((rc = dev_alloc(c, lead_max.b, nn))) return rc;
+        hipLaunchKernelGGL(bucket_lead_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, bkt_sorted.b.p,
+                           n, lead.b.p);
+        HIP_TRY(c, hipGetLastError());
+        size_t tb1 = 0;
+        (void)hipcub::DeviceScan::InclusiveScan(nullptr, tb1, lead.b.p, lead_max.b.p, MaxI32(), (int)n, c->stream);
+        if (tb1 > tb) {
+          if ((rc = dev_alloc(c, tmp.b, tb1))) return rc;
+          tb = tb1;
+        }
+        HIP_TRY(c, hipcub::DeviceScan::InclusiveScan(tmp.b.p, tb1, lead.b.p, lead_max.b.p, MaxI32(), (int)n,
+                                                     c->stream));
+        hipLaunchKernelGGL(record_slots_kernel, dim3(blocks_for(n)), dim3(256), 0, c->stream, bkt_sorted.b.p,
+                           lead_max.b.p, perm.b.p, n, voff2.p, more.b.p, last.b.p);
+        HIP_TRY(c, hipGetLastError());
+        uint32_t last_slot = 0;
+        HIP_TRY(c, hipMemcpyAsync(&last_slot, last.b.p, sizeof last_slot, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        nslots = std::max<uint64_t>(nslots, (uint64_t)last_slot + 2);
       }
-      HIP_TRY(c, hipcub::DeviceScan::InclusiveScan(tmp.b.p, tb1, lead.b.p, lead_max.b.p, MaxI32(), (int)s->n,
-                                                   c->stream));
-      hipLaunchKernelGGL(record_slots_kernel, dim3(blocks_for(s->n)), dim3(256), 0, c->stream, bkt_sorted.b.p,
-                         lead_max.b.p, perm.b.p, s->n, c->voff2.p, more.b.p, last.b.p);
+      if (nslots >> 32)
+        return fail(c, CMPR_EUNSUPPORTED, "reference set too large for 32-bit record positions");
+      if ((rc = dev_alloc(c, rec2, (size_t)nslots * sizeof(RefRec)))) return rc;
+      if ((rc = dev_alloc(c, bmap2, (size_t)(slots / 32 + 1)))) return rc;
+      HIP_TRY(c, hipMemsetAsync(bmap2.p, 0, (size_t)(slots / 32 + 1) * sizeof(uint32_t), c->stream));
+      /* (all ones: RefRec::idx of an empty slot) */
+      HIP_TRY(c, hipMemsetAsync(rec2.p, 0xff, (size_t)nslots * sizeof(RefRec), c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));     /* (the temporaries go away) */
+    }
+    if (n) {
+      B.bloom = c->rows ? nullptr : bloom.p;
+      B.bloom_byte_mask = (uint32_t)((c->bloom_words - 1) << 3);
+      B.sliced = c->sliced ? 1u : 0u;
+      B.indels = c->rows && c->opt.indels ? 1u : 0u;
+      B.pairs = pair_rows(c) ? 1u : 0u;
+      B.geom = c->geom;
+      const uint32_t grid = (uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
+      if (c->rows) {
+        B.bloom = bloom.p;
+        hipLaunchKernelGGL(build_rows_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, B);
+      } else if (!no_filter) {
+        /* (variants 0, 1: the per-variant filter; no table) */
+        hipLaunchKernelGGL(build_index_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, B);
+      }
       HIP_TRY(c, hipGetLastError());
-      uint32_t last_slot = 0;
-      HIP_TRY(c, hipMemcpyAsync(&last_slot, last.b.p, sizeof last_slot, hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      nslots = std::max<uint64_t>(nslots, (uint64_t)last_slot + 2);
     }
-    if (nslots >> 32)
-      return fail(c, CMPR_EUNSUPPORTED, "reference set too large for 32-bit record positions");
-    if ((rc = dev_alloc(c, c->rec2, (size_t)nslots * sizeof(RefRec)))) return rc;
-    if ((rc = dev_alloc(c, c->bmap2, (size_t)(c->slots / 32 + 1)))) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->bmap2.p, 0, (size_t)(c->slots / 32 + 1) * sizeof(uint32_t), c->stream));
-    /* (all ones: RefRec::idx of an empty slot) */
-    HIP_TRY(c, hipMemsetAsync(c->rec2.p, 0xff, (size_t)nslots * sizeof(RefRec), c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));     /* (the temporaries go away) */
-  }
-  if (s->n) {
-    B.bloom = c->rows ? nullptr : c->bloom.p;
-    B.bloom_byte_mask = (uint32_t)((c->bloom_words - 1) << 3);
-    B.sliced = c->sliced ? 1u : 0u;
-    B.indels = c->rows && c->opt.indels ? 1u : 0u;
-    B.pairs = pair_rows(c) ? 1u : 0u;
-    B.geom = c->geom;
-    const uint32_t grid = (uint32_t)((s->n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-    if (c->rows) {
-      B.bloom = c->bloom.p;
-      hipLaunchKernelGGL(build_rows_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, B);
-    } else if (!no_filter) {
-      /* (variants 0, 1: the per-variant filter; no table) */
-      hipLaunchKernelGGL(build_index_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, B);
+    if (n) {
+      PackParams K{};
+      K.voff = voff2.p;
+      K.res = c->res2.p;
+      K.off = c->off2.p + first;
+      K.cnt = c->opt.ignore_counts || !c->cnt2.p ? nullptr : c->cnt2.p + first;
+      K.v = c->opt.ignore_genes ? nullptr : c->v2.p + first;
+      K.j = c->opt.ignore_genes ? nullptr : c->j2.p + first;
+      K.rep = c->rep2.p + first;
+      K.n = n;
+      K.first = first;
+      K.tag = tags.b.p;
+      K.home = buckets.b.p;
+      K.more = more.b.p;
+      K.bmap = bmap2.p;
+      K.packed = A == 4 ? 1u : 0u;
+      K.out = rec2.p;
+      const uint32_t grid = (uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
+      hipLaunchKernelGGL(pack_records_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, K);
+      HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipGetLastError());
-  }
-  if (s->n) {
-    PackParams K{};
-    K.voff = c->voff2.p;
-    K.res = c->res2.p;
-    K.off = c->off2.p;
-    K.cnt = c->opt.ignore_counts ? nullptr : c->cnt2.p;
-    K.v = c->opt.ignore_genes ? nullptr : c->v2.p;
-    K.j = c->opt.ignore_genes ? nullptr : c->j2.p;
-    K.rep = c->rep2.p;
-    K.n = s->n;
-    K.tag = tags.b.p;
-    K.home = buckets.b.p;
-    K.more = more.b.p;
-    K.bmap = c->bmap2.p;
-    K.packed = A == 4 ? 1u : 0u;
-    K.out = c->rec2.p;
-    const uint32_t grid = (uint32_t)((s->n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-    hipLaunchKernelGGL(pack_records_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, K);
-    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CMPR_OK;
+  };
+
+  /* part p: sequences p * q + min(p, r) .., q = n / parts, r = n % parts (the first r parts one more) */
+  const uint64_t q = s->n / nparts, r = s->n % nparts;
+  auto part_first = [&](uint64_t p) { return p * q + std::min(p, r); };
+  c->part0_n = part_first(1);
+  c->slots = table_buckets(c->part0_n, c->table_log2_delta);
+  if ((rc = build_part(0, c->part0_n, c->slots, c->bloom, c->rec2, c->bmap2, c->voff2)))
+    return rc;
+  if (nparts > 1) {
+    c->xparts.resize((size_t)nparts - 1);
+    for (uint64_t p = 1; p < nparts; p++) {
+      RefPart &rp = c->xparts[(size_t)p - 1];
+      rp.first = part_first(p);
+      rp.n = part_first(p + 1) - rp.first;
+      rp.slots = table_buckets(rp.n, c->table_log2_delta);
+      Tmp<uint32_t> voff;
+      if ((rc = build_part(rp.first, rp.n, rp.slots, rp.bloom, rp.rec, rp.bmap, voff.b)))
+        return rc;
+    }
+    if ((rc = dev_alloc(c, c->stats_acc, STAT_COUNT))) return rc;
+    c->nparts = (uint32_t)nparts;
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->have_ref = true;

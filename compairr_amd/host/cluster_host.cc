@@ -104,6 +104,7 @@ int run_cluster(const Options &o, OverlapBackend &backend, FILE *log, FILE *out)
   }
   fprintf(log, "Hashing sequences: 100%% (%.9lfs)\n", rep.seconds_index);
   fprintf(log, "Building network:  100%% (%.9lfs)\n", rep.seconds_queries + rep.seconds_analysis);
+  log_parts(log, rep);
   if (!rep.device_name.empty())
     fprintf(log, "GPU kernel:        %.3f ms, %lu variants, %lu pairs\n", rep.kernel_ms,
             (unsigned long)rep.variants, (unsigned long)rep.matches);

@@ -35,6 +35,7 @@ struct Api {
   int (*overlap_pairs)(cmpr_context *, uint64_t, uint32_t *, uint32_t *, uint64_t *) = nullptr;
   int (*warm_up)(const cmpr_options *) = nullptr;
   int (*warm_up_sized)(const cmpr_options *, uint64_t, uint64_t, uint64_t) = nullptr;
+  int (*get_tunable)(cmpr_context *, const char *, int64_t *) = nullptr;
 };
 
 template <typename F>
@@ -61,6 +62,50 @@ cmpr_set_view view_of(const RepertoireSet &s)
   v.count = s.count.data();
   v.n_repertoires = (uint32_t)s.repertoires.names.size();
   return v;
+}
+
+/* sequences at .. end - 1 of v as a set of their own (offsets rebased into `offs`) */
+cmpr_set_view sub_view(const cmpr_set_view &v, uint64_t at, uint64_t end, std::vector<uint64_t> &offs)
+{
+  offs.resize(end - at + 1);
+  for (uint64_t i = at; i <= end; i++)
+    offs[i - at] = v.offsets[i] - v.offsets[at];
+  cmpr_set_view s = v;
+  s.n = end - at;
+  s.residues = v.residues + v.offsets[at];
+  s.offsets = offs.data();
+  s.v_gene = v.v_gene + at;
+  s.j_gene = v.j_gene + at;
+  s.repertoire = v.repertoire + at;
+  s.count = v.count + at;
+  return s;
+}
+
+/* the matrix of the queries from `first` on into the whole one: -x rows belong to the queries and are
+   placed (R2 cells each), other cells are integer-valued sums (exact in double below 2^53) and added */
+void merge_cells(std::vector<double> &cells, const std::vector<double> &part, bool existence, uint64_t first,
+                 size_t R2)
+{
+  if (existence)
+    std::copy(part.begin(), part.end(), cells.begin() + (size_t)first * R2);
+  else
+    for (size_t k = 0; k < cells.size(); k++)
+      cells[k] += part[k];
+}
+
+/* their pairs, the seeds numbered in the whole query set */
+void append_pairs(PairList &all, const PairList &part, uint64_t first)
+{
+  for (size_t k = 0; k < part.seed.size(); k++) {
+    all.seed.push_back(part.seed[k] + (uint32_t)first);
+    all.hit.push_back(part.hit[k]);
+  }
+}
+
+/* a refusal of cmpr_set_queries that a smaller batch avoids: the layout's 32-bit counts and positions */
+bool size_refusal(const char *msg)
+{
+  return strstr(msg, "too many") || strstr(msg, "32-bit") || strstr(msg, "2^31-1");
 }
 
 double since(std::chrono::steady_clock::time_point t0)
@@ -170,17 +215,7 @@ public:
       }
       Shard &sh = shards[g];
       sh.first = at;
-      shard_offsets[g].resize(end - at + 1);
-      for (uint64_t i = at; i <= end; i++)
-        shard_offsets[g][i - at] = set1.offsets[i] - set1.offsets[at];
-      sh.view = v1;
-      sh.view.n = end - at;
-      sh.view.residues = v1.residues + set1.offsets[at];
-      sh.view.offsets = shard_offsets[g].data();
-      sh.view.v_gene = v1.v_gene + at;
-      sh.view.j_gene = v1.j_gene + at;
-      sh.view.repertoire = v1.repertoire + at;
-      sh.view.count = v1.count + at;
+      sh.view = sub_view(v1, at, end, shard_offsets[g]);
       shard_cells[g].assign(o.existence ? (size_t)(end - at) * R2 : cells.size(), 0.0);
       sh.cells = &shard_cells[g];
       sh.pairs = pairs ? &shard_pairs[g] : nullptr;
@@ -216,13 +251,9 @@ public:
       }
     rep = reports[first_busy];
     for (size_t g = 0; g < G; g++) {
-      if (o.existence)
-        std::copy(shard_cells[g].begin(), shard_cells[g].end(),
-                  cells.begin() + (size_t)shards[g].first * R2);
-      else
-        for (size_t k = 0; k < cells.size(); k++)
-          cells[k] += shard_cells[g][k];
+      merge_cells(cells, shard_cells[g], o.existence, shards[g].first, R2);
       if (g != first_busy) {
+        rep.query_batches += reports[g].query_batches;
         rep.seconds_index = std::max(rep.seconds_index, reports[g].seconds_index);
         rep.seconds_queries = std::max(rep.seconds_queries, reports[g].seconds_queries);
         rep.seconds_analysis = std::max(rep.seconds_analysis, reports[g].seconds_analysis);
@@ -233,12 +264,8 @@ public:
         rep.matches += reports[g].matches;
         rep.algorithmic_bytes += reports[g].algorithmic_bytes;
       }
-      if (pairs) {
-        for (size_t k = 0; k < shard_pairs[g].seed.size(); k++) {
-          pairs->seed.push_back(shard_pairs[g].seed[k] + (uint32_t)shards[g].first);
-          pairs->hit.push_back(shard_pairs[g].hit[k]);
-        }
-      }
+      if (pairs)
+        append_pairs(*pairs, shard_pairs[g], shards[g].first);
     }
     rep.device_name = std::to_string(G) + " HIP devices";
     return true;
@@ -262,14 +289,14 @@ private:
       error = api_.last_error(nullptr);
       return false;
     }
-    const bool ok = run_on(ctx, sh, v1_all, v2, longest_query, same, count_dups, rep, error);
+    const bool ok = run_on(ctx, sh, v1_all, v2, longest_query, same, count_dups, co.existence != 0, rep, error);
     api_.destroy(ctx);
     return ok;
   }
 
   bool run_on(cmpr_context *ctx, const Shard &sh, const cmpr_set_view &v1_all,
               const cmpr_set_view &v2, uint32_t longest_query, bool same, bool count_dups,
-              BackendReport &rep, std::string &error) const
+              bool existence_rows, BackendReport &rep, std::string &error) const
   {
     auto t0 = std::chrono::steady_clock::now();
     if (api_.set_reference(ctx, &v2, longest_query)) {
@@ -294,46 +321,91 @@ private:
       }
     }
     rep.seconds_index = since(t0);
-    t0 = std::chrono::steady_clock::now();
-    if (api_.set_queries(ctx, &sh.view)) {
-      error = api_.last_error(ctx);
-      return false;
-    }
-    rep.seconds_queries = since(t0);
-    t0 = std::chrono::steady_clock::now();
-    if (api_.overlap_matrix_f64(ctx, sh.cells->data())) {
-      error = api_.last_error(ctx);
-      return false;
-    }
-    rep.seconds_analysis = since(t0);
-    /* (the pairs pass below sizes its arrays from these counters, and a failing
-       cmpr_get_stats means the matrix itself is not to be trusted: fatal either way) */
-    cmpr_stats st;
-    if (api_.get_stats(ctx, &st)) {
-      error = api_.last_error(ctx);
-      return false;
-    }
-    rep.kernel_ms = st.kernel_ms;
-    rep.variants = st.variants;
-    rep.bloom_positive = st.bloom_positive;
-    rep.hash_equal = st.hash_equal;
-    rep.matches = st.matches;
-    rep.algorithmic_bytes = st.algorithmic_bytes;
+    int64_t parts = 1;
+    (void)api_.get_tunable(ctx, "reference_parts", &parts);
+    rep.ref_parts = (uint64_t)parts;
     rep.device_name = "HIP device";
-    if (sh.pairs) {
-      /* the matrix pass counted the pairs exactly; list them with a second pass */
-      uint64_t n = rep.matches, got = 0;
-      sh.pairs->seed.resize(n);
-      sh.pairs->hit.resize(n);
-      if (api_.overlap_pairs(ctx, n, sh.pairs->seed.data(), sh.pairs->hit.data(), &got)) {
+    /* Set 1 in contiguous batches when one call cannot lay it out (the layout's 32-bit counts and positions,
+       include/compairr_hip.h) or COMPAIRR_QUERY_BATCH asks for at most that many sequences per call: the
+       arithmetic of --devices -- matrices added, -x rows placed, pair seeds offset. */
+    const uint64_t n = sh.view.n;
+    uint64_t batch = std::max<uint64_t>(n, 1);
+    if (const char *e = getenv("COMPAIRR_QUERY_BATCH")) {
+      const long long b = atoll(e);
+      if (b > 0)
+        batch = std::min<uint64_t>(batch, (uint64_t)b);
+    }
+    const size_t R2 = v2.n_repertoires;
+    const bool existence = existence_rows;
+    std::vector<double> part_cells;
+    std::vector<uint64_t> offs;
+    PairList part_pairs;
+    bool whole = batch >= n;            /* one call into the caller's matrix and pair list, as before */
+    uint64_t at = 0;
+    rep.query_batches = 0;
+    do {
+      const uint64_t end = std::min<uint64_t>(n, at + batch);
+      const cmpr_set_view view = whole ? sh.view : sub_view(sh.view, at, end, offs);
+      t0 = std::chrono::steady_clock::now();
+      if (api_.set_queries(ctx, &view)) {
+        const char *msg = api_.last_error(ctx);
+        if (end - at > 1 && size_refusal(msg)) {
+          batch = (end - at + 1) / 2;
+          if (whole) {
+            whole = false;
+            std::fill(sh.cells->begin(), sh.cells->end(), 0.0);
+          }
+          continue;
+        }
+        error = msg;
+        return false;
+      }
+      rep.seconds_queries += since(t0);
+      std::vector<double> &cells = whole ? *sh.cells : part_cells;
+      if (!whole)
+        part_cells.assign(existence ? (size_t)(end - at) * R2 : sh.cells->size(), 0.0);
+      t0 = std::chrono::steady_clock::now();
+      if (api_.overlap_matrix_f64(ctx, cells.data())) {
         error = api_.last_error(ctx);
         return false;
       }
-      if (got != n) {
-        error = "pair count changed between passes";
+      rep.seconds_analysis += since(t0);
+      /* (the pairs pass below sizes its arrays from these counters, and a failing
+         cmpr_get_stats means the matrix itself is not to be trusted: fatal either way) */
+      cmpr_stats st;
+      if (api_.get_stats(ctx, &st)) {
+        error = api_.last_error(ctx);
         return false;
       }
-    }
+      rep.kernel_ms += st.kernel_ms;
+      rep.variants += st.variants;
+      rep.bloom_positive += st.bloom_positive;
+      rep.hash_equal += st.hash_equal;
+      rep.matches += st.matches;
+      rep.algorithmic_bytes += st.algorithmic_bytes;
+      if (sh.pairs) {
+        /* the matrix pass counted the pairs exactly; list them with a second pass */
+        PairList &pl = whole ? *sh.pairs : part_pairs;
+        const uint64_t np = st.matches;
+        uint64_t got = 0;
+        pl.seed.resize(np);
+        pl.hit.resize(np);
+        if (api_.overlap_pairs(ctx, np, pl.seed.data(), pl.hit.data(), &got)) {
+          error = api_.last_error(ctx);
+          return false;
+        }
+        if (got != np) {
+          error = "pair count changed between passes";
+          return false;
+        }
+        if (!whole)
+          append_pairs(*sh.pairs, part_pairs, at);
+      }
+      if (!whole)
+        merge_cells(*sh.cells, part_cells, existence, at, R2);
+      rep.query_batches++;
+      at = end;
+    } while (at < n);
     return true;
   }
 
@@ -383,7 +455,8 @@ OverlapBackend *make_hip_backend(const char *argv0, std::string &error)
       !bind(api.handle, "cmpr_count_duplicates", api.count_duplicates, error) ||
       !bind(api.handle, "cmpr_overlap_pairs", api.overlap_pairs, error) ||
       !bind(api.handle, "cmpr_warm_up", api.warm_up, error) ||
-      !bind(api.handle, "cmpr_warm_up_sized", api.warm_up_sized, error)) {
+      !bind(api.handle, "cmpr_warm_up_sized", api.warm_up_sized, error) ||
+      !bind(api.handle, "cmpr_get_tunable", api.get_tunable, error)) {
     dlclose(api.handle);
     return nullptr;
   }

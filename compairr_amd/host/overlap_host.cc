@@ -17,6 +17,13 @@
 
 namespace cmprhost {
 
+void log_parts(FILE *log, const BackendReport &rep)
+{
+  if (rep.ref_parts > 1 || rep.query_batches > 1)
+    fprintf(log, "Index parts:       set 2 in %lu parts, set 1 in %lu batches\n", (unsigned long)rep.ref_parts,
+            (unsigned long)rep.query_batches);
+}
+
 namespace {
 
 FILE *open_output(const char *name)
@@ -303,6 +310,7 @@ int compairr_main(int argc, char **argv, OverlapBackend &backend)
     fprintf(log, "Warning: %lu duplicates detected in repertoire set 2\n",
             (unsigned long)rep.dup_set2);
   fprintf(log, "Query layout:      100%% (%.9lfs)\n", rep.seconds_queries);
+  log_parts(log, rep);
   fprintf(log, "Analysing:         100%% (%.9lfs)\n", rep.seconds_analysis);
   if (!rep.device_name.empty()) {
     const double s = rep.kernel_ms * 1e-3;

@@ -21,8 +21,13 @@ struct BackendReport {
   uint64_t variants = 0, bloom_positive = 0, hash_equal = 0, matches = 0;
   uint64_t dup_set1 = 0, dup_set2 = 0;   /* exact duplicates (overlap.cc:850,872) */
   uint64_t algorithmic_bytes = 0;
+  uint64_t ref_parts = 0;         /* parts of the set-2 index (0: not reported) */
+  uint64_t query_batches = 0;     /* calls set 1 was laid out and launched in */
   std::string device_name;
 };
+
+/* "Index parts:" line of the log -- only where set 2 is in parts or set 1 in batches */
+void log_parts(FILE *log, const BackendReport &rep);
 
 /* (seed, hit) pairs for -p/--pairs: indices into set 1 / set 2 */
 struct PairList {

@@ -140,15 +140,31 @@ const char *cmpr_last_error(const cmpr_context *ctx);
  * Footprint: the record table holds one 64-byte slot per BUCKET, buckets = 2^table_log2_delta x the
  * smallest power of two >= n / 0.7 (hashtable.cc:24, 36-38) -- 183 to 366 bytes per reference sequence at
  * the default delta of 1 (10M: 2 GiB; 100M: 32 GiB) --, the row filter 2 bytes per residue position + 2 per
- * sequence (twice that with -i), the set itself ~45 bytes per sequence.  At most 2^30 buckets: sets beyond
- * ~375M sequences (187M at delta 1 ... 750M at delta 0) return CMPR_EUNSUPPORTED; "table_log2_delta" = 0
- * halves the table.
+ * sequence (twice that with -i), the set itself ~45 bytes per sequence.  "table_log2_delta" = 0 halves the table.
+ *
+ * Size: at most 2^32-64 sequences (pair lists hold uint32 sequence numbers) and device memory.  A set whose
+ * record table would exceed 2^"part_buckets_log2" buckets (default 2^30: ~375M sequences at delta 1) is
+ * indexed in PARTS -- contiguous sequence ranges, as few as the cap allows or the count with the fewest
+ * table bytes in all -- that share everything the query layout reads (Zobrist keys, class geometry, slice
+ * count, pages) and differ in their filter words, record table and bucket bitmap; each part's filter is as
+ * large as the whole set's.  Every cmpr_overlap_* call then makes one pass of its kernels per part, in
+ * stream order, into the same matrix; cmpr_stats counts summed over the passes (`variants` and
+ * `filter_reads` once per part).  "reference_parts" says how many are in effect.  Work shards compose
+ * with parts: each context does its share of the slices for every part.  Beyond memory, CMPR_ENOMEM.
  */
 int cmpr_set_reference(cmpr_context *ctx, const cmpr_set_view *set2,
                        uint32_t longest_query);
 
 /*
- * Upload set 1 (the queries) and lay it out for the kernel.  After this call
+ * Upload set 1 (the queries) and lay it out for the kernel.  Per call: at most 2^31-1 sequences, and the
+ * layout's 32-bit counts and positions must hold -- fewer than 2^32 query slots (64 per tile; tiles are
+ * padded per (slice, length) group, read-only tunable "query_slots"), 2^32 four-byte words of laid-out
+ * residues, 2^32 class-item slots, 2^31 chunks and 2^31 (slice, length) groups --, else CMPR_EUNSUPPORTED
+ * ("too many ..." / "... 32-bit ...").  Slots, residue words and chunks grow with the set plus a padding of
+ * up to one tile per (slice, length) group, and the slice count comes from the reference: no set size is
+ * accepted against every reference, so the bound is these checks, not a number.  Calls are independent: a larger set is handed over in contiguous batches whose matrices add up (-x rows and pair
+ * lists number the sequences of the batch) -- bin/compairr halves a batch the layout refuses for its size.
+ * After this call
  * the queries are resident in HBM; cmpr_overlap_* may be called repeatedly.
  * Passing the same view as set 2 gives the reference's one-file mode
  * (overlap.cc:799-825).  The context keeps its device allocations from call to
@@ -359,6 +375,10 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
      "chunk_deal"            variant 2: 1 (default): beyond a workgroup's first four, chunks are handed out
                              by counters in list order (heaviest first) -- on skewed data (the cdr3 law,
                              d = 1 -i) the probe kernel takes 1.5 ms where a static deal takes 2.5; 0: static
+     "part_buckets_log2"     the most buckets one part's record table may have (2..30, default 30),
+                             counted after table_log2_delta: a larger set 2 is indexed in parts (see
+                             cmpr_set_reference; environment COMPAIRR_HIP_PART_BUCKETS_LOG2 at cmpr_create).
+                             Read-only "reference_parts": the parts in effect (0 before cmpr_set_reference)
      "table_log2_delta"      buckets of the record table = 2^delta x the 70 % rule of hashtable.cc:24 (default 1:
                              at most 0.35 full -- one memory line per looked-up sequence); 0..3
      "bucket_bitmap"         resolve_kernel asks a bitmap (one bit per bucket: it holds a record) before it
@@ -384,7 +404,7 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
      "assume_never_overflows" TEST ONLY: the next launch runs without redo pass as if
                              the margin had been shown
    "variant", "bloom_bits_log2_delta", "class_residues", "slice_words_log2", "d2_pairs", "d2_buffers",
-   "table_log2_delta", "slice_pages", "page_budget", "fill_slices" and "row_filter_x16" must be set before
+   "table_log2_delta", "part_buckets_log2", "slice_pages", "page_budget", "fill_slices" and "row_filter_x16" must be set before
    cmpr_set_reference(); "chunk_tiles", "waves_per_block",
    "small_slice_tiles", "direct_slices_log2" and the work shard before cmpr_set_queries().  ("debug" exists
    only in a -DCMPR_ABLATION build of the library.) */

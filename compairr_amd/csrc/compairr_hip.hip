@@ -258,6 +258,12 @@ extern "C" void cmpr_destroy(cmpr_context *c)
   cmpr_release_reservations();              /* (what cmpr_warm_up_sized reserved and nobody took) */
   if (c->stream)
     (void)hipStreamSynchronize(c->stream);
+  /* launches that still read these buffers on a caller's stream: the last one of the set in place, or one
+     of a set that a failed cmpr_set_queries* retired without getting to its wait */
+  if (c->events_valid && c->ev_k1)
+    (void)hipEventSynchronize(c->ev_k1);
+  if (c->pending_launch)
+    (void)hipEventSynchronize(c->pending_launch);
   invalidate_plan(c);
   c->zob.release();
   c->res2.release(); c->off2.release(); c->cnt2.release();
@@ -804,14 +810,37 @@ static int cmpr_count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, u
 /* ------------------------------------------------------------------ */
 
 /* what every way of handing over queries does first (cmpr_set_queries, _device, _routed,
-   cmpr_route_queries): the old set, and what was left unasked about it, goes */
+   cmpr_route_queries): the old set is no longer launchable -- a call that fails from here on
+   leaves "no queries set".
+
+   It does NOT wait for the launches on the old set that may still be running on a caller's
+   stream.  They read the resident layout and the per-launch scratch, which only the second
+   half of the layout writes; the first half (upload or device view, keys_kernel, the sizes)
+   reads the caller's arrays and the reference's tables and writes arena A alone, and runs
+   beside them.  The wait, and the question about what was left unasked about the old set,
+   is cmpr_settle_previous_launch, called by the layout where it first needs it.  The end
+   event of the last launch is kept in pending_launch (ev_k1 itself is a ring entry that the
+   reset of `calls` hands to the next launch), also across a call that fails before the wait:
+   the next cmpr_set_queries*, cmpr_set_reference* or cmpr_destroy waits for it. */
 static int retire_queries(cmpr_context *c)
 {
   HIP_TRY(c, hipSetDevice(c->device));
-  /* launches on the old set that may still be running on a caller's stream read what the
-     layout is about to overwrite */
   if (c->events_valid)
-    HIP_TRY(c, hipEventSynchronize(c->ev_k1));
+    c->pending_launch = c->ev_k1;
+  c->have_q = false;
+  c->usage_pending = c->never_overflows = false;
+  c->last_without_redo = false;
+  c->events_valid = false;
+  c->calls = 0;
+  invalidate_plan(c);
+  return CMPR_OK;
+}
+
+int cmpr_settle_previous_launch(cmpr_context *c)
+{
+  int rc;
+  if ((rc = cmpr_wait_previous_launch(c)))
+    return rc;
   /* asynchronous launches on the OLD set that nobody has asked about (cmpr_get_stats): the
      question is answered here, loudly, rather than carried over to the new set -- a sticky
      overflow word must not fail the first cmpr_get_stats on the new one, nor be lost */
@@ -827,12 +856,6 @@ static int retire_queries(cmpr_context *c)
                                   "query set: its result was invalid (cmpr_get_stats was not asked); repeat "
                                   "the call to set the new queries");
   }
-  c->have_q = false;
-  c->usage_pending = c->never_overflows = false;
-  c->last_without_redo = false;
-  c->events_valid = false;
-  c->calls = 0;
-  invalidate_plan(c);
   return CMPR_OK;
 }
 
@@ -1878,6 +1901,10 @@ extern "C" int cmpr_route_queries(cmpr_context *c, const cmpr_set_view *share, u
     if (first_index + share->n > 0xffffffffull)
       return fail(c, CMPR_EUNSUPPORTED, "more than 2^32 sequences in the whole query set");
     if ((rc = retire_queries(c)))
+      return rc;
+    /* (the keyed share stays in arena A for cmpr_route_pack and the routed call that follows; nothing of
+       this call runs beside a launch on the old set) */
+    if ((rc = cmpr_settle_previous_launch(c)))
       return rc;
     LayoutSource src;
     src.kind = LayoutSource::HOST;

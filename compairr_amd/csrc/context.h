@@ -145,6 +145,11 @@ struct cmpr_context {
   hipEvent_t   ev_k0 = nullptr, ev_km = nullptr, ev_k1 = nullptr;   /* = the ring entry of the last call */
   bool         events_valid = false;
   bool         stop_is_k1 = false;   /* the last call ended with the kernels (ev_k1), no copy behind them */
+  /* the end event of a launch on a RETIRED query set that nobody has waited for yet (retire_queries): the
+     layout of the next set waits for it where it first needs to (cmpr_settle_previous_launch), and it
+     outlives a call that fails before that point.  Nothing records on a ring event while it is pending:
+     launches need a query set, and no set is accepted without this wait */
+  hipEvent_t   pending_launch = nullptr;
   std::string  err;
 
   /* tunables */
@@ -378,6 +383,22 @@ int dev_alloc(cmpr_context *c, DevBuf<T> &b, size_t n)
   b.cap = n;
   return CMPR_OK;
 }
+
+/* The host waits for a launch on a retired query set that may still run on a caller's stream
+   (cmpr_context::pending_launch): called before anything such a launch reads or writes is overwritten,
+   freed or reallocated. */
+inline int cmpr_wait_previous_launch(cmpr_context *c)
+{
+  if (c->pending_launch) {
+    HIP_TRY(c, hipEventSynchronize(c->pending_launch));
+    c->pending_launch = nullptr;
+  }
+  return CMPR_OK;
+}
+
+/* compairr_hip.hip: cmpr_wait_previous_launch, then the question about the sticky overflow word of the
+   retired set's unasked launches (CMPR_ESTATE when one overflowed) */
+int cmpr_settle_previous_launch(cmpr_context *c);
 
 /* like dev_alloc, but an allocation that is large enough is kept (contents undefined) */
 template <typename T>

@@ -2532,6 +2532,9 @@ int cmpr_layout_queries(cmpr_context *c, const LayoutSource &src)
     }
   }
   const size_t o_cub = cut.take(cub_bytes + 256);
+  /* (an arena that has to grow is freed and allocated again: not beside a launch on the retired set) */
+  if (!(c->arena_a.base && c->arena_a.cap >= cut.used) && (rc = cmpr_wait_previous_launch(c)))
+    return rc;
   if ((rc = arena_fit(c, c->arena_a, cut.used))) return rc;
   const auto t_arena_a = std::chrono::steady_clock::now();
   char *const base = c->arena_a.base;
@@ -3040,6 +3043,26 @@ int cmpr_layout_queries(cmpr_context *c, const LayoutSource &src)
   if (nchunks >= 0x7fffffffull || nlist >= 0xffffffffull)
     return fail(c, CMPR_EUNSUPPORTED, "too many chunks");
 
+  /* ---- here, not at the start of the call, the previous set's launches have to be through ----
+     A launch of the set that this call retired may still run on a caller's stream.  Up to this point it ran
+     beside the layout: everything above reads the caller's arrays and the reference's tables (zob, ctab,
+     page_tab: written by cmpr_set_reference alone) and writes arena A and the pinned SizesBlock, which no
+     launch reads.  Audit of what make_plan / issue_step hand to the probe, resolve, redo and reduce kernels
+     (ProbeParams, the same struct for matrix, pair-list and -x output): the reference's buffers (zob, bloom,
+     bmap2, res2 .. rec2, the parts' tables, geom's ctab / page_tab); the resident layout (tiles, chunks,
+     tile_refs, small_tiles, qres, qv, qj, qgh, qlen, qck, qrec, qhins, qhdel, qpk, items, cpk, slice_items:
+     DevBufs of the context, reserved or released below); the per-launch scratch (pos_buf, pos_ctr, part,
+     matrix, matrix_f64, stats_acc, d_usage: reserved by LayoutSource::finish or owned by the context); the
+     caller's output matrix; and the pair buffers, local to a synchronous cmpr_overlap_pairs.  The two arenas
+     are named in this file alone, QAux (arena B) lives from here to the end of this call, and the routed
+     records are unpacked into arena A before anything reads them: no configuration reads an arena or the
+     caller's query arrays in a launch.  From here on the call writes, frees and reallocates what a launch
+     reads, so the HOST waits (the launch is normally long through: it had keys_kernel and the round trip
+     to finish in), and the question about the retired set's unasked launches is answered.  A return above
+     this line leaves the event pending for the next call (cmpr_context::pending_launch). */
+  if ((rc = cmpr_settle_previous_launch(c)))
+    return rc;
+
   /* ---- arena B: the temporaries sized by the device ---- */
   const size_t slots = (size_t)ntiles * WAVE;
   size_t sort_bytes = 0, small_sort_bytes = 0;
@@ -3270,6 +3293,9 @@ int cmpr_layout_queries(cmpr_context *c, const LayoutSource &src)
     x = 0.0f;
   if (c->layout_marks == 0x3fu) {
     /* keys | sizes (per-slice needs, scans, the host's round trip) | slices + scatter | tiles | chunk order */
+    /* (the first two are wall intervals on this stream: behind a launch on the previous set that is still
+       running on a caller's stream, "keys" includes the time keys_kernel's workgroups waited for compute units
+       that launch held, and "sizes" the host's wait for it where there was one) */
     for (int k = 0; k < 5; k++)
       (void)hipEventElapsedTime(&c->layout_kernel_ms[k], c->ev_layout[k], c->ev_layout[k + 1]);
   }

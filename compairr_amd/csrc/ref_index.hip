@@ -247,6 +247,9 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
   /* launches that still read the old index on a caller's stream */
   if (c->events_valid)
     HIP_TRY(c, hipEventSynchronize(c->ev_k1));
+  /* (and one on a query set that a failed cmpr_set_queries* retired without getting to its wait) */
+  if ((rc = cmpr_wait_previous_launch(c)))
+    return rc;
   c->have_ref = false;
   c->have_q = false;
   for (RefPart &p : c->xparts)

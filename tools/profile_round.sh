@@ -4,19 +4,29 @@
 # 2. one rocprofv3 --pmc pass per counter group (FETCH_SIZE and WRITE_SIZE each alone,
 #    as MI355X_MICROARCH.md prescribes; PMC passes are never mixed with traces).
 # Everything lands in gpurun_out/<tag>/; tools/pmc_summary.py turns it into profiles/.
+# Every GPU step runs under a time limit of its own, and the first one that fails (a fault, an abort, a time
+# limit) ends the script with its exit status: nothing more is started on a card that may be in trouble.
 tag=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/$tag
 mkdir -p $O
 python3 $R/tools/csrc_hash.py > $O/csrc_sha256.txt
 cd /tmp && export TMPDIR=/tmp
-if [ "$STATS_ONLY" != 1 ]; then timeout ${BENCH_TIMEOUT:-900} python3 $R/bench.py --full "$@" > $O/bench.json 2> $O/bench.err; fi
+step() {   # <seconds> <command...>: run it under its limit; a failure ends the script
+  local limit=$1; shift
+  timeout -k 10 $limit "$@"
+  local rc=$?
+  if [ $rc != 0 ]; then echo "profile_round.sh: exit status $rc from: $*" >&2; exit $rc; fi
+}
+if [ "$STATS_ONLY" != 1 ]; then
+  step ${BENCH_TIMEOUT:-900} python3 $R/bench.py --full "$@" > $O/bench.json 2> $O/bench.err
+fi
 # (BENCH_ONLY=1: the bench line alone -- tools/reprofile.sh, once the counters are summarised)
 if [ "$BENCH_ONLY" = 1 ]; then exit 0; fi
 if [ "$STATS_ONLY" = 1 ]; then rm -rf $O/prof_stats; fi
 # (--skip-host-layout: every launch of the layout's kernels in the trace is a full-size one of a step -- the trace's
 #  averages are then the bench line's per-kernel times)
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/prof_stats -o p --output-format csv -- \
+step 600 rocprofv3 --kernel-trace --stats -d $O/prof_stats -o p --output-format csv -- \
     python3 $R/bench.py --full --cpu-sample -1 --skip-host-layout "$@" > $O/stats_bench.json 2> $O/stats.err
 if [ "$STATS_ONLY" = 1 ]; then find $O -name '*agent_info*' -delete; find $O -name '*.csv' -size +8M -delete; exit 0; fi
 i=0
@@ -32,7 +42,7 @@ if [ "$PMC_GROUPS" != "essential" ]; then
 fi
 for ctrs in "${CTR_GROUPS[@]}"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $ctrs -d $O/pmc_$i -o p --output-format csv -- \
+  step 600 rocprofv3 --pmc $ctrs -d $O/pmc_$i -o p --output-format csv -- \
       python3 $R/bench.py --full --cpu-sample -1 --steps 3 --warmup 1 "$@" > $O/pmc_$i.log 2>&1
 done
 find $O -name '*agent_info*' -delete; find $O -name '*.csv' -size +8M -delete

@@ -42,6 +42,7 @@ namespace {
 void use_counter_block(cmpr_context *c, int which);
 void invalidate_plan(cmpr_context *c);
 int make_plan(cmpr_context *c);
+void tunable_from_environment(cmpr_context *c, const char *variable, const char *name);
 }
 
 int validate_view(const cmpr_options &o, const cmpr_set_view *s, std::string &why, bool on_device)
@@ -225,27 +226,10 @@ extern "C" int cmpr_create(const cmpr_options *options, cmpr_context **out)
     CREATE_TRY(hipEventCreateWithFlags(&e, tflags));
 
 #undef CREATE_TRY
-  /* environment overrides of the tunables (for the CLI, which has no flag) */
-  if (const char *e = getenv("COMPAIRR_HIP_VARIANT")) {
-    int v = atoi(e);
-    if (v >= 0 && v <= 2)
-      c->variant = v;
-  }
-  if (const char *e = getenv("COMPAIRR_HIP_SLICE_WORDS_LOG2")) {
-    int v = atoi(e);
-    if (v >= 1 && v <= 13)
-      c->slice_words_log2 = v;
-  }
-  if (const char *e = getenv("COMPAIRR_HIP_PART_BUCKETS_LOG2")) {
-    int v = atoi(e);
-    if (v >= 2 && v <= 30)
-      c->part_buckets_log2 = v;
-  }
-  if (const char *e = getenv("COMPAIRR_HIP_CLASS_RESIDUES")) {
-    int v = atoi(e);
-    if (v >= -1 && v <= (int)max_class_res((uint32_t)c->opt.alphabet_size))
-      c->class_residues = v;
-  }
+  tunable_from_environment(c, "COMPAIRR_HIP_VARIANT", "variant");
+  tunable_from_environment(c, "COMPAIRR_HIP_SLICE_WORDS_LOG2", "slice_words_log2");
+  tunable_from_environment(c, "COMPAIRR_HIP_PART_BUCKETS_LOG2", "part_buckets_log2");
+  tunable_from_environment(c, "COMPAIRR_HIP_CLASS_RESIDUES", "class_residues");
   *out = c;
   return CMPR_OK;
 }
@@ -309,222 +293,143 @@ extern "C" const char *cmpr_last_error(const cmpr_context *c)
 extern "C" uint32_t cmpr_rows(const cmpr_context *c) { return c ? c->R1 : 0; }
 extern "C" uint32_t cmpr_cols(const cmpr_context *c) { return c ? c->R2 : 0; }
 
-static int set_tunable_value(cmpr_context *c, const std::string &n, int64_t value, bool &affects_plan);
+/* ---- the tunables ----
+   One row per name cmpr_set_tunable() accepts.  A set is checked in this order: the name, the range (lo..hi
+   and the row's predicate: CMPR_EINVAL), the lock (CMPR_ESTATE); only then is anything stored, so a refused
+   set leaves the context as it was.  Behind a successful set the cached step (kernels, grid) is worked out
+   again and the no-redo shortcut of variant 2 has to be earned again, except for the T_NO_PLAN names no launch
+   depends on.  cmpr_get_tunable() reads the row's field unless it has an arm of its own (the names whose value
+   in effect is decided with the data) or the row is T_WRITE_ONLY. */
+namespace {
+enum TunLock { LOCK_NEVER, LOCK_REF, LOCK_QUERIES };   /* settable: always / before cmpr_set_reference / before cmpr_set_queries */
+enum : unsigned { T_NO_PLAN = 1, T_WRITE_ONLY = 2 };
+
+struct Tunable {
+  const char *name;
+  int64_t cmpr_context::*field;                    /* nullptr: `after` does the store */
+  int64_t lo, hi;
+  TunLock lock;
+  unsigned flags;
+  const char *range_msg;                           /* CMPR_EINVAL text; one that starts with a blank follows the name */
+  bool (*also)(const cmpr_context *, int64_t);     /* what lo..hi cannot say, or nullptr */
+  void (*after)(cmpr_context *, int64_t);          /* side effect of a successful set, or nullptr */
+  const char *lock_msg;                            /* CMPR_ESTATE text; nullptr: "set <name> before <call>" */
+};
+
+bool power_of_two(const cmpr_context *, int64_t v) { return (v & (v - 1)) == 0; }
+bool not_zero(const cmpr_context *, int64_t v) { return v != 0; }
+bool class_res_fits(const cmpr_context *c, int64_t v) { return v <= (int64_t)max_class_res((uint32_t)c->opt.alphabet_size); }
+void force_waves(cmpr_context *c, int64_t) { c->waves_per_block_forced = true; }
+/* TEST ONLY: the next launch runs without redo pass as if the margin had been shown (tests/test_gpu_parity.py) */
+void pretend_never_overflows(cmpr_context *c, int64_t v)
+{
+  c->force_no_redo = v != 0;
+  c->usage_pending = false;                 /* (a measurement in flight would overrule the pretence) */
+}
+const char SHARD_RANGE[] = "work_shard_count must be 1..65535, work_shard_index 0..count-1",
+           SHARD_LOCK[] = "set the work shard before cmpr_set_queries";
+const char BOOL_RANGE[] = " must be 0 or 1", AUTO_RANGE[] = " must be -1 (auto), 0 or 1";
+
+#define F(field) &cmpr_context::field
+const Tunable TUNABLES[] = {
+  {"blocks_per_cu", F(blocks_per_cu), 1, 16, LOCK_NEVER, 0, " must be 1..16"},
+  {"variant", F(variant), -1, 2, LOCK_REF, 0, " must be -1 (default), 0, 1 or 2"},
+  /* (one text whatever the alphabet; the bound is the alphabet's) */
+  {"class_residues", F(class_residues), -1, 8, LOCK_REF, 0,
+   " must be -1..4 (amino acids; four: variant 2, d = 1, else three) / -1..8 (nucleotides)", class_res_fits},
+  {"class_anchor", F(class_anchor), -1, 65535, LOCK_REF, 0, " must be -1..65535"},
+  {"heavy_threshold", F(heavy_threshold), -1, INT64_MAX, LOCK_REF, 0, " must be >= -1"},
+  {"slice_words_log2", F(slice_words_log2), -1, 13, LOCK_REF, 0, " must be -1 (default) or 1..13", not_zero},
+  {"chunk_tiles", F(chunk_tiles), 0, 512, LOCK_QUERIES, 0, " must be 0..512"},
+#ifdef CMPR_ABLATION
+  {"debug", F(debug), INT64_MIN, INT64_MAX, LOCK_NEVER, 0, ""},
+#else
+  {"debug", F(debug), 1, 0, LOCK_NEVER, 0, "the debug switches exist only in a -DCMPR_ABLATION build"},   /* (no value is in 1..0) */
+#endif
+  {"host_threads", F(host_threads), 1, 256, LOCK_NEVER, T_NO_PLAN, " must be 1..256"},
+  {"table_log2_delta", F(table_log2_delta), 0, 3, LOCK_REF, 0, " must be 0..3"},
+  {"part_buckets_log2", F(part_buckets_log2), 2, 30, LOCK_REF, 0, " must be 2..30"},
+  {"deferred_resolve", F(deferred_resolve), 0, 1, LOCK_NEVER, 0, BOOL_RANGE},
+  {"d2_pairs", F(d2_pairs), -1, 1, LOCK_REF, 0, AUTO_RANGE},
+  {"d2_buffers", F(d2_buffers), 1, 2, LOCK_REF, 0, " must be 1 or 2"},
+  {"chunk_deal", F(chunk_deal), 0, 1, LOCK_NEVER, 0, " must be 0 (static) or 1 (by a counter)"},
+  {"narrow_upload", F(narrow_upload), -1, 1, LOCK_NEVER, T_NO_PLAN, AUTO_RANGE},
+  {"item_wg", F(item_wg), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  {"layout_recompute", F(layout_recompute), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  {"layout_timing", F(layout_timing), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  {"layout_zob_lds", F(layout_zob_lds), 0, 1, LOCK_NEVER, T_NO_PLAN | T_WRITE_ONLY, BOOL_RANGE},
+  {"record_tiles", F(record_tiles), 0, 2, LOCK_QUERIES, T_NO_PLAN, " must be 0, 1 or 2"},
+  {"assume_never_overflows", nullptr, INT64_MIN, INT64_MAX, LOCK_NEVER, T_NO_PLAN | T_WRITE_ONLY, "", nullptr, pretend_never_overflows},
+  {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
+  {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
+  {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},
+  {"pos_capacity", F(pos_capacity), 0, INT64_MAX, LOCK_QUERIES, 0, " must be >= 0"},
+  {"work_shard_count", F(work_shard_count), 1, 65535, LOCK_QUERIES, 0, SHARD_RANGE, nullptr, nullptr, SHARD_LOCK},
+  {"work_shard_index", F(work_shard_index), 0, 65535, LOCK_QUERIES, 0, SHARD_RANGE, nullptr, nullptr, SHARD_LOCK},
+  {"small_slice_tiles", F(small_slice_tiles), 0, 64, LOCK_QUERIES, 0, " must be 0..64"},
+  {"sub2_items", F(sub2_items), -1, 1, LOCK_QUERIES, 0, " must be -1 (default), 0 or 1"},
+  {"class_rows_unstaged", F(class_rows_unstaged), 0, 1, LOCK_QUERIES, 0, BOOL_RANGE},
+  {"waves_per_block", F(waves_per_block), 4, 16, LOCK_QUERIES, 0, " must be 4, 8 or 16", power_of_two, force_waves},
+  {"bloom_bits_log2_delta", F(bloom_log2_delta), -4, 4, LOCK_REF, 0, " must be -4..4"},
+  {"slice_pages", F(slice_pages), -1, (int64_t)PAGE_E_MAX, LOCK_REF, 0, " must be -1..3"},
+  {"page_budget", F(page_budget), 0, 1 << 24, LOCK_REF, 0, " must be 0..2^24"},
+  {"bucket_bitmap", F(bucket_bitmap), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},
+  {"fill_slices", F(fill_slices), 0, 1, LOCK_REF, 0, BOOL_RANGE},
+  {"direct_slices_log2", F(direct_slices_log2), -1, 12, LOCK_NEVER, 0, " must be -1 (auto) or 0..12"},
+  {"row_filter_x16", F(row_filter_x16), 8, 128, LOCK_REF, 0, " must be 8..128 (sixteenths of a byte per entry)"},
+};
+#undef F
+
+const Tunable *find_tunable(const char *name)
+{
+  for (const Tunable &t : TUNABLES)
+    if (!strcmp(t.name, name))
+      return &t;
+  return nullptr;
+}
+
+bool in_range(const cmpr_context *c, const Tunable &t, int64_t value)
+{
+  return value >= t.lo && value <= t.hi && (!t.also || t.also(c, value));
+}
+
+void store_tunable(cmpr_context *c, const Tunable &t, int64_t value)
+{
+  if (t.field)
+    c->*t.field = value;
+  if (t.after)
+    t.after(c, value);
+}
+
+/* cmpr_create: the value of an environment variable, for the CLI, which has no flag.  Read with atoi as ever
+   (junk is 0); what the row's range refuses is ignored without a word.  (The rows also take the -1 the
+   variables never did: it is the default a new context has anyway.) */
+void tunable_from_environment(cmpr_context *c, const char *variable, const char *name)
+{
+  const char *e = getenv(variable);
+  const Tunable *t = find_tunable(name);
+  if (e && t && in_range(c, *t, atoi(e)))
+    store_tunable(c, *t, atoi(e));
+}
+
+}  // namespace
 
 extern "C" int cmpr_set_tunable(cmpr_context *c, const char *name, int64_t value)
 {
   if (!c || !name)
     return CMPR_EINVAL;
-  std::string n(name);
-  /* A tunable that was set: the cached step (kernels, grid) is worked out again and the
-     no-redo shortcut of variant 2 has to be earned again -- only behind a successful change
-     (a refused name or value leaves the context as it was), and not for the knobs no
-     launch depends on. */
-  bool plan = true;
-  const int rc = set_tunable_value(c, n, value, plan);
-  if (rc == CMPR_OK && plan) {
+  const Tunable *t = find_tunable(name);
+  if (!t)
+    return fail(c, CMPR_EINVAL, std::string("unknown tunable: ") + name);
+  if (!in_range(c, *t, value))
+    return fail(c, CMPR_EINVAL, t->range_msg[0] == ' ' ? t->name + std::string(t->range_msg) : t->range_msg);
+  if (t->lock == LOCK_REF ? c->have_ref : t->lock == LOCK_QUERIES && c->have_q)
+    return fail(c, CMPR_ESTATE, t->lock_msg ? t->lock_msg : std::string("set ") + t->name + " before " +
+                                (t->lock == LOCK_REF ? "cmpr_set_reference" : "cmpr_set_queries"));
+  store_tunable(c, *t, value);
+  if (!(t->flags & T_NO_PLAN)) {
     invalidate_plan(c);
     c->usage_pending = c->never_overflows = false;
-  }
-  return rc;
-}
-
-static int set_tunable_value(cmpr_context *c, const std::string &n, int64_t value, bool &affects_plan)
-{
-  if (n == "blocks_per_cu") {
-    if (value < 1 || value > 16)
-      return fail(c, CMPR_EINVAL, "blocks_per_cu must be 1..16");
-    c->blocks_per_cu = value;
-  } else if (n == "variant") {
-    if (value < -1 || value > 2)
-      return fail(c, CMPR_EINVAL, "variant must be -1 (default), 0, 1 or 2");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set variant before cmpr_set_reference");
-    c->variant = value;
-  } else if (n == "class_residues") {
-    if (value < -1 || value > (int64_t)max_class_res((uint32_t)c->opt.alphabet_size))
-      return fail(c, CMPR_EINVAL, "class_residues must be -1..4 (amino acids; four: variant 2, d = 1, else three) / -1..8 (nucleotides)");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set class_residues before cmpr_set_reference");
-    c->class_residues = value;
-  } else if (n == "class_anchor") {
-    if (value < -1 || value > 65535)
-      return fail(c, CMPR_EINVAL, "class_anchor must be -1..65535");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set class_anchor before cmpr_set_reference");
-    c->class_anchor = value;
-  } else if (n == "heavy_threshold") {
-    if (value < -1)
-      return fail(c, CMPR_EINVAL, "heavy_threshold must be >= -1");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set heavy_threshold before cmpr_set_reference");
-    c->heavy_threshold = value;
-  } else if (n == "slice_words_log2") {
-    if (value < -1 || value == 0 || value > 13)
-      return fail(c, CMPR_EINVAL, "slice_words_log2 must be -1 (default) or 1..13");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set slice_words_log2 before cmpr_set_reference");
-    c->slice_words_log2 = value;
-  } else if (n == "chunk_tiles") {
-    if (value < 0 || value > 512)
-      return fail(c, CMPR_EINVAL, "chunk_tiles must be 0..512");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set chunk_tiles before cmpr_set_queries");
-    c->chunk_tiles = value;
-  } else if (n == "debug") {
-#ifdef CMPR_ABLATION
-    c->debug = value;
-#else
-    return fail(c, CMPR_EINVAL, "the debug switches exist only in a -DCMPR_ABLATION build");
-#endif
-  } else if (n == "host_threads") {
-    if (value < 1 || value > 256)
-      return fail(c, CMPR_EINVAL, "host_threads must be 1..256");
-    c->host_threads = value;
-    affects_plan = false;
-  } else if (n == "table_log2_delta") {
-    if (value < 0 || value > 3)
-      return fail(c, CMPR_EINVAL, "table_log2_delta must be 0..3");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set table_log2_delta before cmpr_set_reference");
-    c->table_log2_delta = value;
-  } else if (n == "part_buckets_log2") {
-    if (value < 2 || value > 30)
-      return fail(c, CMPR_EINVAL, "part_buckets_log2 must be 2..30");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set part_buckets_log2 before cmpr_set_reference");
-    c->part_buckets_log2 = value;
-  } else if (n == "deferred_resolve") {
-    if (value < 0 || value > 1)
-      return fail(c, CMPR_EINVAL, "deferred_resolve must be 0 or 1");
-    c->deferred_resolve = value;
-  } else if (n == "d2_pairs") {
-    if (value < -1 || value > 1)
-      return fail(c, CMPR_EINVAL, "d2_pairs must be -1 (auto), 0 or 1");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set d2_pairs before cmpr_set_reference");
-    c->d2_pairs = value;
-  } else if (n == "d2_buffers") {
-    if (value < 1 || value > 2)
-      return fail(c, CMPR_EINVAL, "d2_buffers must be 1 or 2");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set d2_buffers before cmpr_set_reference");
-    c->d2_buffers = value;
-  } else if (n == "chunk_deal") {
-    if (value < 0 || value > 1)
-      return fail(c, CMPR_EINVAL, "chunk_deal must be 0 (static) or 1 (by a counter)");
-    c->chunk_deal = value;
-  } else if (n == "narrow_upload") {
-    if (value < -1 || value > 1)
-      return fail(c, CMPR_EINVAL, "narrow_upload must be -1 (auto), 0 or 1");
-    c->narrow_upload = value;
-    affects_plan = false;
-  } else if (n == "item_wg" || n == "layout_recompute" || n == "layout_timing" || n == "layout_zob_lds" ||
-             n == "record_tiles") {
-    if (value < 0 || value > (n == "record_tiles" ? 2 : 1))
-      return fail(c, CMPR_EINVAL, n + (n == "record_tiles" ? " must be 0, 1 or 2" : " must be 0 or 1"));
-    if (n == "record_tiles" && c->have_q)
-      return fail(c, CMPR_ESTATE, "set record_tiles before cmpr_set_queries");
-    (n == "item_wg" ? c->item_wg : n == "layout_recompute" ? c->layout_recompute :
-     n == "layout_zob_lds" ? c->layout_zob_lds : n == "record_tiles" ? c->record_tiles : c->layout_timing) = value;
-    affects_plan = false;
-  } else if (n == "assume_never_overflows") {
-    /* TEST ONLY: the next launch runs without redo pass as if the margin had been
-       shown (tests/test_gpu_parity.py forces an overflow behind it) */
-    c->force_no_redo = value != 0;
-    c->usage_pending = false;               /* (a measurement in flight would overrule the pretence) */
-    affects_plan = false;
-  } else if (n == "resolve_blocks_per_cu") {
-    if (value < 1 || value > 8)
-      return fail(c, CMPR_EINVAL, "resolve_blocks_per_cu must be 1..8");
-    c->resolve_blocks_per_cu = value;
-  } else if (n == "pos_segments") {
-    if (value < 1 || value > 256 || (value & (value - 1)))
-      return fail(c, CMPR_EINVAL, "pos_segments must be a power of two, 1..256");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set pos_segments before cmpr_set_queries");
-    c->pos_segments = value;
-  } else if (n == "pos_grow") {
-    if (value < -1 || value > 1)
-      return fail(c, CMPR_EINVAL, "pos_grow must be -1 (auto), 0 or 1");
-    c->pos_grow = value;
-  } else if (n == "pos_capacity") {
-    if (value < 0)
-      return fail(c, CMPR_EINVAL, "pos_capacity must be >= 0");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set pos_capacity before cmpr_set_queries");
-    c->pos_capacity = value;
-  } else if (n == "work_shard_count" || n == "work_shard_index") {
-    if (value < 0 || value > 65535 || (n == "work_shard_count" && value < 1))
-      return fail(c, CMPR_EINVAL, "work_shard_count must be 1..65535, work_shard_index 0..count-1");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set the work shard before cmpr_set_queries");
-    (n == "work_shard_count" ? c->work_shard_count : c->work_shard_index) = value;
-  } else if (n == "small_slice_tiles") {
-    if (value < 0 || value > 64)
-      return fail(c, CMPR_EINVAL, "small_slice_tiles must be 0..64");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set small_slice_tiles before cmpr_set_queries");
-    c->small_slice_tiles = value;
-  } else if (n == "sub2_items") {
-    if (value < -1 || value > 1)
-      return fail(c, CMPR_EINVAL, "sub2_items must be -1 (default), 0 or 1");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set sub2_items before cmpr_set_queries");
-    c->sub2_items = value;
-  } else if (n == "class_rows_unstaged") {
-    if (value < 0 || value > 1)
-      return fail(c, CMPR_EINVAL, "class_rows_unstaged must be 0 or 1");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set class_rows_unstaged before cmpr_set_queries");
-    c->class_rows_unstaged = value;
-  } else if (n == "waves_per_block") {
-    if (value != 4 && value != 8 && value != 16)
-      return fail(c, CMPR_EINVAL, "waves_per_block must be 4, 8 or 16");
-    if (c->have_q)
-      return fail(c, CMPR_ESTATE, "set waves_per_block before cmpr_set_queries");
-    c->waves_per_block = value;
-    c->waves_per_block_forced = true;
-  } else if (n == "bloom_bits_log2_delta") {
-    if (value < -4 || value > 4)
-      return fail(c, CMPR_EINVAL, "bloom_bits_log2_delta must be -4..4");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set bloom_bits_log2_delta before cmpr_set_reference");
-    c->bloom_log2_delta = value;
-  } else if (n == "slice_pages") {
-    if (value < -1 || value > (int64_t)PAGE_E_MAX)
-      return fail(c, CMPR_EINVAL, "slice_pages must be -1..3");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set slice_pages before cmpr_set_reference");
-    c->slice_pages = value;
-  } else if (n == "page_budget") {
-    if (value < 0 || value > (1 << 24))
-      return fail(c, CMPR_EINVAL, "page_budget must be 0..2^24");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set page_budget before cmpr_set_reference");
-    c->page_budget = value;
-  } else if (n == "bucket_bitmap") {
-    if (value < -1 || value > 1)
-      return fail(c, CMPR_EINVAL, "bucket_bitmap must be -1 (auto), 0 or 1");
-    c->bucket_bitmap = value;
-  } else if (n == "fill_slices") {
-    if (value < 0 || value > 1)
-      return fail(c, CMPR_EINVAL, "fill_slices must be 0 or 1");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set fill_slices before cmpr_set_reference");
-    c->fill_slices = value;
-  } else if (n == "direct_slices_log2") {
-    if (value < -1 || value > 12)
-      return fail(c, CMPR_EINVAL, "direct_slices_log2 must be -1 (auto) or 0..12");
-    c->direct_slices_log2 = value;
-  } else if (n == "row_filter_x16") {
-    if (value < 8 || value > 128)
-      return fail(c, CMPR_EINVAL, "row_filter_x16 must be 8..128 (sixteenths of a byte per entry)");
-    if (c->have_ref)
-      return fail(c, CMPR_ESTATE, "set row_filter_x16 before cmpr_set_reference");
-    c->row_filter_x16 = value;
-  } else {
-    return fail(c, CMPR_EINVAL, "unknown tunable: " + n);
   }
   return CMPR_OK;
 }
@@ -534,8 +439,8 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   if (!c || !name || !value)
     return CMPR_EINVAL;
   std::string n(name);
+  /* settable names whose value in effect differs from the stored one */
   if (n == "variant") *value = c->have_ref ? (c->rows ? 2 : c->sliced ? 1 : 0) : c->variant;
-  else if (n == "blocks_per_cu") *value = c->blocks_per_cu;
   else if (n == "bloom_bits_log2_delta") {
     *value = 0;
     for (uint64_t b = std::max<uint64_t>(c->slots, 8); b < c->bloom_words * 8; b <<= 1)
@@ -543,30 +448,25 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   }
   else if (n == "class_residues") *value = c->sliced && c->have_ref ? (int64_t)c->geom.k : c->class_residues;
   else if (n == "slice_words_log2") *value = c->sliced && c->have_ref ? (int64_t)c->geom.words_log2 : c->slice_words_log2;
-  else if (n == "slice_bytes") *value = !c->sliced ? 0 : c->rows ? (int64_t)c->geom.rw_words * ROW_WORD_BYTES : (int64_t)8 << c->geom.words_log2;
-  else if (n == "passes") *value = c->npasses;
+  else if (n == "class_anchor") *value = c->sliced && c->have_ref ? (int64_t)c->geom.c0 : c->class_anchor;
   else if (n == "chunk_tiles") *value = c->chunk_tiles > 0 ? c->chunk_tiles : 8 * c->waves_per_block;
   else if (n == "waves_per_block") *value = c->plan.valid ? (int64_t)c->plan.nw : c->waves_per_block;
-  else if (n == "narrow_upload") *value = c->narrow_upload;
   else if (n == "d2_buffers") *value = c->have_ref && c->d2pairs ? (int64_t)c->geom.nbuf : c->d2_buffers;
   else if (n == "d2_pairs") *value = c->have_ref ? (c->d2pairs ? 1 : 0) : c->d2_pairs;
-  else if (n == "chunk_deal") *value = c->chunk_deal;
+  else if (n == "record_tiles") *value = c->have_q ? (c->rec_tiles ? (c->rec_hash ? 1 : 2) : 0) : c->record_tiles;
+  else if (n == "pos_capacity") *value = (int64_t)(c->pos_cap * c->pos_segments);
+  /* read-only names */
+  else if (n == "slice_bytes") *value = !c->sliced ? 0 : c->rows ? (int64_t)c->geom.rw_words * ROW_WORD_BYTES : (int64_t)8 << c->geom.words_log2;
+  else if (n == "passes") *value = c->npasses;
   else if (n == "layout_upload_us") *value = (int64_t)(c->layout_upload_ms * 1e3);
   else if (n == "layout_tail_us") *value = (int64_t)(c->layout_tail_ms * 1e3);
   else if (n == "layout_total_us") *value = (int64_t)(c->layout_total_ms * 1e3);
-  else if (n == "item_wg") *value = c->item_wg;
-  else if (n == "layout_recompute") *value = c->layout_recompute;
-  else if (n == "layout_timing") *value = c->layout_timing;
-  else if (n == "record_tiles") *value = c->have_q ? (c->rec_tiles ? (c->rec_hash ? 1 : 2) : 0) : c->record_tiles;
   else if (n == "layout_keys_us") *value = (int64_t)(c->layout_kernel_ms[0] * 1e3);
   else if (n == "layout_sizes_us") *value = (int64_t)(c->layout_kernel_ms[1] * 1e3);
   else if (n == "layout_scatter_us") *value = (int64_t)(c->layout_kernel_ms[2] * 1e3);
   else if (n == "layout_tiles_us") *value = (int64_t)(c->layout_kernel_ms[3] * 1e3);
   else if (n == "layout_order_us") *value = (int64_t)(c->layout_kernel_ms[4] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
-  else if (n == "debug") *value = c->debug;
-  else if (n == "heavy_threshold") *value = c->heavy_threshold;
-  else if (n == "class_anchor") *value = c->sliced && c->have_ref ? (int64_t)c->geom.c0 : c->class_anchor;
   else if (n == "heavy_buckets") {
     *value = 0;
     if (c->sliced && c->have_ref)
@@ -577,27 +477,8 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "tiles") *value = c->ntiles;
   else if (n == "chunks") *value = c->nchunks;
   else if (n == "small_tiles") *value = c->nsmall;
-  else if (n == "small_slice_tiles") *value = c->small_slice_tiles;
-  else if (n == "sub2_items") *value = c->sub2_items;
-  else if (n == "work_shard_count") *value = c->work_shard_count;
-  else if (n == "work_shard_index") *value = c->work_shard_index;
-  else if (n == "class_rows_unstaged") *value = c->class_rows_unstaged;
-  else if (n == "deferred_resolve") *value = c->deferred_resolve;
-  else if (n == "table_log2_delta") *value = c->table_log2_delta;
-  else if (n == "part_buckets_log2") *value = c->part_buckets_log2;
   else if (n == "reference_parts") *value = c->have_ref ? (int64_t)c->nparts : 0;
-  else if (n == "row_filter_x16") *value = c->row_filter_x16;
-  else if (n == "fill_slices") *value = c->fill_slices;
-  else if (n == "direct_slices_log2") *value = c->direct_slices_log2;
-  else if (n == "bucket_bitmap") *value = c->bucket_bitmap;
-  else if (n == "slice_pages") *value = c->slice_pages;
-  else if (n == "page_budget") *value = c->page_budget;
   else if (n == "page_slices") *value = (int64_t)c->page_slices;
-  else if (n == "host_threads") *value = c->host_threads;
-  else if (n == "pos_capacity") *value = (int64_t)(c->pos_cap * c->pos_segments);
-  else if (n == "pos_segments") *value = c->pos_segments;
-  else if (n == "pos_grow") *value = c->pos_grow;
-  else if (n == "resolve_blocks_per_cu") *value = c->resolve_blocks_per_cu;
   else if (n == "query_slots") *value = (int64_t)c->ntiles * WAVE;
   else if (n == "items") *value = (int64_t)c->items.n;       /* variant 2 / sub2: item slots, padding included */
 #ifdef CMPR_PHASE_TIMING
@@ -609,6 +490,8 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
     *value = (int64_t)x;
   }
 #endif
+  else if (const Tunable *t = find_tunable(name); t && t->field && !(t->flags & T_WRITE_ONLY))
+    *value = c->*t->field;
   else
     return fail(c, CMPR_EINVAL, "unknown tunable: " + n);
   return CMPR_OK;
@@ -1437,6 +1320,31 @@ int check_ready(cmpr_context *c)
   return CMPR_OK;
 }
 
+/* One step on the context's stream that the host waits for, behind every synchronous entry point: `before`
+   queues what each attempt needs in front of the kernels, `after` the copy-out behind them (both return a
+   CMPR_ code).  A launch that relied on the no-redo shortcut and overflowed all the same is repeated once,
+   now with the redo pass behind it: no caller is handed an incomplete result. */
+template <typename Before, typename After>
+int run_step_and_wait(cmpr_context *c, unsigned long long *d_out, Before before, After after)
+{
+  for (int attempt = 0;; attempt++) {
+    int rc;
+    if ((rc = before()) || (rc = enqueue_overlap(c, d_out, c->stream)) || (rc = after()) ||
+        (rc = fetch_overflow_word(c, c->stream)))
+      return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+    c->stop_is_k1 = false;
+    c->events_valid = true;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!overflowed_without_redo(c, c->stream))
+      return CMPR_OK;
+    if (attempt)
+      return fail(c, CMPR_ESTATE, "positives buffer overflowed twice without redo pass");
+  }
+}
+
+const auto no_hook = [] { return (int)CMPR_OK; };
+
 }  // namespace
 
 extern "C" int cmpr_overlap_matrix_device(cmpr_context *c, void *d_matrix, void *stream)
@@ -1448,25 +1356,8 @@ extern "C" int cmpr_overlap_matrix_device(cmpr_context *c, void *d_matrix, void 
     return fail(c, CMPR_EINVAL, "d_matrix is NULL");
   if (is_f64_score(c->opt))
     return fail(c, CMPR_EINVAL, "ratio score needs cmpr_overlap_matrix_f64");
-  if (!stream) {
-    /* synchronous use: checked like the other synchronous entry points -- a launch that
-       relied on the no-redo shortcut and overflowed is repeated with the redo pass */
-    for (int attempt = 0;; attempt++) {
-      rc = enqueue_overlap(c, (unsigned long long *)d_matrix, c->stream);
-      if (rc)
-        return rc;
-      if ((rc = fetch_overflow_word(c, c->stream)))
-        return rc;
-      HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-      c->stop_is_k1 = false;
-      c->events_valid = true;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      if (!overflowed_without_redo(c, c->stream))
-        return CMPR_OK;
-      if (attempt)
-        return fail(c, CMPR_ESTATE, "positives buffer overflowed twice without redo pass");
-    }
-  }
+  if (!stream)      /* synchronous use: checked like the other synchronous entry points */
+    return run_step_and_wait(c, (unsigned long long *)d_matrix, no_hook, no_hook);
   hipStream_t st = (hipStream_t)stream;
   rc = enqueue_overlap(c, (unsigned long long *)d_matrix, st);
   if (rc)
@@ -1488,27 +1379,11 @@ extern "C" int cmpr_overlap_matrix(cmpr_context *c, uint64_t *out)
   if (is_f64_score(c->opt))
     return fail(c, CMPR_EINVAL, "ratio score needs cmpr_overlap_matrix_f64");
   const size_t cells = (size_t)c->R1 * c->R2;
-  for (int attempt = 0;; attempt++) {
-    rc = enqueue_overlap(c, c->matrix.p, c->stream);
-    if (rc)
-      return rc;
+  return run_step_and_wait(c, c->matrix.p, no_hook, [&]() -> int {
     if (cells)
-      HIP_TRY(c, hipMemcpyAsync(out, c->matrix.p, cells * sizeof(uint64_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_overflow_word(c, c->stream)))
-      return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->stop_is_k1 = false;
-    c->events_valid = true;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    /* a launch that relied on the no-redo shortcut and overflowed all the same: once
-       more, now with the redo pass behind it */
-    if (!overflowed_without_redo(c, c->stream))
-      break;
-    if (attempt)
-      return fail(c, CMPR_ESTATE, "positives buffer overflowed twice without redo pass");
-  }
-  return CMPR_OK;
+      HIP_TRY(c, hipMemcpyAsync(out, c->matrix.p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    return CMPR_OK;
+  });
 }
 
 static int cmpr_overlap_matrix_f64_impl(cmpr_context *c, double *out)
@@ -1520,29 +1395,15 @@ static int cmpr_overlap_matrix_f64_impl(cmpr_context *c, double *out)
     return fail(c, CMPR_EINVAL, "matrix_out is NULL");
   const size_t cells = (size_t)c->R1 * c->R2;
   std::vector<unsigned long long> tmp(cells);
-  for (int attempt = 0;; attempt++) {
-    rc = enqueue_overlap(c, c->matrix.p, c->stream);
-    if (rc)
-      return rc;
-    if (cells) {
-      if (is_f64_score(c->opt))
-        HIP_TRY(c, hipMemcpyAsync(out, c->matrix_f64.p, cells * sizeof(double),
-                                  hipMemcpyDeviceToHost, c->stream));
-      else
-        HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->matrix.p, cells * sizeof(uint64_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-    }
-    if ((rc = fetch_overflow_word(c, c->stream)))
-      return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->stop_is_k1 = false;
-    c->events_valid = true;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!overflowed_without_redo(c, c->stream))
-      break;
-    if (attempt)
-      return fail(c, CMPR_ESTATE, "positives buffer overflowed twice without redo pass");
-  }
+  rc = run_step_and_wait(c, c->matrix.p, no_hook, [&]() -> int {
+    if (cells && is_f64_score(c->opt))
+      HIP_TRY(c, hipMemcpyAsync(out, c->matrix_f64.p, cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    else if (cells)
+      HIP_TRY(c, hipMemcpyAsync(tmp.data(), c->matrix.p, cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    return CMPR_OK;
+  });
+  if (rc)
+    return rc;
   if (!is_f64_score(c->opt)) {
     const bool mean = c->opt.score == CMPR_SCORE_MEAN && !c->opt.ignore_counts;
     for (size_t k = 0; k < cells; k++)
@@ -1574,23 +1435,11 @@ extern "C" int cmpr_overlap_pairs(cmpr_context *c, uint64_t capacity, uint32_t *
   c->pair_count = dn.p;
   c->pair_cap = capacity;
   unsigned long long n = 0;
-  for (int attempt = 0;; attempt++) {
-    HIP_TRY(c, hipMemsetAsync(dn.p, 0, sizeof(unsigned long long), c->stream));
-    rc = enqueue_overlap(c, c->matrix.p, c->stream);
-    if (rc)
-      return rc;
-    HIP_TRY(c, hipMemcpyAsync(&n, dn.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_overflow_word(c, c->stream)))
-      return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->stop_is_k1 = false;
-    c->events_valid = true;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (!overflowed_without_redo(c, c->stream))
-      break;
-    if (attempt)
-      return fail(c, CMPR_ESTATE, "positives buffer overflowed twice without redo pass");
-  }
+  rc = run_step_and_wait(c, c->matrix.p,
+      [&]() -> int { HIP_TRY(c, hipMemsetAsync(dn.p, 0, sizeof(unsigned long long), c->stream)); return CMPR_OK; },
+      [&]() -> int { HIP_TRY(c, hipMemcpyAsync(&n, dn.p, sizeof n, hipMemcpyDeviceToHost, c->stream)); return CMPR_OK; });
+  if (rc)
+    return rc;
   const uint64_t have = std::min<uint64_t>(n, capacity);
   if (have) {
     HIP_TRY(c, hipMemcpy(query_out, dq.p, have * sizeof(uint32_t), hipMemcpyDeviceToHost));

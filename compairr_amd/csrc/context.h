@@ -152,7 +152,7 @@ struct cmpr_context {
   hipEvent_t   pending_launch = nullptr;
   std::string  err;
 
-  /* tunables */
+  /* tunables: each is set through its row of TUNABLES (compairr_hip.hip), which holds its range and when it locks */
   int64_t blocks_per_cu = 8;
   int64_t variant = -1;           /* 0: one global Bloom; 1: LDS-staged slices; 2: LDS-staged
                                      row filter (kernels_rows.h); -1: by alphabet */
@@ -160,7 +160,7 @@ struct cmpr_context {
   int64_t row_filter_x16 = 32;    /* variant 2: filter bytes per entry, in sixteenths (32 = 2 bytes: 16 bits per
                                      entry, eight of them set) */
   int64_t slice_pages = -1;       /* variant 2, d = 1: overfull slices get up to 2^this pages; -1 = up to 8, 0 = none */
-  int64_t page_budget = 0;        /* entries a slice may hold before it gets pages; 0 = 24 per word (tests: small) */
+  int64_t page_budget = 0;        /* entries a slice may hold before it gets pages; 0 = 20 per word (tests: small) */
   int64_t bucket_bitmap = -1;     /* resolve_kernel asks the bucket bitmap before it reads a slot of the record table:
                                      -1 = where most positives are false (d = 2), 0 never, 1 always */
   int64_t direct_slices_log2 = -1; /* d = 0 on variant 0: pseudo-slices of the query layout (-1: by the number of queries) */
@@ -191,6 +191,17 @@ struct cmpr_context {
   bool    waves_per_block_forced = false;
   int64_t debug = 0;              /* ablation switches (layout.h DBG_*), -DCMPR_ABLATION builds only */
   int64_t slice_words_log2 = -1;  /* -1: 12 (8-byte words, variant 1) / 11 (16-byte words, variant 2) */
+  int64_t part_buckets_log2 = 30; /* set 2 in parts: the most buckets of one part's record table */
+  int64_t d2_pairs = -1;          /* nucleotides, d = 2 on pair rows (kernels_pairs2.h): -1 auto, 0 off, 1 on */
+  int64_t d2_buffers = 1;         /* slice buffers of that kernel (layout.h SliceGeom::nbuf; cfg5: 51 ms with one, 60 with two) */
+  int64_t narrow_upload = -1;     /* the narrowed upload of cmpr_set_queries: -1 auto, 0 off, 1 on */
+  /* of the query layout (query_layout.hip): item counters per workgroup in LDS, hashes worked out from the
+     records by fill_tiles_kernel (both 1 = default; 0 = round 5's form, kept for A/B and the parity suite),
+     and HIP events around its big kernels (default 0) */
+  int64_t item_wg = 1, layout_recompute = 1, layout_timing = 0;
+  int64_t layout_zob_lds = 1;     /* keys_kernel keeps the Zobrist keys in LDS when they fit */
+  int64_t record_tiles = 1;       /* 1 = where the layout allows (layout.h rec_tiles), the hash in the record where
+                                     the sequences leave room; 2 = never the hash (rows) */
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */
@@ -225,7 +236,6 @@ struct cmpr_context {
   uint64_t          slots = 0, bloom_words = 0;     /* slots: buckets of the record table (a power of two) */
   /* set 2 in parts (ref_index.hip): when one record table cannot hold it, contiguous sequence ranges, each
      with its own filter words, records and bitmap; everything the query layout reads is shared */
-  int64_t           part_buckets_log2 = 30;   /* tunable: the most buckets of one part's record table */
   uint32_t          nparts = 1;
   uint64_t          part0_n = 0;              /* sequences of part 0 (first 0) */
   std::vector<RefPart> xparts;                /* parts 1 .. nparts - 1 */
@@ -255,8 +265,6 @@ struct cmpr_context {
   DevBuf<cmpr::ResPack> cpk;             /* sub2 items: the query's residues, 2 bits each */
   DevBuf<cmpr::ResPack> qpk;             /* nucleotides, d = 2 on pair rows: per slot, the query's residues */
   bool              d2pairs = false;    /* ... that kernel is in use (kernels_pairs2.h; decided with the index) */
-  int64_t           d2_pairs = -1;      /* tunable: -1 auto, 0 off, 1 on */
-  int64_t           d2_buffers = 1;     /* tunable: slice buffers of that kernel (layout.h SliceGeom::nbuf; cfg5: 51 ms with one, 60 with two) */
   uint64_t          algorithmic_bytes = 0;
   double            max_cell_bound = 0;   /* max_i total1[i] * max_j total2[j] */
   std::vector<double> tot1, tot2;
@@ -290,20 +298,12 @@ struct cmpr_context {
   DevArena                   arena_a, arena_b;            /* temporaries of cmpr_set_queries */
   void                      *stage_host = nullptr;        /* pinned staging of the narrowed upload */
   size_t                     stage_host_bytes = 0;
-  int64_t                    narrow_upload = -1;          /* tunable: -1 auto, 0 off, 1 on */
   hipStream_t                copy_stream = nullptr;       /* uploads of cmpr_set_queries */
   static const uint32_t      NCOPY_EV = 4;
   hipEvent_t                 ev_copy[NCOPY_EV] = {};
   /* of the last cmpr_set_queries: host time inside the copies, from the last copy to the
      end (the device work the upload did not hide), and in all */
   double                     layout_upload_ms = 0, layout_tail_ms = 0, layout_total_ms = 0;
-  /* tunables of the query layout (query_layout.hip): item counters per workgroup in LDS, hashes worked out
-     from the records by fill_tiles_kernel (both 1 = default; 0 = round 5's form, kept for A/B and the
-     parity suite), and HIP events around its big kernels (tunable "layout_timing", default 0) */
-  int64_t                    item_wg = 1, layout_recompute = 1, layout_timing = 0;
-  int64_t                    layout_zob_lds = 1;          /* keys_kernel keeps the Zobrist keys in LDS when they fit */
-  int64_t                    record_tiles = 1;            /* tunable: 1 = where the layout allows (layout.h rec_tiles), the hash in
-                                                             the record where the sequences leave room; 2 = never the hash (rows) */
   bool                       rec_tiles = false;           /* the resident layout has no per-slot arrays: the probe
                                                              kernel reads the queries' records (layout.h ProbeParams) */
   bool                       rec_hash = false;            /* ... and the query's hash lies in the record (layout.h rec_tiles == 2) */

@@ -398,16 +398,29 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
      "pos_grow"              the positives buffer grows to what a launch showed when it overflowed:
                              -1 (default) when its size was automatic, 1 also from a given
                              "pos_capacity", 0 never
-     "deferred_resolve", "resolve_blocks_per_cu", "pos_segments", "pos_capacity",
-     "heavy_threshold", "class_anchor", "class_rows_unstaged",
-     "host_threads"          see compairr_amd/csrc/compairr_hip.hip
+     "deferred_resolve"      1 (default): the filter's positives are queued and walked by a second kernel; 0: the
+                             probe kernel resolves them itself
+     "resolve_blocks_per_cu" resident workgroups per CU that second kernel's grid is sized for (1..8, default 5)
+     "pos_segments"          independently claimed parts of the queue of positives: a power of two, 1..256 (default 64)
+     "pos_capacity"          entries of that queue, all segments together (0 = default: from the number of queries)
+     "heavy_threshold"       population above which a class is split over several slices (-1 = default: from
+                             the slice size; 0: every class)
+     "class_anchor"          first of the sequence positions the class is taken from (-1 = default: from the
+                             lengths of set 2; up to 65535)
+     "class_rows_unstaged"   variant 2: 1: the tiles of the class rows read the filter where it lies; 0 (default): staged
+     "host_threads"          threads of the host-side passes over a set (1..256; default: the machine's, at most 16)
      "assume_never_overflows" TEST ONLY: the next launch runs without redo pass as if
                              the margin had been shown
-   "variant", "bloom_bits_log2_delta", "class_residues", "slice_words_log2", "d2_pairs", "d2_buffers",
-   "table_log2_delta", "part_buckets_log2", "slice_pages", "page_budget", "fill_slices" and "row_filter_x16" must be set before
-   cmpr_set_reference(); "chunk_tiles", "waves_per_block",
-   "small_slice_tiles", "direct_slices_log2" and the work shard before cmpr_set_queries().  ("debug" exists
-   only in a -DCMPR_ABLATION build of the library.) */
+   What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
+   the state):
+     before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",
+                                   "heavy_threshold", "slice_words_log2", "d2_pairs", "d2_buffers", "table_log2_delta",
+                                   "part_buckets_log2", "slice_pages", "page_budget", "fill_slices", "row_filter_x16"
+     before cmpr_set_queries():    "chunk_tiles", "waves_per_block", "small_slice_tiles", "sub2_items",
+                                   "class_rows_unstaged", "pos_segments", "pos_capacity", "work_shard_count",
+                                   "work_shard_index", "record_tiles"
+     at any time:                  every other name; "direct_slices_log2" takes effect at the next cmpr_set_queries()
+   ("debug" exists only in a -DCMPR_ABLATION build of the library.) */
 int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
 
 /* Current value of a tunable (for the data-dependent ones, the value in effect

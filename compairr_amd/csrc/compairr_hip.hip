@@ -360,6 +360,9 @@ const Tunable TUNABLES[] = {
   {"layout_zob_lds", F(layout_zob_lds), 0, 1, LOCK_NEVER, T_NO_PLAN | T_WRITE_ONLY, BOOL_RANGE},
   {"record_tiles", F(record_tiles), 0, 2, LOCK_QUERIES, T_NO_PLAN, " must be 0, 1 or 2"},
   {"assume_never_overflows", nullptr, INT64_MIN, INT64_MAX, LOCK_NEVER, T_NO_PLAN | T_WRITE_ONLY, "", nullptr, pretend_never_overflows},
+  /* TEST ONLY: at 0 every occupied slot of a chain has the sequence's tag, and the "same tag, another sequence,
+     next slot" path of dedup_insert_kernel (dedup.hip) runs on ordinary data (tests/test_dedup_gpu.py) */
+  {"dedup_tag_bits", F(dedup_tag_bits), 0, 32, LOCK_NEVER, T_NO_PLAN, " must be 0..32"},
   {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
   {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
   {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},

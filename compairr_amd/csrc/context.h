@@ -202,6 +202,7 @@ struct cmpr_context {
   int64_t layout_zob_lds = 1;     /* keys_kernel keeps the Zobrist keys in LDS when they fit */
   int64_t record_tiles = 1;       /* 1 = where the layout allows (layout.h rec_tiles), the hash in the record where
                                      the sequences leave room; 2 = never the hash (rows) */
+  int64_t dedup_tag_bits = 32;    /* TEST ONLY: bits of the hash a table word of cmpr_deduplicate carries (dedup.hip) */
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */

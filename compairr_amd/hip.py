@@ -27,6 +27,7 @@ EXPORTS = [
     "cmpr_set_reference_device", "cmpr_set_queries_device",
     "cmpr_route_queries", "cmpr_route_pack", "cmpr_set_queries_routed",
     "cmpr_warm_up", "cmpr_warm_up_sized",
+    "cmpr_deduplicate", "cmpr_deduplicate_device",
 ]
 
 
@@ -143,6 +144,9 @@ def load_library() -> C.CDLL:
     lib.cmpr_overlap_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                        C.POINTER(C.c_uint64)]
     lib.cmpr_count_duplicates.argtypes = [C.c_void_p, C.POINTER(_SetView), C.POINTER(C.c_uint64)]
+    lib.cmpr_deduplicate.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_uint64, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    lib.cmpr_deduplicate_device.argtypes = lib.cmpr_deduplicate.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -320,6 +324,30 @@ class HipOverlap:
             self._ctx, C.byref(v) if v is not None else None, C.byref(out)))
         return out.value
 
+    # ---- the duplicates of a set merged (include/compairr_hip.h: cmpr_deduplicate*) ----
+
+    def deduplicate(self, s: RepertoireSet):
+        """(first uint32[n_unique], count uint64[n_unique], merged): per class of equal entries of `s`, in
+        increasing `first`, its smallest sequence number and its summed duplicate_count (with ignore_counts
+        its size); merged = n - n_unique, the reference's "Duplicates merged:" (dedup.cc:192)."""
+        v = _view(s)
+        first = np.zeros(s.n, dtype=np.uint32)
+        count = np.zeros(s.n, dtype=np.uint64)
+        unique, merged = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.cmpr_deduplicate(self._ctx, C.byref(v), s.n, first.ctypes.data, count.ctypes.data,
+                                               C.byref(unique), C.byref(merged)))
+        return first[:unique.value].copy(), count[:unique.value].copy(), merged.value
+
+    def deduplicate_device(self, view: _SetView, capacity: int = 0, d_first: int = 0, d_count: int = 0):
+        """The same for a view of device pointers (device_view): up to `capacity` classes are written to the
+        device arrays d_first (uint32) and d_count (uint64); returns (n_unique, merged).  capacity = 0 with no
+        arrays only counts."""
+        unique, merged = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.cmpr_deduplicate_device(
+            self._ctx, C.byref(view), capacity, C.c_void_p(d_first or None), C.c_void_p(d_count or None),
+            C.byref(unique), C.byref(merged)))
+        return unique.value, merged.value
+
     def kernel_times(self, max_calls: int = 64):
         """(kernel_ms[], probe_ms[]) of the last calls, oldest first (HIP events)."""
         n = min(max_calls, 63)
@@ -345,3 +373,16 @@ def overlap(set1: RepertoireSet, set2: RepertoireSet, opt: Options):
         h.set_queries(set1)
         m = h.overlap_matrix_f64()
         return m, h.stats()
+
+
+def deduplicate(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
+    """Convenience: (merged_set, merged) -- `s` with every class of equal entries reduced to its first
+    member, which carries the class's summed count (the reference's --deduplicate, dedup.cc).  `tunables`
+    are set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        first, count, merged = h.deduplicate(s)
+    out = s.subset(first)
+    out.count = count
+    return out, merged

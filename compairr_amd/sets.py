@@ -100,6 +100,33 @@ class RepertoireSet:
             pc.write_csv(tbl, fh, write_options=pc.WriteOptions(
                 include_header=False, delimiter="\t", quoting_style="none"))
 
+    def dedup_tsv(self, ignore_genes: bool = False, cdr3: bool = False) -> bytes:
+        """The set in the format the reference's --deduplicate writes (dedup.cc:45-56, 177-181): a header
+        `repertoire_id, duplicate_count[, v_call, j_call], <sequence column>` and one line per entry; the
+        gene columns are dropped with `ignore_genes`; nucleotides are printed in lower case
+        (db_fprint_sequence, db.cc:1035-1049)."""
+        nucleotides = self.alphabet == NT
+        col = ("cdr3" if cdr3 else "junction") + ("" if nucleotides else "_aa")
+        letters = self.alphabet.lower() if nucleotides else self.alphabet
+        lut = np.frombuffer(letters.encode(), dtype=np.uint8)
+        text = lut[self.residues].tobytes()
+        off = self.offsets.astype(np.int64)
+        vn = self.v_names or ["V%d" % k for k in range(int(self.v_gene.max(initial=0)) + 1)]
+        jn = self.j_names or ["J%d" % k for k in range(int(self.j_gene.max(initial=0)) + 1)]
+        out = [("\t".join(["repertoire_id", "duplicate_count"] + ([] if ignore_genes else ["v_call", "j_call"])
+                          + [col]) + "\n").encode()]
+        for i in range(self.n):
+            fields = [self.repertoire_ids[int(self.repertoire[i])].encode(), b"%d" % int(self.count[i])]
+            if not ignore_genes:
+                fields += [vn[int(self.v_gene[i])].encode(), jn[int(self.j_gene[i])].encode()]
+            fields.append(text[off[i]:off[i + 1]])
+            out.append(b"\t".join(fields) + b"\n")
+        return b"".join(out)
+
+    def write_dedup_tsv(self, path: str, ignore_genes: bool = False, cdr3: bool = False) -> None:
+        with open(path, "wb") as fh:
+            fh.write(self.dedup_tsv(ignore_genes, cdr3))
+
     def write_tsv(self, path: str, nucleotides: bool = False, cdr3: bool = False,
                   crlf: bool = False) -> None:
         """AIRR rearrangement TSV with the columns the path needs."""

@@ -31,6 +31,8 @@
 extern "C" {
 #endif
 
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*) break no caller
+   and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
 enum {
@@ -294,6 +296,46 @@ int cmpr_overlap_pairs(cmpr_context *ctx, uint64_t capacity, uint32_t *query_out
 int cmpr_count_duplicates(cmpr_context *ctx, const cmpr_set_view *set, uint64_t *out);
 
 /*
+ * The duplicates of one set MERGED: the reference's --deduplicate (process() and report(),
+ * dedup.cc:27-132; the loops of dedup(), dedup.cc:184-199).  Two sequences of `set` are the same entry when
+ * they have the same repertoire number, the same V and J gene numbers (unless ignore_genes), the same length
+ * and the same residues (dedup.cc:90-111); never across repertoires, not even with ignore_genes.  Per
+ * equivalence class, in increasing `first` -- the order the reference prints them in --:
+ *   first_out[k]  the smallest sequence number of the class (the reference prints a class at its first
+ *                 member, with that member's ids);
+ *   count_out[k]  the sum of duplicate_count over the class, with ignore_counts the number of its members
+ *                 (dedup.cc:34-43); uint64 arithmetic, which wraps as the reference's does.
+ * Up to `capacity` classes are written; *n_unique_out = the number of classes, *merged_out = n - classes --
+ * the reference's "Duplicates merged:" figure, and what cmpr_count_duplicates() returns for the same set --
+ * are always exact, are HOST pointers in both variants, and either may be NULL.  capacity == 0 with NULL
+ * arrays only counts, as in cmpr_overlap_pairs().  n == 0 is CMPR_OK with zero classes.
+ *
+ * `set` is required (NULL: CMPR_EINVAL) and means what it means in cmpr_set_queries(): a HOST view, uploaded
+ * and validated like every other set (same codes and messages).  cmpr_deduplicate_device() takes a DEVICE
+ * view as cmpr_set_queries_device() does, and writes d_first_out / d_count_out -- device memory of
+ * `capacity` elements on the context's device -- where they lie: nothing crosses PCIe but two offsets and
+ * the class count.  The caller's arrays are only read, and may be freed once the call has returned.
+ *
+ * Synchronous; may be called at any time after cmpr_create(); the options' `differences` and `indels` play
+ * no part (the reference insists on d = 0 at its command line; here they are ignored).  Does not disturb
+ * the resident sets, plans or statistics.  Every temporary is freed before the call returns, also when it
+ * fails.  Results are identical from run to run (integer sums; the smallest number of a class does not
+ * depend on the schedule).
+ *
+ * Footprint per sequence, for the duration of the call: the validated copy of the set (~45 bytes; also for
+ * a device view), one 8-byte table word per slot of ONE open-addressing table under the 70 % rule of
+ * hashtable.cc:24 (11.4 to 22.9 bytes), 4 bytes for its slot and 8 for its sum: 70 to 80 bytes, plus 12
+ * per class written by the host variant.  At most 2^32-64 sequences (CMPR_EUNSUPPORTED, "more than 2^32-64
+ * sequences in one set"); no parts: a table or temporary that does not fit is CMPR_ENOMEM.
+ */
+int cmpr_deduplicate(cmpr_context *ctx, const cmpr_set_view *set, uint64_t capacity,
+                     uint32_t *first_out, uint64_t *count_out,
+                     uint64_t *n_unique_out, uint64_t *merged_out);
+int cmpr_deduplicate_device(cmpr_context *ctx, const cmpr_set_view *d_set, uint64_t capacity,
+                            uint32_t *d_first_out, uint64_t *d_count_out,
+                            uint64_t *n_unique_out, uint64_t *merged_out);
+
+/*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
  * runtime, the device's context, the code objects of the kernels the given options will run.
  * The reference has no counterpart -- its threads start in microseconds (overlap.cc:926-936);
@@ -411,6 +453,10 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
      "host_threads"          threads of the host-side passes over a set (1..256; default: the machine's, at most 16)
      "assume_never_overflows" TEST ONLY: the next launch runs without redo pass as if
                              the margin had been shown
+     "dedup_tag_bits"        TEST ONLY: bits of the hash a table word of cmpr_deduplicate() carries beside the
+                             sequence number (0..32, default 32).  At 0 every occupied slot of a chain passes
+                             the tag test and is compared in full: the path a tag collision takes, a 2^-32
+                             event otherwise
    What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
    the state):
      before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",

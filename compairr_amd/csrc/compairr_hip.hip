@@ -500,197 +500,6 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   return CMPR_OK;
 }
 
-/* duplicates of a set in parts: part p's entries against the tables of parts 0 .. p (kernels.h
-   count_duplicates_parts_kernel); D names the set (global arrays) and the counter, cleared */
-static int count_duplicates_in_parts(cmpr_context *c, const DupParams &D, const std::vector<DupTable> &tabs,
-                                     const std::vector<uint64_t> &first, uint64_t *out)
-{
-  int rc;
-  DevBuf<DupTable> d_tabs;
-  struct Tc { DevBuf<DupTable> &t; ~Tc() { t.release(); } } tclean{d_tabs};
-  if ((rc = dev_upload(c, d_tabs, tabs.data(), tabs.size()))) return rc;
-  DupPartsParams B{};
-  B.zob = D.zob; B.A = D.A; B.zpos = D.zpos; B.n_v = D.n_v; B.use_genes = D.use_genes;
-  B.res = D.res; B.off = D.off; B.v = D.v; B.j = D.j; B.rep = D.rep;
-  B.tables = d_tabs.p;
-  B.count = D.count;
-  for (size_t p = 0; p < tabs.size(); p++) {
-    B.first = first[p];
-    B.n = first[p + 1] - first[p];
-    B.ntables = (uint32_t)p + 1;
-    if (B.n) {
-      hipLaunchKernelGGL(count_duplicates_parts_kernel, dim3((uint32_t)((B.n + BLOCK_THREADS - 1) / BLOCK_THREADS)),
-                         dim3(BLOCK_THREADS), 0, c->stream, B);
-      HIP_TRY(c, hipGetLastError());
-    }
-  }
-  unsigned long long hc = 0;
-  HIP_TRY(c, hipMemcpyAsync(&hc, D.count, sizeof hc, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *out = hc;
-  return CMPR_OK;
-}
-
-static int cmpr_count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, uint64_t *out)
-{
-  if (!c || !out)
-    return CMPR_EINVAL;
-  HIP_TRY(c, hipSetDevice(c->device));
-  *out = 0;
-  const uint32_t A = (uint32_t)c->opt.alphabet_size;
-  const uint32_t n_v = c->opt.ignore_genes ? 0 : c->opt.n_v_genes;
-  DevBuf<unsigned long long> d_count;
-  DevBuf<uint8_t> res;
-  DevBuf<uint64_t> off;
-  DevBuf<uint32_t> v, j, rep;
-  DevBuf<Slot> table;
-  struct Cleanup {
-    DevBuf<unsigned long long> &a; DevBuf<uint8_t> &b; DevBuf<uint64_t> &c1;
-    DevBuf<uint32_t> &d1, &d2, &d3; DevBuf<Slot> &e;
-    ~Cleanup() { a.release(); b.release(); c1.release();
-                 d1.release(); d2.release(); d3.release(); e.release(); }
-  } cleanup{d_count, res, off, v, j, rep, table};
-  int rc;
-  if ((rc = dev_alloc(c, d_count, 1))) return rc;
-  HIP_TRY(c, hipMemsetAsync(d_count.p, 0, sizeof(unsigned long long), c->stream));
-
-  DupParams D{};
-  D.A = A;
-  D.n_v = n_v;
-  D.use_genes = c->opt.ignore_genes ? 0u : 1u;
-  D.count = d_count.p;
-  if (!s) {
-    if (!c->have_ref)
-      return fail(c, CMPR_ESTATE, "cmpr_set_reference must be called first");
-    D.zob = c->zob.p;
-    D.zpos = c->zpos;
-    D.res = c->res2.p; D.off = c->off2.p; D.v = c->v2.p; D.j = c->j2.p; D.rep = c->rep2.p;
-    D.n = c->n2;
-    D.rec = c->rec2.p;
-    D.dir_mask = (uint32_t)(c->slots - 1);
-    if (c->nparts > 1) {
-      /* set 2 in parts: each part's entries looked up in the record tables of it and of the parts before */
-      std::vector<DupTable> tabs(c->nparts);
-      std::vector<uint64_t> first(c->nparts + 1);
-      tabs[0] = DupTable{c->rec2.p, c->slots - 1, 0, 1u, 0u};
-      first[0] = 0;
-      for (uint32_t k = 1; k < c->nparts; k++) {
-        const RefPart &rp = c->xparts[k - 1];
-        tabs[k] = DupTable{rp.rec.p, rp.slots - 1, 0, 1u, 0u};
-        first[k] = rp.first;
-      }
-      first[c->nparts] = c->n2;
-      if ((rc = count_duplicates_in_parts(c, D, tabs, first, out))) return rc;
-      return CMPR_OK;
-    }
-  } else {
-    std::string why;
-    if ((rc = validate_view(c->opt, s, why)))
-      return fail(c, rc, why);
-    /* upload + validation on the device (query_layout.hip) */
-    uint32_t longest = 0;
-    std::vector<double> tot;
-    DevBuf<uint64_t> cnt_tmp;
-    struct Ct { DevBuf<uint64_t> &z; ~Ct() { z.release(); } } ctclean{cnt_tmp};
-    if ((rc = cmpr_upload_and_validate(c, s, res, off, v, j, rep, cnt_tmp, longest, tot)))
-      return rc;
-    /* own Zobrist keys when no reference set is resident or it is too short */
-    DevBuf<uint64_t> zob_own;
-    struct Z { DevBuf<uint64_t> &z; ~Z() { z.release(); } } zclean{zob_own};
-    uint32_t zpos = c->zpos;
-    const uint64_t *zob = c->zob.p;
-    if (!c->have_ref || longest + EXTRA_POSITIONS > c->zpos) {
-      zpos = longest + EXTRA_POSITIONS;
-      const uint32_t n_j = c->opt.ignore_genes ? 0 : c->opt.n_j_genes;
-      std::vector<uint64_t> z((size_t)A * zpos + n_v + n_j);
-      SplitMix64 rng(0x6475706c69636174ull);
-      for (auto &x : z)
-        x = rng.next();
-      if ((rc = dev_upload(c, zob_own, z.data(), z.size()))) return rc;
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      zob = zob_own.p;
-    }
-    D.zob = zob; D.zpos = zpos;
-    D.res = res.p; D.off = off.p; D.v = v.p; D.j = j.p; D.rep = rep.p;
-    D.n = s->n;
-    /* a set larger than one table of at most 2^part_buckets_log2 slots: a table per contiguous part */
-    const uint64_t per_part = (uint64_t)FILL_PERCENT * (1ull << c->part_buckets_log2) / 100;
-    const uint64_t nparts = s->n > per_part ? (s->n + per_part - 1) / per_part : 1;
-    if (nparts > 65536)
-      return fail(c, CMPR_EUNSUPPORTED, "set needs more than 65536 parts (part_buckets_log2)");
-    if (nparts > 1) {
-      std::vector<DevBuf<Slot>> tables((size_t)nparts);
-      struct Tt { std::vector<DevBuf<Slot>> &t; ~Tt() { for (auto &x : t) x.release(); } } ttclean{tables};
-      std::vector<DupTable> tabs((size_t)nparts);
-      std::vector<uint64_t> first((size_t)nparts + 1);
-      const uint64_t q = s->n / nparts, r = s->n % nparts;
-      for (uint64_t p = 0; p <= nparts; p++)
-        first[(size_t)p] = p * q + std::min(p, r);
-      for (uint64_t p = 0; p < nparts; p++) {
-        const uint64_t f = first[(size_t)p], n = first[(size_t)p + 1] - f;
-        uint64_t ps = 1;
-        while (FILL_PERCENT * ps < 100 * n)
-          ps <<= 1;
-        ps = std::max<uint64_t>(ps, 4);
-        if ((rc = dev_alloc(c, tables[(size_t)p], (size_t)ps))) return rc;
-        HIP_TRY(c, hipMemsetAsync(tables[(size_t)p].p, 0xff, ps * sizeof(Slot), c->stream));
-        BuildParams B{};
-        B.zob = zob; B.A = A; B.zpos = zpos; B.n_v = n_v; B.use_genes = D.use_genes;
-        B.res = res.p; B.off = off.p + f; B.v = v.p ? v.p + f : nullptr; B.j = j.p ? j.p + f : nullptr; B.n = n;
-        B.table = tables[(size_t)p].p; B.slot_mask = ps - 1;
-        B.bloom = nullptr; B.bloom_byte_mask = 0; B.sliced = 0;   /* table only */
-        if (n) {
-          hipLaunchKernelGGL(build_index_kernel, dim3((uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS)),
-                             dim3(BLOCK_THREADS), 0, c->stream, B);
-          HIP_TRY(c, hipGetLastError());
-        }
-        tabs[(size_t)p] = DupTable{tables[(size_t)p].p, ps - 1, f, 0u, 0u};
-      }
-      return count_duplicates_in_parts(c, D, tabs, first, out);
-    }
-    uint64_t slots = 1;
-    while (FILL_PERCENT * slots < 100 * s->n)
-      slots <<= 1;
-    slots = std::max<uint64_t>(slots, 4);         /* chains start on 4-slot boundaries */
-    if ((rc = dev_alloc(c, table, (size_t)slots))) return rc;
-    HIP_TRY(c, hipMemsetAsync(table.p, 0xff, slots * sizeof(Slot), c->stream));
-    if (s->n) {
-      BuildParams B{};
-      B.zob = zob; B.A = A; B.zpos = zpos; B.n_v = n_v; B.use_genes = D.use_genes;
-      B.res = res.p; B.off = off.p; B.v = v.p; B.j = j.p; B.n = s->n;
-      B.table = table.p; B.slot_mask = slots - 1;
-      B.bloom = nullptr; B.bloom_byte_mask = 0; B.sliced = 0;   /* table only */
-      const uint32_t grid = (uint32_t)((s->n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-      hipLaunchKernelGGL(build_index_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, B);
-      HIP_TRY(c, hipGetLastError());
-    }
-    D.zob = zob; D.zpos = zpos;
-    D.res = res.p; D.off = off.p; D.v = v.p; D.j = j.p; D.rep = rep.p;
-    D.n = s->n;
-    D.table = table.p; D.slot_mask = slots - 1;
-    if (D.n) {
-      const uint32_t grid = (uint32_t)((D.n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-      hipLaunchKernelGGL(count_duplicates_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, D);
-      HIP_TRY(c, hipGetLastError());
-    }
-    unsigned long long hc = 0;
-    HIP_TRY(c, hipMemcpyAsync(&hc, d_count.p, sizeof hc, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *out = hc;
-    return CMPR_OK;
-  }
-  if (D.n) {
-    const uint32_t grid = (uint32_t)((D.n + BLOCK_THREADS - 1) / BLOCK_THREADS);
-    hipLaunchKernelGGL(count_duplicates_kernel, dim3(grid), dim3(BLOCK_THREADS), 0, c->stream, D);
-    HIP_TRY(c, hipGetLastError());
-  }
-  unsigned long long hc = 0;
-  HIP_TRY(c, hipMemcpyAsync(&hc, d_count.p, sizeof hc, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *out = hc;
-  return CMPR_OK;
-}
-
 /* ------------------------------------------------------------------ */
 /* set 1: sort by length, cut into 64-query tiles, upload               */
 /* ------------------------------------------------------------------ */
@@ -1682,16 +1491,6 @@ extern "C" int cmpr_warm_up_sized(const cmpr_options *o, uint64_t n_queries_hint
   g_warm.dev_bytes = dev_bytes;
   g_warm.device = device;
   return CMPR_OK;
-}
-
-extern "C" int cmpr_count_duplicates(cmpr_context *c, const cmpr_set_view *s, uint64_t *out)
-{
-  /* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-  try {
-    return cmpr_count_duplicates_impl(c, s, out);
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
 }
 
 static int set_queries_guarded(cmpr_context *c, const LayoutSource &src)

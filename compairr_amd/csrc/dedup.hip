@@ -1,6 +1,8 @@
 /*
- * dedup.hip -- cmpr_deduplicate / cmpr_deduplicate_device: the reference's --deduplicate
- * (dedup.cc:27-132, 184-199) for a set in host or in device memory.
+ * dedup.hip -- the exact duplicates of one set.  cmpr_deduplicate / cmpr_deduplicate_device: the reference's
+ * --deduplicate (dedup.cc:27-132, 184-199) for a set in host or in device memory.  cmpr_count_duplicates: the
+ * number alone -- a lookup of every entry in the record tables of the resident reference, or in a table built
+ * for a passed-in set (count_duplicates_kernel, at the end).
  *
  * The reference inserts the sequences one after the other and links every sequence to the last equal one
  * before it (process(), dedup.cc:60-132); report() then prints a chain at its first member with the summed
@@ -14,7 +16,7 @@
  *   dedup_scan_kernel     exclusive scan of those counts (one workgroup)
  *   dedup_scatter_kernel  (first, count) of every class written in increasing `first`
  *
- * Nothing here reads or writes the resident sets, plans or statistics of the context.
+ * Nothing here writes the resident sets, plans or statistics of the context.
  */
 #include "context.h"
 
@@ -32,15 +34,26 @@ constexpr uint32_t DEDUP_SCAN_WG = 1024;
 constexpr unsigned long long DEDUP_EMPTY = ~0ull;         /* (tag << 32) | index is never this: index < 2^32 - 64 */
 constexpr size_t DEDUP_ZOB_LDS_BYTES = 12288;             /* the Zobrist keys go to LDS up to this (query_layout.hip) */
 
-struct DedupParams {
+template <typename T>
+struct Tmp {
+  DevBuf<T> b;
+  ~Tmp() { b.release(); }
+};
+
+/* the entries of a set and the keys they are hashed with */
+struct EntrySet {
   const uint64_t *zob;
   uint32_t        A, zpos, n_v, use_genes;
-  uint32_t        zob_lds, zob_words;      /* the keys (gene keys included) are copied to LDS */
-  uint32_t        tag_drop;                /* 32 - dedup_tag_bits: the tag is the hash's low dword without its low bits */
-  uint32_t        pad;
   const uint8_t  *res;
   const uint64_t *off;
   const uint32_t *v, *j, *rep;
+};
+
+struct DedupParams {
+  EntrySet        S;
+  uint32_t        zob_lds, zob_words;      /* the keys (gene keys included) are copied to LDS */
+  uint32_t        tag_drop;                /* 32 - dedup_tag_bits: the tag is the hash's low dword without its low bits */
+  uint32_t        pad;
   const uint64_t *cnt;                     /* NULL: every sequence counts 1 (ignore_counts) */
   uint64_t        n;
   unsigned long long *table;               /* (tag << 32) | sequence number, DEDUP_EMPTY: free */
@@ -54,23 +67,36 @@ struct DedupParams {
   uint64_t       *count_out;
 };
 
-/* sequence i (residues at b, length L) and sequence o are the same entry (dedup.cc:90-111) */
-__device__ __forceinline__ bool same_entry(const DedupParams &P, uint64_t i, uint64_t o, uint64_t b, uint32_t L)
+/* Zobrist hash of entry i (residues at b, length L; zobrist.cc:74-88) with the keys at zt: S.zob or a copy of it */
+__device__ __forceinline__ uint64_t entry_hash(const EntrySet &S, const uint64_t *zt, uint64_t i, uint64_t b, uint32_t L)
 {
-  if (P.rep[o] != P.rep[i])
+  uint64_t h = 0;
+  if (S.use_genes) {
+    const uint64_t *vk = zt + (uint64_t)S.A * S.zpos;
+    h = vk[S.v[i]] ^ vk[S.n_v + S.j[i]];
+  }
+  for (uint32_t p = 0; p < L; p++)
+    h ^= zt[S.A * p + S.res[b + p]];
+  return h;
+}
+
+/* sequence i (residues at b, length L) and sequence o are the same entry (dedup.cc:90-111) */
+__device__ __forceinline__ bool same_entry(const EntrySet &S, uint64_t i, uint64_t o, uint64_t b, uint32_t L)
+{
+  if (S.rep[o] != S.rep[i])
     return false;
-  if (P.use_genes && (P.v[o] != P.v[i] || P.j[o] != P.j[i]))
+  if (S.use_genes && (S.v[o] != S.v[i] || S.j[o] != S.j[i]))
     return false;
-  const uint64_t ob = P.off[o];
-  if ((uint32_t)(P.off[o + 1] - ob) != L)
+  const uint64_t ob = S.off[o];
+  if ((uint32_t)(S.off[o + 1] - ob) != L)
     return false;
   for (uint32_t p = 0; p < L; p++)
-    if (P.res[ob + p] != P.res[b + p])
+    if (S.res[ob + p] != S.res[b + p])
       return false;
   return true;
 }
 
-/* One thread per sequence: the hash of build_index_kernel (kernels.h; zobrist.cc:74-88), then the walk.
+/* One thread per sequence: its hash, then the walk.
    A slot is claimed once (CAS on the empty word) and never freed, and from then on it belongs to the
    claimer's CLASS: the only later write is an atomicMin by a sequence that has compared itself equal to the
    slot's owner of the moment, so every owner a slot ever has is of one class, and a comparison against any
@@ -85,21 +111,15 @@ dedup_insert_kernel(const DedupParams P)
   extern __shared__ uint64_t dedup_zl[];
   if (P.zob_lds) {
     for (uint32_t k = threadIdx.x; k < P.zob_words; k += DEDUP_WG)
-      dedup_zl[k] = P.zob[k];
+      dedup_zl[k] = P.S.zob[k];
     __syncthreads();
   }
-  const uint64_t *const zt = P.zob_lds ? dedup_zl : P.zob;
+  const uint64_t *const zt = P.zob_lds ? dedup_zl : P.S.zob;
   const uint64_t step = (uint64_t)gridDim.x * DEDUP_WG;
   for (uint64_t i = (uint64_t)blockIdx.x * DEDUP_WG + threadIdx.x; i < P.n; i += step) {
-    const uint64_t b = P.off[i];
-    const uint32_t L = (uint32_t)(P.off[i + 1] - b);
-    uint64_t h = 0;
-    if (P.use_genes) {
-      const uint64_t *vk = zt + (uint64_t)P.A * P.zpos;
-      h = vk[P.v[i]] ^ vk[P.n_v + P.j[i]];
-    }
-    for (uint32_t p = 0; p < L; p++)
-      h ^= zt[P.A * p + P.res[b + p]];
+    const uint64_t b = P.S.off[i];
+    const uint32_t L = (uint32_t)(P.S.off[i + 1] - b);
+    const uint64_t h = entry_hash(P.S, zt, i, b, L);
     /* the slot from the high dword (hashtable.h:36-41), the tag from the low one: independent bits */
     const uint32_t tag = (uint32_t)((h & 0xffffffffull) >> P.tag_drop);
     const unsigned long long mine = ((unsigned long long)tag << 32) | (uint32_t)i;
@@ -112,7 +132,7 @@ dedup_insert_kernel(const DedupParams P)
           break;                           /* claimed: the class's slot, this sequence its first so far */
         /* lost: w is what the winner put here -- the same slot is looked at again */
       }
-      if ((uint32_t)(w >> 32) == tag && same_entry(P, i, w & 0xffffffffull, b, L)) {
+      if ((uint32_t)(w >> 32) == tag && same_entry(P.S, i, w & 0xffffffffull, b, L)) {
         if (mine < w)                      /* (the word only ever gets smaller: nothing to do for a larger number) */
           atomicMin(&P.table[slot], mine);
         break;
@@ -208,6 +228,96 @@ dedup_scatter_kernel(const DedupParams P)
   }
 }
 
+/* Exact duplicates counted, not merged: entry i counts when an entry j < i of the same repertoire has the same
+   sequence (and V/J unless -g) -- what hash_insert reports while indexing (overlap.cc:76-115) and
+   check_duplicates() sums (overlap.cc:579-605).  The reference finds j because it inserts in input order; the
+   tables here are built in parallel, so every entry of the key's chain is inspected and "earlier" is decided
+   by the number.  A set in parts has a table per part: entry i of part p is looked up in the tables of parts
+   0 .. p -- the later parts hold only later entries.  A table is the record table of a resident part (global
+   numbers in RefRec::idx) or the open-addressing table of a passed-in part (local numbers, `base` added). */
+struct DupTable {
+  const void *t;
+  uint64_t    mask;                /* buckets - 1 (record table) / slots - 1 */
+  uint64_t    base;                /* Slot tables: global number of the part's first entry */
+  uint32_t    records;             /* 1: RefRec table, 0: Slot table */
+  uint32_t    pad;
+};
+
+struct DupParams {
+  EntrySet        S;               /* the whole set */
+  uint64_t        first, n;        /* the entries of part p */
+  DupTable        part0;           /* the table of part 0 */
+  const DupTable *more;            /* those of parts 1 .. ntables - 1 */
+  uint32_t        ntables;         /* p + 1 */
+  unsigned long long *count;
+};
+
+__global__ void __launch_bounds__(BLOCK_THREADS)
+count_duplicates_kernel(const DupParams B)
+{
+  const uint64_t t = (uint64_t)blockIdx.x * BLOCK_THREADS + threadIdx.x;
+  bool dup = false;
+  if (t < B.n) {
+    const uint64_t i = B.first + t;
+    const uint64_t b = B.S.off[i];
+    const uint32_t L = (uint32_t)(B.S.off[i + 1] - b);
+    const uint64_t key = table_key(entry_hash(B.S, B.S.zob, i, b, L));
+    for (uint32_t q = 0; q < B.ntables && !dup; q++) {
+      const DupTable T = q ? B.more[q - 1] : B.part0;
+      if (T.records) {
+        const uint32_t bk = dir_bucket(key, (uint32_t)T.mask);
+        /* the records of the key's bucket, one after the other (a slot behind the last bucket is empty) */
+        for (const RefRec *r = (const RefRec *)T.t + bk;; r++) {
+          const uint32_t ri = r->idx, rl = r->len, rh = r->home;
+          if (ri == REC_EMPTY)
+            break;
+          if (rh == bk && (rl >> REC_TAG_SHIFT) == dir_tag(key) && ri < i && same_entry(B.S, i, ri, b, L)) {
+            dup = true;
+            break;
+          }
+          if (walk_ends(ri, rl, rh, bk))
+            break;
+        }
+      } else {
+        for (uint64_t slot = table_home(key, T.mask);; slot = (slot + 1) & T.mask) {
+          const Slot sl = ((const Slot *)T.t)[slot];
+          if (sl.key == EMPTY_KEY)
+            break;
+          if (sl.key == key && T.base + sl.val < i && same_entry(B.S, i, T.base + sl.val, b, L)) {
+            dup = true;
+            break;
+          }
+        }
+      }
+    }
+  }
+  const uint64_t m = __ballot(dup);
+  if (m && lane_id() == 0)
+    atomicAdd(B.count, (unsigned long long)__popcll(m));
+}
+
+/* The Zobrist keys for a set whose longest sequence has `longest` residues: the resident ones when a reference
+   is resident and long enough, else a freshly drawn table in `own`.  (Every user compares the residues in
+   full: no result depends on the keys.) */
+int keys_for_set(cmpr_context *c, uint32_t longest, DevBuf<uint64_t> &own, const uint64_t *&zob, uint32_t &zpos)
+{
+  zob = c->zob.p;
+  zpos = c->zpos;
+  if (c->have_ref && longest + EXTRA_POSITIONS <= c->zpos)
+    return CMPR_OK;
+  zpos = longest + EXTRA_POSITIONS;
+  const uint32_t genes = c->opt.ignore_genes ? 0 : c->opt.n_v_genes + c->opt.n_j_genes;
+  std::vector<uint64_t> z((size_t)c->opt.alphabet_size * zpos + genes);
+  SplitMix64 rng(0x6465647570ull);   /* "dedup" */
+  for (auto &x : z)
+    x = rng.next();
+  int rc;
+  if ((rc = dev_upload(c, own, z.data(), z.size()))) return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));            /* (z leaves scope) */
+  zob = own.p;
+  return CMPR_OK;
+}
+
 int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint64_t capacity,
                      uint32_t *first_out, uint64_t *count_out, uint64_t *n_unique_out, uint64_t *merged_out)
 {
@@ -223,23 +333,10 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   if (n_unique_out) *n_unique_out = 0;
   if (merged_out) *merged_out = 0;
 
-  DevBuf<uint8_t> res;
-  DevBuf<uint64_t> off, cnt, zob_own, d_count;
-  DevBuf<uint32_t> v, j, rep, slot, blk, d_first;
-  DevBuf<unsigned long long> table, sum, total;
-  struct Cleanup {
-    DevBuf<uint8_t> &a;
-    DevBuf<uint64_t> &b1, &b2, &b3, &b4;
-    DevBuf<uint32_t> &c1, &c2, &c3, &c4, &c5, &c6;
-    DevBuf<unsigned long long> &d1, &d2, &d3;
-    ~Cleanup()
-    {
-      a.release();
-      b1.release(); b2.release(); b3.release(); b4.release();
-      c1.release(); c2.release(); c3.release(); c4.release(); c5.release(); c6.release();
-      d1.release(); d2.release(); d3.release();
-    }
-  } cleanup{res, off, cnt, zob_own, d_count, v, j, rep, slot, blk, d_first, table, sum, total};
+  Tmp<uint8_t> res;
+  Tmp<uint64_t> off, cnt, zob_own, d_count;
+  Tmp<uint32_t> v, j, rep, slot, blk, d_first;
+  Tmp<unsigned long long> table, sum, total;
 
   /* residues in all: offsets[n], which a device view keeps on the device (ref_index.hip) */
   uint64_t residues = 0;
@@ -256,28 +353,18 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   /* upload (a device view: a copy inside the device) + validation on the device (query_layout.hip) */
   uint32_t longest = 0;
   std::vector<double> tot;
-  if ((rc = cmpr_upload_and_validate(c, s, res, off, v, j, rep, cnt, longest, tot, on_device, residues)))
+  if ((rc = cmpr_upload_and_validate(c, s, res.b, off.b, v.b, j.b, rep.b, cnt.b, longest, tot, on_device, residues)))
     return rc;
   const uint64_t n = s->n;
   if (n == 0)
     return CMPR_OK;
 
-  /* own Zobrist keys when no reference set is resident or it is too short (cmpr_count_duplicates) */
-  const uint32_t A = (uint32_t)c->opt.alphabet_size;
-  const uint32_t n_v = c->opt.ignore_genes ? 0 : c->opt.n_v_genes;
-  const uint32_t n_j = c->opt.ignore_genes ? 0 : c->opt.n_j_genes;
-  uint32_t zpos = c->zpos;
-  const uint64_t *zob = c->zob.p;
-  if (!c->have_ref || longest + EXTRA_POSITIONS > c->zpos) {
-    zpos = longest + EXTRA_POSITIONS;
-    std::vector<uint64_t> z((size_t)A * zpos + n_v + n_j);
-    SplitMix64 rng(0x6465647570ull);   /* "dedup" */
-    for (auto &x : z)
-      x = rng.next();
-    if ((rc = dev_upload(c, zob_own, z.data(), z.size()))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));            /* (z leaves scope) */
-    zob = zob_own.p;
-  }
+  DedupParams P{};
+  P.S.A = (uint32_t)c->opt.alphabet_size;
+  P.S.n_v = c->opt.ignore_genes ? 0 : c->opt.n_v_genes;
+  P.S.use_genes = c->opt.ignore_genes ? 0u : 1u;
+  if ((rc = keys_for_set(c, longest, zob_own.b, P.S.zob, P.S.zpos))) return rc;
+  P.S.res = res.b.p; P.S.off = off.b.p; P.S.v = v.b.p; P.S.j = j.b.p; P.S.rep = rep.b.p;
 
   /* one table under the 70 % rule of hashtable.cc:24; slot numbers are 32 bits, so beyond 0.7 x 2^32
      sequences it is fuller than that (never full: there are fewer classes than 2^32 - 64) */
@@ -285,24 +372,21 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   while (FILL_PERCENT * slots < 100 * n && slots < (1ull << 32))
     slots <<= 1;
   const uint64_t nblk = (n + DEDUP_WG - 1) / DEDUP_WG;
-  if ((rc = dev_alloc(c, table, (size_t)slots))) return rc;
-  if ((rc = dev_alloc(c, slot, (size_t)n))) return rc;
-  if ((rc = dev_alloc(c, sum, (size_t)n))) return rc;
-  if ((rc = dev_alloc(c, blk, (size_t)nblk))) return rc;
-  if ((rc = dev_alloc(c, total, 1))) return rc;
-  HIP_TRY(c, hipMemsetAsync(table.p, 0xff, slots * sizeof(unsigned long long), c->stream));
-  HIP_TRY(c, hipMemsetAsync(sum.p, 0, n * sizeof(unsigned long long), c->stream));
+  if ((rc = dev_alloc(c, table.b, (size_t)slots))) return rc;
+  if ((rc = dev_alloc(c, slot.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, sum.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, blk.b, (size_t)nblk))) return rc;
+  if ((rc = dev_alloc(c, total.b, 1))) return rc;
+  HIP_TRY(c, hipMemsetAsync(table.b.p, 0xff, slots * sizeof(unsigned long long), c->stream));
+  HIP_TRY(c, hipMemsetAsync(sum.b.p, 0, n * sizeof(unsigned long long), c->stream));
 
-  DedupParams P{};
-  P.zob = zob; P.A = A; P.zpos = zpos; P.n_v = n_v; P.use_genes = c->opt.ignore_genes ? 0u : 1u;
-  P.zob_words = (uint32_t)((size_t)A * zpos + n_v + n_j);
+  P.zob_words = (uint32_t)((size_t)P.S.A * P.S.zpos + P.S.n_v + (c->opt.ignore_genes ? 0 : c->opt.n_j_genes));
   P.zob_lds = (size_t)P.zob_words * sizeof(uint64_t) <= DEDUP_ZOB_LDS_BYTES ? 1u : 0u;
   P.tag_drop = 32u - (uint32_t)c->dedup_tag_bits;
-  P.res = res.p; P.off = off.p; P.v = v.p; P.j = j.p; P.rep = rep.p;
-  P.cnt = c->opt.ignore_counts ? nullptr : cnt.p;
+  P.cnt = c->opt.ignore_counts ? nullptr : cnt.b.p;
   P.n = n;
-  P.table = table.p; P.slot_mask = slots - 1;
-  P.slot = slot.p; P.sum = sum.p; P.blk = blk.p; P.total = total.p;
+  P.table = table.b.p; P.slot_mask = slots - 1;
+  P.slot = slot.b.p; P.sum = sum.b.p; P.blk = blk.b.p; P.total = total.b.p;
 
   const size_t lds = P.zob_lds ? (size_t)P.zob_words * sizeof(uint64_t) : 0;
   /* (the keys are copied once per workgroup: as many workgroups as are resident, each over many sequences) */
@@ -311,10 +395,10 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   HIP_TRY(c, hipGetLastError());
   hipLaunchKernelGGL(dedup_sum_kernel, dim3((uint32_t)nblk), dim3(DEDUP_WG), 0, c->stream, P);
   HIP_TRY(c, hipGetLastError());
-  hipLaunchKernelGGL(dedup_scan_kernel, dim3(1), dim3(DEDUP_SCAN_WG), 0, c->stream, blk.p, nblk, total.p);
+  hipLaunchKernelGGL(dedup_scan_kernel, dim3(1), dim3(DEDUP_SCAN_WG), 0, c->stream, blk.b.p, nblk, total.b.p);
   HIP_TRY(c, hipGetLastError());
   unsigned long long classes = 0;
-  HIP_TRY(c, hipMemcpyAsync(&classes, total.p, sizeof classes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&classes, total.b.p, sizeof classes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
 
   const uint64_t written = std::min<uint64_t>(capacity, classes);
@@ -324,16 +408,16 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
       P.first_out = first_out;
       P.count_out = count_out;
     } else {
-      if ((rc = dev_alloc(c, d_first, (size_t)written))) return rc;
-      if ((rc = dev_alloc(c, d_count, (size_t)written))) return rc;
-      P.first_out = d_first.p;
-      P.count_out = d_count.p;
+      if ((rc = dev_alloc(c, d_first.b, (size_t)written))) return rc;
+      if ((rc = dev_alloc(c, d_count.b, (size_t)written))) return rc;
+      P.first_out = d_first.b.p;
+      P.count_out = d_count.b.p;
     }
     hipLaunchKernelGGL(dedup_scatter_kernel, dim3((uint32_t)nblk), dim3(DEDUP_WG), 0, c->stream, P);
     HIP_TRY(c, hipGetLastError());
     if (!on_device) {
-      HIP_TRY(c, hipMemcpyAsync(first_out, d_first.p, written * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, written * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(first_out, d_first.b.p, written * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(count_out, d_count.b.p, written * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
@@ -342,12 +426,110 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   return CMPR_OK;
 }
 
-int deduplicate_guarded(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint64_t capacity,
-                        uint32_t *first_out, uint64_t *count_out, uint64_t *n_unique_out, uint64_t *merged_out)
+int count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, uint64_t *out)
 {
-  /* the header promises CMPR_ENOMEM, not an exception across the C boundary */
+  if (!c || !out)
+    return CMPR_EINVAL;
+  HIP_TRY(c, hipSetDevice(c->device));
+  *out = 0;
+  int rc;
+  Tmp<uint8_t> res;
+  Tmp<uint64_t> off, cnt, zob_own;
+  Tmp<uint32_t> v, j, rep;
+  Tmp<unsigned long long> count;
+  Tmp<DupTable> more;
+  std::vector<Tmp<Slot>> slots;                /* a passed-in set: the table of each part */
+
+  DupParams B{};
+  B.S.A = (uint32_t)c->opt.alphabet_size;
+  B.S.n_v = c->opt.ignore_genes ? 0 : c->opt.n_v_genes;
+  B.S.use_genes = c->opt.ignore_genes ? 0u : 1u;
+  std::vector<DupTable> tabs;                  /* parts 0 .. */
+  std::vector<uint64_t> first;                 /* their first entries, and the set's size */
+  if (!s) {
+    if (!c->have_ref)
+      return fail(c, CMPR_ESTATE, "cmpr_set_reference must be called first");
+    B.S.zob = c->zob.p; B.S.zpos = c->zpos;
+    B.S.res = c->res2.p; B.S.off = c->off2.p; B.S.v = c->v2.p; B.S.j = c->j2.p; B.S.rep = c->rep2.p;
+    tabs.push_back(DupTable{c->rec2.p, c->slots - 1, 0, 1u, 0u});
+    first.push_back(0);
+    for (const RefPart &rp : c->xparts) {
+      tabs.push_back(DupTable{rp.rec.p, rp.slots - 1, 0, 1u, 0u});
+      first.push_back(rp.first);
+    }
+    first.push_back(c->n2);
+  } else {
+    std::string why;
+    if ((rc = validate_view(c->opt, s, why)))
+      return fail(c, rc, why);
+    /* upload + validation on the device (query_layout.hip) */
+    uint32_t longest = 0;
+    std::vector<double> tot;
+    if ((rc = cmpr_upload_and_validate(c, s, res.b, off.b, v.b, j.b, rep.b, cnt.b, longest, tot)))
+      return rc;
+    if ((rc = keys_for_set(c, longest, zob_own.b, B.S.zob, B.S.zpos))) return rc;
+    B.S.res = res.b.p; B.S.off = off.b.p; B.S.v = v.b.p; B.S.j = j.b.p; B.S.rep = rep.b.p;
+    /* a set larger than one table of at most 2^part_buckets_log2 slots: a table per contiguous part */
+    const uint64_t per_part = (uint64_t)FILL_PERCENT * (1ull << c->part_buckets_log2) / 100;
+    const uint64_t nparts = s->n > per_part ? (s->n + per_part - 1) / per_part : 1;
+    if (nparts > 65536)
+      return fail(c, CMPR_EUNSUPPORTED, "set needs more than 65536 parts (part_buckets_log2)");
+    slots.resize((size_t)nparts);
+    const uint64_t q = s->n / nparts, r = s->n % nparts;
+    for (uint64_t p = 0; p <= nparts; p++)
+      first.push_back(p * q + std::min(p, r));
+    for (uint64_t p = 0; p < nparts; p++) {
+      const uint64_t f = first[(size_t)p], n = first[(size_t)p + 1] - f;
+      uint64_t ps = 4;                         /* chains start on 4-slot boundaries */
+      while (FILL_PERCENT * ps < 100 * n)
+        ps <<= 1;
+      Slot *&table = slots[(size_t)p].b.p;
+      if ((rc = dev_alloc(c, slots[(size_t)p].b, (size_t)ps))) return rc;
+      HIP_TRY(c, hipMemsetAsync(table, 0xff, ps * sizeof(Slot), c->stream));
+      BuildParams K{};
+      K.zob = B.S.zob; K.A = B.S.A; K.zpos = B.S.zpos; K.n_v = B.S.n_v; K.use_genes = B.S.use_genes;
+      K.res = res.b.p; K.off = off.b.p + f; K.v = v.b.p ? v.b.p + f : nullptr; K.j = j.b.p ? j.b.p + f : nullptr;
+      K.n = n;
+      K.table = table; K.slot_mask = ps - 1;       /* table only: no filter */
+      if (n) {
+        hipLaunchKernelGGL(build_index_kernel, dim3((uint32_t)((n + BLOCK_THREADS - 1) / BLOCK_THREADS)),
+                           dim3(BLOCK_THREADS), 0, c->stream, K);
+        HIP_TRY(c, hipGetLastError());
+      }
+      tabs.push_back(DupTable{table, ps - 1, f, 0u, 0u});
+    }
+  }
+
+  /* one tail: part p's entries against the tables of parts 0 .. p, the counter copied back */
+  if ((rc = dev_alloc(c, count.b, 1))) return rc;
+  HIP_TRY(c, hipMemsetAsync(count.b.p, 0, sizeof(unsigned long long), c->stream));
+  if (tabs.size() > 1 && (rc = dev_upload(c, more.b, tabs.data() + 1, tabs.size() - 1))) return rc;
+  B.part0 = tabs[0];
+  B.more = more.b.p;
+  B.count = count.b.p;
+  for (size_t p = 0; p < tabs.size(); p++) {
+    B.first = first[p];
+    B.n = first[p + 1] - first[p];
+    B.ntables = (uint32_t)p + 1;
+    if (B.n) {
+      hipLaunchKernelGGL(count_duplicates_kernel, dim3((uint32_t)((B.n + BLOCK_THREADS - 1) / BLOCK_THREADS)),
+                         dim3(BLOCK_THREADS), 0, c->stream, B);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  unsigned long long hc = 0;
+  HIP_TRY(c, hipMemcpyAsync(&hc, count.b.p, sizeof hc, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *out = hc;
+  return CMPR_OK;
+}
+
+/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
+template <typename F>
+int guarded(cmpr_context *c, F call)
+{
   try {
-    return deduplicate_impl(c, s, on_device, capacity, first_out, count_out, n_unique_out, merged_out);
+    return call();
   } catch (const std::bad_alloc &) {
     return fail(c, CMPR_ENOMEM, "out of host memory");
   }
@@ -355,16 +537,21 @@ int deduplicate_guarded(cmpr_context *c, const cmpr_set_view *s, bool on_device,
 
 }  // namespace
 
+extern "C" int cmpr_count_duplicates(cmpr_context *c, const cmpr_set_view *s, uint64_t *out)
+{
+  return guarded(c, [&] { return count_duplicates_impl(c, s, out); });
+}
+
 extern "C" int cmpr_deduplicate(cmpr_context *c, const cmpr_set_view *set, uint64_t capacity,
                                 uint32_t *first_out, uint64_t *count_out,
                                 uint64_t *n_unique_out, uint64_t *merged_out)
 {
-  return deduplicate_guarded(c, set, false, capacity, first_out, count_out, n_unique_out, merged_out);
+  return guarded(c, [&] { return deduplicate_impl(c, set, false, capacity, first_out, count_out, n_unique_out, merged_out); });
 }
 
 extern "C" int cmpr_deduplicate_device(cmpr_context *c, const cmpr_set_view *d_set, uint64_t capacity,
                                        uint32_t *d_first_out, uint64_t *d_count_out,
                                        uint64_t *n_unique_out, uint64_t *merged_out)
 {
-  return deduplicate_guarded(c, d_set, true, capacity, d_first_out, d_count_out, n_unique_out, merged_out);
+  return guarded(c, [&] { return deduplicate_impl(c, d_set, true, capacity, d_first_out, d_count_out, n_unique_out, merged_out); });
 }

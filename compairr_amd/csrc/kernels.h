@@ -203,7 +203,7 @@ build_index_kernel(const BuildParams B)
   }
 
   if (!B.bloom)
-    return;                            /* table only: duplicate counting, row filter */
+    return;                            /* table only: duplicate counting (dedup.hip) */
   uint64_t boff = bloom_off(h) & B.bloom_byte_mask;
   if (B.sliced) {
     const uint32_t slice = class_key_of(B.geom.ctab, B.geom, B.A, B.use_genes != 0,
@@ -215,179 +215,6 @@ build_index_kernel(const BuildParams B)
   const uint64_t pat = pattern_of(h);
   atomicAnd((unsigned long long *)((char *)B.bloom + boff),
             (unsigned long long)~pat);
-}
-
-/* Exact duplicates inside one set: entry i counts when an entry j < i of the
-   same repertoire has the same sequence (and V/J unless -g) -- what hash_insert
-   reports while indexing (overlap.cc:76-115) and check_duplicates() sums
-   (overlap.cc:579-605).  The reference finds j because it inserts in input
-   order; here the table is built in parallel, so every same-key entry of the
-   probe chain is inspected and "earlier" is decided by the index. */
-struct DupParams {
-  const uint64_t *zob;
-  uint32_t        A, zpos, n_v, use_genes;
-  const uint8_t  *res;
-  const uint64_t *off;
-  const uint32_t *v, *j, *rep;
-  uint64_t        n;
-  const Slot     *table;           /* a set of its own: open-addressing table of sequence numbers */
-  uint64_t        slot_mask;
-  const unsigned char *rec;        /* the resident reference: its record table */
-  uint32_t        dir_mask;
-  unsigned long long *count;
-};
-
-static __global__ void __launch_bounds__(BLOCK_THREADS)
-count_duplicates_kernel(const DupParams B)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * BLOCK_THREADS + threadIdx.x;
-  bool dup = false;
-  if (i < B.n) {
-    const uint64_t b = B.off[i];
-    const uint32_t L = (uint32_t)(B.off[i + 1] - b);
-    uint64_t h = 0;
-    if (B.use_genes) {
-      const uint64_t *vk = B.zob + (uint64_t)B.A * B.zpos;
-      h = vk[B.v[i]] ^ vk[B.n_v + B.j[i]];
-    }
-    for (uint32_t p = 0; p < L; p++)
-      h ^= B.zob[B.A * p + B.res[b + p]];
-    const uint64_t key = table_key(h);
-    uint64_t slot = table_home(key, B.slot_mask);
-    /* the resident reference: the records of the key's bucket, one after the other */
-    const uint32_t bk = dir_bucket(key, B.dir_mask);
-    uint32_t piece = bk;
-    bool ended = false;
-    for (;;) {
-      uint64_t k, o;
-      if (B.rec) {
-        if (ended)
-          break;
-        const RefRec *r = (const RefRec *)B.rec + piece;
-        const uint32_t ri = r->idx, rl = r->len, rh = r->home;
-        ended = walk_ends(ri, rl, rh, bk);
-        if (ri == REC_EMPTY)
-          break;
-        k = (rh == bk && (rl >> REC_TAG_SHIFT) == dir_tag(key)) ? key : ~key;
-        o = ri;
-        piece++;
-      } else {
-        const Slot sl = B.table[slot];
-        k = sl.key;
-        o = sl.val;
-        if (k == EMPTY_KEY)
-          break;
-        slot = (slot + 1) & B.slot_mask;
-      }
-      if (k == key) {
-        if (o < i && B.rep[o] == B.rep[i] &&
-            (!B.use_genes || (B.v[o] == B.v[i] && B.j[o] == B.j[i]))) {
-          const uint64_t ob = B.off[o];
-          if ((uint32_t)(B.off[o + 1] - ob) == L) {
-            bool same = true;
-            for (uint32_t p = 0; p < L && same; p++)
-              same = B.res[ob + p] == B.res[b + p];
-            if (same) {
-              dup = true;
-              break;
-            }
-          }
-        }
-      }
-    }
-  }
-  const uint64_t m = __ballot(dup);
-  if (m && lane_id() == 0)
-    atomicAdd(B.count, (unsigned long long)__popcll(m));
-}
-
-/* The same count over a set in parts (compairr_hip.hip): entry i of part p counts when an entry j < i of the
-   same repertoire has the same sequence (and V/J unless -g) in one of the tables of parts 0 .. p -- the
-   later parts hold only later entries.  A table is the record table of a resident part (global numbers in
-   RefRec::idx) or the open-addressing table of a passed-in part (local numbers, `base` added). */
-struct DupTable {
-  const void *t;
-  uint64_t    mask;                /* buckets - 1 (record table) / slots - 1 */
-  uint64_t    base;                /* Slot tables: global number of the part's first entry */
-  uint32_t    records;             /* 1: RefRec table, 0: Slot table */
-  uint32_t    pad;
-};
-
-struct DupPartsParams {
-  const uint64_t *zob;
-  uint32_t        A, zpos, n_v, use_genes;
-  const uint8_t  *res;
-  const uint64_t *off;             /* global arrays of the whole set */
-  const uint32_t *v, *j, *rep;
-  uint64_t        first, n;        /* the entries of part p */
-  const DupTable *tables;          /* parts 0 .. ntables - 1 (= p) */
-  uint32_t        ntables;
-  unsigned long long *count;
-};
-
-static __global__ void __launch_bounds__(BLOCK_THREADS)
-count_duplicates_parts_kernel(const DupPartsParams B)
-{
-  const uint64_t t = (uint64_t)blockIdx.x * BLOCK_THREADS + threadIdx.x;
-  bool dup = false;
-  if (t < B.n) {
-    const uint64_t i = B.first + t;
-    const uint64_t b = B.off[i];
-    const uint32_t L = (uint32_t)(B.off[i + 1] - b);
-    uint64_t h = 0;
-    if (B.use_genes) {
-      const uint64_t *vk = B.zob + (uint64_t)B.A * B.zpos;
-      h = vk[B.v[i]] ^ vk[B.n_v + B.j[i]];
-    }
-    for (uint32_t p = 0; p < L; p++)
-      h ^= B.zob[B.A * p + B.res[b + p]];
-    const uint64_t key = table_key(h);
-    for (uint32_t q = 0; q < B.ntables && !dup; q++) {
-      const DupTable T = B.tables[q];
-      const uint32_t bk = dir_bucket(key, (uint32_t)T.mask);
-      uint64_t slot = table_home(key, T.mask);
-      uint32_t piece = bk;
-      bool ended = false;
-      for (;;) {
-        uint64_t k, o;
-        if (T.records) {
-          if (ended)
-            break;
-          const RefRec *r = (const RefRec *)T.t + piece;
-          const uint32_t ri = r->idx, rl = r->len, rh = r->home;
-          ended = walk_ends(ri, rl, rh, bk);
-          if (ri == REC_EMPTY)
-            break;
-          k = (rh == bk && (rl >> REC_TAG_SHIFT) == dir_tag(key)) ? key : ~key;
-          o = ri;
-          piece++;
-        } else {
-          const Slot sl = ((const Slot *)T.t)[slot];
-          k = sl.key;
-          o = T.base + sl.val;
-          if (k == EMPTY_KEY)
-            break;
-          slot = (slot + 1) & T.mask;
-        }
-        if (k == key && o < i && B.rep[o] == B.rep[i] &&
-            (!B.use_genes || (B.v[o] == B.v[i] && B.j[o] == B.j[i]))) {
-          const uint64_t ob = B.off[o];
-          if ((uint32_t)(B.off[o + 1] - ob) == L) {
-            bool same = true;
-            for (uint32_t p = 0; p < L && same; p++)
-              same = B.res[ob + p] == B.res[b + p];
-            if (same) {
-              dup = true;
-              break;
-            }
-          }
-        }
-      }
-    }
-  }
-  const uint64_t m = __ballot(dup);
-  if (m && lane_id() == 0)
-    atomicAdd(B.count, (unsigned long long)__popcll(m));
 }
 
 /* SoA -> header + residues per set-2 sequence (layout.h RefRec) */

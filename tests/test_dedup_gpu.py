@@ -211,6 +211,10 @@ def test_empty_set_is_ok_with_zero_classes():
         first, count, merged = h.deduplicate(s)
         assert (len(first), len(count), merged) == (0, 0, 0)
         assert raw_deduplicate(h, s, 0, None, None) == (0, 0, 0)
+        # the count alone: with nothing resident, and beside a resident reference
+        assert h.count_duplicates(s) == 0
+        h.set_reference(small_set(), small_set().longest)
+        assert h.count_duplicates(s) == 0
 
 
 def test_zero_count_fails_with_the_existing_message():

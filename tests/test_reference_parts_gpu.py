@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import _dedup
 import _oracle
 from compairr_amd import HipOverlap, Options, synth
 from compairr_amd import hip as hipmod
@@ -167,14 +168,22 @@ def test_count_duplicates_across_parts():
                 assert h.get_tunable("reference_parts") > 1
                 assert h.count_duplicates() == ost.dup_set2
                 assert h.count_duplicates(a) == ost.dup_set1
+    # buckets with long runs of equal records; the resident path (in one part and in many) and the passed-in
+    # path (a table of its own, in parts too) agree with each other, with the oracle and with the dedup model
     t = synth.tiny_set(500, 3, letters=2, max_len=4)
-    o = Options(differences=0, n_v_genes=2, n_j_genes=2)
-    _, ost = _oracle.overlap(t, t, o)
-    with HipOverlap(o) as h:
-        h.set_tunable("part_buckets_log2", 4)
-        h.set_reference(t, 0)
-        assert h.count_duplicates() == ost.dup_set2 > 100
-        assert h.count_duplicates(t) == ost.dup_set2
+    for genes in (True, False):
+        o = Options(differences=0, ignore_genes=not genes, n_v_genes=2, n_j_genes=2)
+        _, ost = _oracle.overlap(t, t, o)
+        want = _dedup.model(t, o)[2]
+        assert want == ost.dup_set2 > 100
+        for log2 in (None, 4):
+            with HipOverlap(o) as h:
+                if log2:
+                    h.set_tunable("part_buckets_log2", log2)
+                h.set_reference(t, 0)
+                assert (h.get_tunable("reference_parts") > 1) == bool(log2)
+                assert h.count_duplicates() == want
+                assert h.count_duplicates(t) == want
 
 
 @pytest.mark.parametrize("name,opt,nt", [("aa_d1", dict(differences=1), False),

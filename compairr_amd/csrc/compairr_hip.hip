@@ -934,6 +934,7 @@ int issue_step(cmpr_context *c, const StepArgs &a, hipStream_t st, hipEvent_t ev
     P.pair_h = c->pair_h;
     P.pair_count = c->pair_count;
     P.pair_cap = c->pair_cap;
+    P.link_parent = c->link_parent;
     if (S.deferred)
       P.pos_ctr = c->ctr_cur;
     if (c->rows && S.deferred)
@@ -1259,6 +1260,25 @@ extern "C" int cmpr_overlap_pairs(cmpr_context *c, uint64_t capacity, uint32_t *
   }
   *count_out = n;
   return CMPR_OK;
+}
+
+int cmpr_link_step(cmpr_context *c, uint32_t *parent)
+{
+  int rc = check_ready(c);
+  if (rc)
+    return rc;
+  /* The matches take the pairs-mode branch of score_match and are linked there instead of listed: the
+     counter is never touched (its address only has to be non-NULL), nothing is copied out.  A repeated
+     attempt and the redo pass add links that are already implied: the forest is not reset. */
+  struct Cleanup {
+    cmpr_context *c;
+    ~Cleanup() { c->pair_count = nullptr; c->link_parent = nullptr; }
+  } cleanup{c};
+  c->pair_q = c->pair_h = nullptr;
+  c->pair_cap = 0;
+  c->pair_count = (unsigned long long *)parent;
+  c->link_parent = parent;
+  return run_step_and_wait(c, c->matrix.p, no_hook, no_hook);
 }
 
 extern "C" int cmpr_get_kernel_times(cmpr_context *c, uint32_t max, double *kernel_ms,

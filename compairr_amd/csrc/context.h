@@ -335,6 +335,9 @@ struct cmpr_context {
   uint32_t           *pair_q = nullptr, *pair_h = nullptr;
   unsigned long long *pair_count = nullptr;
   uint64_t            pair_cap = 0;
+  /* link mode, set only while cmpr_cluster runs its step (cluster.hip): the union-find forest the matches
+     are linked in, in place of being listed */
+  uint32_t           *link_parent = nullptr;
 };
 
 
@@ -476,6 +479,11 @@ int cmpr_upload_and_validate(cmpr_context *c, const cmpr_set_view *s, DevBuf<uin
                              DevBuf<uint64_t> &off, DevBuf<uint32_t> &v, DevBuf<uint32_t> &j,
                              DevBuf<uint32_t> &rep, DevBuf<uint64_t> &cnt, uint32_t &longest,
                              std::vector<double> &rep_total, bool on_device = false, uint64_t total_dev = 0);
+
+/* compairr_hip.hip: the synchronous step in link mode (cmpr_cluster, cluster.hip) -- every matching pair of the
+   resident sets united in `parent` (one word per sequence, parent[i] == i or a forest that earlier steps
+   left); the same run_step_and_wait loop as the other synchronous entry points */
+int cmpr_link_step(cmpr_context *c, uint32_t *parent);
 
 /* ref_index.hip: cmpr_set_reference (on_device: the view holds device pointers) */
 int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longest_query, bool on_device);

@@ -423,6 +423,9 @@ struct ProbeParams {
   uint32_t           *pair_q, *pair_h;
   unsigned long long *pair_count;   /* NULL: matrix mode                        */
   uint64_t            pair_cap;
+  /* link mode (cmpr_cluster): rides on pairs mode -- pair_count is then set but never touched --; matches
+     are neither listed nor counted, their two sequences are united in this forest (kernels.h link_pair) */
+  uint32_t           *link_parent;  /* NULL everywhere but in cmpr_cluster        */
   /* sliced mode */
   SliceGeom       geom;
   const Chunk    *chunks;

@@ -28,6 +28,7 @@ EXPORTS = [
     "cmpr_route_queries", "cmpr_route_pack", "cmpr_set_queries_routed",
     "cmpr_warm_up", "cmpr_warm_up_sized",
     "cmpr_deduplicate", "cmpr_deduplicate_device",
+    "cmpr_cluster", "cmpr_cluster_device",
 ]
 
 
@@ -147,6 +148,8 @@ def load_library() -> C.CDLL:
     lib.cmpr_deduplicate.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     lib.cmpr_deduplicate_device.argtypes = lib.cmpr_deduplicate.argtypes
+    lib.cmpr_cluster.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.cmpr_cluster_device.argtypes = lib.cmpr_cluster.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -348,6 +351,28 @@ class HipOverlap:
             C.byref(unique), C.byref(merged)))
         return unique.value, merged.value
 
+    # ---- the single-linkage clusters of a set (include/compairr_hip.h: cmpr_cluster*) ----
+
+    def cluster(self, s: RepertoireSet):
+        """(label uint32[n], size uint32[n], n_clusters): per sequence of `s` the smallest sequence number of
+        its cluster and the number of members of that cluster -- the reference's --cluster (cluster.cc) without
+        its output order.  Afterwards `s` is resident as both sets."""
+        v = _view(s)
+        label = np.zeros(s.n, dtype=np.uint32)
+        size = np.zeros(s.n, dtype=np.uint32)
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_cluster(self._ctx, C.byref(v), label.ctypes.data, size.ctypes.data,
+                                           C.byref(clusters)))
+        return label, size, clusters.value
+
+    def cluster_device(self, view: _SetView, d_label: int = 0, d_size: int = 0) -> int:
+        """The same for a view of device pointers (device_view): labels and sizes are written to the device
+        arrays d_label and d_size (uint32[n] each; 0: not wanted); returns n_clusters."""
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_cluster_device(self._ctx, C.byref(view), C.c_void_p(d_label or None),
+                                                  C.c_void_p(d_size or None), C.byref(clusters)))
+        return clusters.value
+
     def kernel_times(self, max_calls: int = 64):
         """(kernel_ms[], probe_ms[]) of the last calls, oldest first (HIP events)."""
         n = min(max_calls, 63)
@@ -386,3 +411,12 @@ def deduplicate(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None)
     out = s.subset(first)
     out.count = count
     return out, merged
+
+
+def cluster(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
+    """Convenience: (label, size, n_clusters) of `s` under `opt` (HipOverlap.cluster) on a context of its
+    own.  `tunables` are set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        return h.cluster(s)

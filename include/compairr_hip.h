@@ -31,8 +31,8 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*) break no caller
-   and leave it as it is. */
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*) break
+   no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
 enum {
@@ -334,6 +334,46 @@ int cmpr_deduplicate(cmpr_context *ctx, const cmpr_set_view *set, uint64_t capac
 int cmpr_deduplicate_device(cmpr_context *ctx, const cmpr_set_view *d_set, uint64_t capacity,
                             uint32_t *d_first_out, uint64_t *d_count_out,
                             uint64_t *n_unique_out, uint64_t *merged_out);
+
+/*
+ * The single-linkage clusters of one set: the reference's --cluster (cluster.cc:200-410) without its output
+ * order.  Two sequences of `set` are linked when the per-query loop of the set against itself would report
+ * them as a pair under the context's options: within `differences` (0..2; with `indels` at d = 1) and with the
+ * same V and J gene numbers unless ignore_genes.  The repertoire numbers and the counts play no part.  A
+ * cluster is a connected component of that graph (what the breadth-first sweep of cluster.cc:276-410 reaches
+ * from a seed):
+ *   label_out[i]     the smallest sequence number in the cluster of i -- the seed the reference's sweep, which
+ *                    takes the seeds in increasing order, prints the cluster at;
+ *   size_out[i]      the number of members of that cluster: the reference's cluster_size column;
+ *   *n_clusters_out  the number of i with label_out[i] == i: the reference's "Clusters:" figure.
+ * (The reference numbers its clusters by size descending, then by that smallest number ascending: a sort of
+ * the i with label_out[i] == i by (-size_out[i], i).)  Any of the three may be NULL; n_clusters_out is a
+ * HOST pointer in both variants.  n == 0 is CMPR_OK with zero clusters.  Results are identical from run to
+ * run and do not depend on any tunable (the smallest number of a component does not depend on the schedule).
+ *
+ * The call (1) indexes `set` as the reference, as cmpr_set_reference[_device](set, 0) does, (2) lays it out
+ * as the queries, as cmpr_set_queries[_device](set) does -- the same validation, codes, messages and size
+ * limits; a refusal of either passes through unchanged --, (3) runs one synchronous step in which every
+ * verified pair, instead of being scored or listed, unites its two sequences in a union-find forest on the
+ * device (no pair list exists, on the device or on the host), and (4) flattens the forest into the labels and
+ * counts the sizes.  AFTERWARDS `set` IS RESIDENT AS BOTH SETS: cmpr_overlap_* may follow directly and give
+ * what a fresh context gives that was handed the same set twice.  Whatever was resident before is replaced.
+ *
+ * `set` is required (NULL: CMPR_EINVAL); options.existence is CMPR_EINVAL; with the tunable work_shard_count
+ * above 1 the call is CMPR_EUNSUPPORTED (the components of shares do not add up by a sum).  May be called
+ * wherever cmpr_set_reference() may be called, also repeatedly on one context.  cmpr_cluster_device() takes
+ * a DEVICE view as cmpr_set_queries_device() does and writes d_label_out / d_size_out -- device memory of n
+ * uint32 each on the context's device -- where they lie: only the sizes the layout needs anyway and the
+ * cluster count cross PCIe.
+ *
+ * Footprint beyond the two resident sets, for the duration of the call: 4 bytes per sequence for the forest,
+ * which afterwards holds the sizes unless they go to the caller's device array, and 4 for the labels unless
+ * they go to the caller's device array.  Every temporary is freed before the call returns, also when it fails.
+ */
+int cmpr_cluster(cmpr_context *ctx, const cmpr_set_view *set,
+                 uint32_t *label_out, uint32_t *size_out, uint64_t *n_clusters_out);
+int cmpr_cluster_device(cmpr_context *ctx, const cmpr_set_view *d_set,
+                        uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out);
 
 /*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP

@@ -469,6 +469,10 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "layout_scatter_us") *value = (int64_t)(c->layout_kernel_ms[2] * 1e3);
   else if (n == "layout_tiles_us") *value = (int64_t)(c->layout_kernel_ms[3] * 1e3);
   else if (n == "layout_order_us") *value = (int64_t)(c->layout_kernel_ms[4] * 1e3);
+  else if (n == "neighbors_count_us") *value = (int64_t)(c->nb_ms[0] * 1e3);
+  else if (n == "neighbors_scan_us") *value = (int64_t)(c->nb_ms[1] * 1e3);
+  else if (n == "neighbors_fill_us") *value = (int64_t)(c->nb_ms[2] * 1e3);
+  else if (n == "neighbors_order_us") *value = (int64_t)(c->nb_ms[3] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
   else if (n == "heavy_buckets") {
     *value = 0;
@@ -935,6 +939,9 @@ int issue_step(cmpr_context *c, const StepArgs &a, hipStream_t st, hipEvent_t ev
     P.pair_count = c->pair_count;
     P.pair_cap = c->pair_cap;
     P.link_parent = c->link_parent;
+    P.nb_degree = c->nb_degree;
+    P.nb_row_start = c->nb_row_start;
+    P.nb_hit = c->nb_hit;
     if (S.deferred)
       P.pos_ctr = c->ctr_cur;
     if (c->rows && S.deferred)
@@ -1279,6 +1286,33 @@ int cmpr_link_step(cmpr_context *c, uint32_t *parent)
   c->pair_count = (unsigned long long *)parent;
   c->link_parent = parent;
   return run_step_and_wait(c, c->matrix.p, no_hook, no_hook);
+}
+
+int cmpr_check_ready(cmpr_context *c)
+{
+  return check_ready(c);
+}
+
+int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit,
+                       const std::function<int()> &before)
+{
+  int rc = check_ready(c);
+  if (rc)
+    return rc;
+  /* As in link mode the matches take the pairs-mode branch of score_match and the counter is never touched.
+     Unlike a link, a count or a placement must not be made twice: the hook runs before every attempt. */
+  struct Cleanup {
+    cmpr_context *c;
+    ~Cleanup() { c->pair_count = nullptr; c->nb_degree = c->nb_hit = nullptr; c->nb_row_start = nullptr; }
+  } cleanup{c};
+  c->pair_q = c->pair_h = nullptr;
+  c->pair_cap = 0;
+  c->link_parent = nullptr;
+  c->pair_count = (unsigned long long *)degree;
+  c->nb_degree = degree;
+  c->nb_row_start = row_start;
+  c->nb_hit = hit;
+  return run_step_and_wait(c, c->matrix.p, before, no_hook);
 }
 
 extern "C" int cmpr_get_kernel_times(cmpr_context *c, uint32_t max, double *kernel_ms,

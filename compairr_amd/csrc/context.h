@@ -338,6 +338,11 @@ struct cmpr_context {
   /* link mode, set only while cmpr_cluster runs its step (cluster.hip): the union-find forest the matches
      are linked in, in place of being listed */
   uint32_t           *link_parent = nullptr;
+  /* neighbour mode, set only while cmpr_neighbors runs one of its two steps (neighbors.hip; layout.h
+     ProbeParams::nb_*): the degrees / row cursors, and for the fill step the row offsets and the hits */
+  uint32_t           *nb_degree = nullptr, *nb_hit = nullptr;
+  const uint64_t     *nb_row_start = nullptr;
+  double              nb_ms[4] = {};   /* host time of the last cmpr_neighbors: count | scan | fill | order */
 };
 
 
@@ -484,6 +489,16 @@ int cmpr_upload_and_validate(cmpr_context *c, const cmpr_set_view *s, DevBuf<uin
    resident sets united in `parent` (one word per sequence, parent[i] == i or a forest that earlier steps
    left); the same run_step_and_wait loop as the other synchronous entry points */
 int cmpr_link_step(cmpr_context *c, uint32_t *parent);
+
+/* compairr_hip.hip: the synchronous step in neighbour mode (cmpr_neighbors, neighbors.hip).  hit == NULL: the
+   count step, every match adds one to degree[its query]; otherwise the fill step, every match takes a place of
+   its query's row in `hit` (kernels.h score_match).  `before` queues on the context's stream what EVERY attempt
+   of run_step_and_wait needs in front of its kernels: the degrees zeroed, or set to the row lengths. */
+int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit,
+                       const std::function<int()> &before);
+
+/* compairr_hip.hip: what every entry point on the resident sets asks first (CMPR_ESTATE without them) */
+int cmpr_check_ready(cmpr_context *c);
 
 /* ref_index.hip: cmpr_set_reference (on_device: the view holds device pointers) */
 int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longest_query, bool on_device);

@@ -380,8 +380,9 @@ __device__ __forceinline__ void link_pair(uint32_t *parent, uint32_t a, uint32_t
   }
 }
 
-/* One verified (query, hit) pair: list it (pairs mode), link its two sequences (link mode, inside the pairs
-   branch: the matrix path does not see it) or add its score to the matrix cell (overlap.cc:218-245). */
+/* One verified (query, hit) pair: list it (pairs mode), link its two sequences (link mode) or count / place it
+   in the query's row (neighbour mode) -- both inside the pairs branch: the matrix path does not see them --,
+   or add its score to the matrix cell (overlap.cc:218-245). */
 __device__ __forceinline__ void score_match(const ProbeParams &P, uint32_t qs, uint32_t hit,
                                             uint64_t cell, unsigned long long f,
                                             unsigned long long g, unsigned long long *mat_lds)
@@ -392,6 +393,21 @@ __device__ __forceinline__ void score_match(const ProbeParams &P, uint32_t qs, u
       const uint32_t a = P.qrec[qs].orig;
       if (a != hit)
         link_pair(P.link_parent, a, hit);
+      return;
+    }
+    if (P.nb_degree) {
+      /* neighbour mode (cmpr_neighbors): the row of the query is counted (first step) or filled from its end
+         (second step: the degree word is the cursor; which hit gets which place depends on the schedule, the
+         rows are put in order afterwards).  A step finds a pair once, so a cursor never passes zero; the
+         comparison keeps a store inside the row should one ever do. */
+      const uint32_t q = P.qrec[qs].orig;
+      if (!P.nb_hit) {
+        atomicAdd(P.nb_degree + q, 1u);
+      } else {
+        const uint64_t slot = P.nb_row_start[q] + (uint64_t)(atomicSub(P.nb_degree + q, 1u) - 1u);
+        if (slot < P.nb_row_start[q + 1])
+          P.nb_hit[slot] = hit;
+      }
       return;
     }
     /* pairs mode (overlap.cc:232-245) */

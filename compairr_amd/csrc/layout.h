@@ -426,6 +426,12 @@ struct ProbeParams {
   /* link mode (cmpr_cluster): rides on pairs mode -- pair_count is then set but never touched --; matches
      are neither listed nor counted, their two sequences are united in this forest (kernels.h link_pair) */
   uint32_t           *link_parent;  /* NULL everywhere but in cmpr_cluster        */
+  /* neighbour mode (cmpr_neighbors, neighbors.hip): rides on pairs mode as link mode does.  Count step:
+     nb_hit is NULL and a match adds one to nb_degree[query].  Fill step: nb_degree[query] is the number of
+     hits of the row still to come, and a match takes the last free place of its row in nb_hit */
+  uint32_t           *nb_degree;    /* NULL everywhere but in cmpr_neighbors: one word per query */
+  const uint64_t     *nb_row_start; /* fill step: n1 + 1 row offsets into nb_hit */
+  uint32_t           *nb_hit;
   /* sliced mode */
   SliceGeom       geom;
   const Chunk    *chunks;

@@ -29,6 +29,7 @@ EXPORTS = [
     "cmpr_warm_up", "cmpr_warm_up_sized",
     "cmpr_deduplicate", "cmpr_deduplicate_device",
     "cmpr_cluster", "cmpr_cluster_device",
+    "cmpr_neighbors", "cmpr_neighbors_device",
 ]
 
 
@@ -150,6 +151,12 @@ def load_library() -> C.CDLL:
     lib.cmpr_deduplicate_device.argtypes = lib.cmpr_deduplicate.argtypes
     lib.cmpr_cluster.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     lib.cmpr_cluster_device.argtypes = lib.cmpr_cluster.argtypes
+    # (additions do not bump the ABI version: a version-5 library built before this one lacks it, and only the
+    # callers of neighbors() fail on it, with AttributeError -- tools/neighbors_timing.py --against runs bench.py
+    # on the parent commit's build through this binding)
+    if hasattr(lib, "cmpr_neighbors"):
+        lib.cmpr_neighbors.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.cmpr_neighbors_device.argtypes = lib.cmpr_neighbors.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -373,6 +380,33 @@ class HipOverlap:
                                                   C.c_void_p(d_size or None), C.byref(clusters)))
         return clusters.value
 
+    # ---- the pairs as neighbour lists in CSR (include/compairr_hip.h: cmpr_neighbors*) ----
+
+    def neighbors(self):
+        """(row_start uint64[n1 + 1], hits uint32[E]) of the resident sets: the hits of query i, in increasing
+        order, are hits[row_start[i]:row_start[i + 1]] -- the pairs of overlap_pairs() without a sort on the
+        host.  One degree-only call, then one with the exact capacity."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_neighbors(self._ctx, 0, None, None, C.byref(n)))
+        row_start = np.zeros(self._queries() + 1, dtype=np.uint64)
+        hits = np.zeros(n.value, dtype=np.uint32)
+        self._check(self._lib.cmpr_neighbors(self._ctx, n.value, row_start.ctypes.data,
+                                             hits.ctypes.data if n.value else None, C.byref(n)))
+        assert n.value == len(hits)
+        return row_start, hits
+
+    def neighbors_device(self, capacity: int = 0, d_row_start: int = 0, d_hits: int = 0) -> int:
+        """The same into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted) and d_hits
+        (uint32[capacity]; 0 with capacity 0: degrees only).  Returns the edge count; when it exceeds
+        `capacity` nothing was written to d_hits."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_neighbors_device(self._ctx, capacity, C.c_void_p(d_row_start or None),
+                                                    C.c_void_p(d_hits or None), C.byref(n)))
+        return n.value
+
+    def _queries(self) -> int:
+        return self.stats().queries
+
     def kernel_times(self, max_calls: int = 64):
         """(kernel_ms[], probe_ms[]) of the last calls, oldest first (HIP events)."""
         n = min(max_calls, 63)
@@ -420,3 +454,14 @@ def cluster(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
         for name, value in (tunables or {}).items():
             h.set_tunable(name, value)
         return h.cluster(s)
+
+
+def neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
+    """Convenience: (row_start, hits) of set1 against set2 under `opt` (HipOverlap.neighbors) on a context of
+    its own.  `tunables` are set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        h.set_reference(set2, set1.longest)
+        h.set_queries(set1)
+        return h.neighbors()

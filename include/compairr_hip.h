@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -282,6 +282,45 @@ int cmpr_overlap_matrix_device(cmpr_context *ctx, void *d_matrix, void *stream);
  */
 int cmpr_overlap_pairs(cmpr_context *ctx, uint64_t capacity, uint32_t *query_out,
                        uint32_t *hit_out, uint64_t *count_out);
+
+/*
+ * The same pairs as neighbour lists in CSR: who matched whom, per query, in order.  The edge set is exactly what
+ * cmpr_overlap_pairs() lists for the resident sets under the context's options -- the pairs of
+ * find_variant_matches (overlap.cc:232-245), the (i, i) pairs included when one set is resident as both; the call
+ * filters nothing.  n1 is the n of the last cmpr_set_queries*().
+ *   row_start_out[n1 + 1]  row_start[0] == 0, row_start[i + 1] - row_start[i] = the number of hits of query i.
+ *                          Always written in full and always exact, whatever `capacity` is.  May be NULL when
+ *                          only *n_edges_out is wanted.
+ *   hit_out[capacity]      row i occupies [row_start[i], row_start[i + 1]): sequence numbers of the reference
+ *                          set in strictly increasing order.  When there are more edges than `capacity`, NOTHING
+ *                          is written here (cmpr_overlap_pairs() writes an arbitrary subset; this call does not):
+ *                          the call still returns CMPR_OK with *n_edges_out > capacity, and row_start says what
+ *                          to allocate.  capacity == 0 with hit_out == NULL is the degree-only call: one step, no
+ *                          sort.  capacity > 0 with hit_out == NULL is CMPR_EINVAL.
+ *   *n_edges_out           required (NULL: CMPR_EINVAL), a HOST pointer in both variants; == row_start[n1] ==
+ *                          cmpr_stats.matches of the step.  cmpr_get_stats() afterwards describes the last step
+ *                          the call ran.
+ * cmpr_neighbors_device() takes both arrays as device memory on the context's device and writes only the
+ * elements named above; only the edge count crosses PCIe.
+ *
+ * Results are bit-identical from run to run, under every tunable, and with set 2 indexed in parts.  The call
+ * counts the hits per query in one step, sums the counts into row_start, runs the step again to put every hit
+ * into its row, and sorts each row in place (compairr_amd/csrc/neighbors.hip): two steps where
+ * cmpr_overlap_pairs() runs one, and no per-edge memory beyond the caller's hit_out (the host variant holds the
+ * two arrays on the device for the duration of the call).  Temporaries: 4 bytes per query, the scratch of the
+ * sum, 4 bytes per row of more than 64 hits, and for rows of more than 8192 hits 16 bytes each plus the longest
+ * of them once.  Everything is freed before the call returns, also when it fails.
+ *
+ * Synchronous; needs both resident sets (CMPR_ESTATE as for cmpr_overlap_matrix()).  With the tunable
+ * work_shard_count above 1, and after cmpr_set_queries_routed(), the call is CMPR_EUNSUPPORTED: such a context
+ * holds part of each row, and rows do not add up by a sum.  options.existence and the scores play no part.  The
+ * resident sets, the plan and the other entry points are as usable afterwards as before; the call may be
+ * repeated.  An empty query set is CMPR_OK with row_start == {0} and no edges.
+ */
+int cmpr_neighbors(cmpr_context *ctx, uint64_t capacity,
+                   uint64_t *row_start_out, uint32_t *hit_out, uint64_t *n_edges_out);
+int cmpr_neighbors_device(cmpr_context *ctx, uint64_t capacity,
+                          uint64_t *d_row_start_out, uint32_t *d_hit_out, uint64_t *n_edges_out);
 
 /*
  * Exact duplicates inside one set: the number the reference reports as

@@ -8,7 +8,7 @@ no compute path of its own and no CPU fallback.
 """
 
 from .sets import RepertoireSet  # noqa: F401
-from .hip import HipOverlap, HipError, Options, Stats, cluster, deduplicate, library_path, neighbors  # noqa: F401
+from .hip import HipOverlap, HipError, Options, Stats, cluster, deduplicate, existence_csr, library_path, neighbors  # noqa: F401
 
 __all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "deduplicate",
-           "library_path", "neighbors"]
+           "existence_csr", "library_path", "neighbors"]

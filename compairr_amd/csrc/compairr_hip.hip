@@ -473,6 +473,11 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "neighbors_scan_us") *value = (int64_t)(c->nb_ms[1] * 1e3);
   else if (n == "neighbors_fill_us") *value = (int64_t)(c->nb_ms[2] * 1e3);
   else if (n == "neighbors_order_us") *value = (int64_t)(c->nb_ms[3] * 1e3);
+  else if (n == "existence_edges_us") *value = (int64_t)(c->ex_ms[0] * 1e3);
+  else if (n == "existence_group_us") *value = (int64_t)(c->ex_ms[1] * 1e3);
+  else if (n == "existence_count_us") *value = (int64_t)(c->ex_ms[2] * 1e3);
+  else if (n == "existence_reduce_us") *value = (int64_t)(c->ex_ms[3] * 1e3);
+  else if (n == "existence_copy_us") *value = (int64_t)(c->ex_ms[4] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
   else if (n == "heavy_buckets") {
     *value = 0;

@@ -343,6 +343,7 @@ struct cmpr_context {
   uint32_t           *nb_degree = nullptr, *nb_hit = nullptr;
   const uint64_t     *nb_row_start = nullptr;
   double              nb_ms[4] = {};   /* host time of the last cmpr_neighbors: count | scan | fill | order */
+  double              ex_ms[5] = {};   /* ... of the last cmpr_existence_csr: edges | group | count | reduce | copy-out */
 };
 
 
@@ -496,6 +497,34 @@ int cmpr_link_step(cmpr_context *c, uint32_t *parent);
    of run_step_and_wait needs in front of its kernels: the degrees zeroed, or set to the row lengths. */
 int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit,
                        const std::function<int()> &before);
+
+/* neighbors.hip: the edges of the resident sets for a caller inside the library (cmpr_existence_csr,
+   existence.hip) -- the count step, the sum and the fill step of cmpr_neighbors into buffers of its own, the rows
+   NOT put in order.  The caller has asked cmpr_check_ready and refused shards and routed sets.  With no edge,
+   `hit` stays empty.  Everything is released with the struct. */
+struct NeighborEdges {
+  DevBuf<uint32_t> degree;             /* n1 + 1 words; all zero once the fill step has run */
+  DevBuf<uint64_t> row_start;          /* n1 + 1 (cmpr_neighbors: only when the caller's array is not on the device) */
+  DevBuf<uint32_t> hit;                /* `total` (cmpr_neighbors: likewise) */
+  DevBuf<unsigned long long> census;   /* [0] rows of more than 64 hits, [1] of those the rows of more than 8192,
+                                          [2] the longest of the latter; [3..4] two list counters, zero */
+  DevBuf<char>     scan_tmp;
+  size_t           scan_bytes = 0;
+  bool             pretend_no_redo = false;
+  uint64_t         total = 0, n_big = 0, n_long = 0, longest = 0;   /* rows of 65 .. 8192 | longer | the longest such */
+  NeighborEdges() = default;
+  NeighborEdges(const NeighborEdges &) = delete;
+  NeighborEdges &operator=(const NeighborEdges &) = delete;
+  ~NeighborEdges()
+  {
+    degree.release();
+    row_start.release();
+    hit.release();
+    census.release();
+    scan_tmp.release();
+  }
+};
+int cmpr_neighbor_edges(cmpr_context *c, NeighborEdges &e);
 
 /* compairr_hip.hip: what every entry point on the resident sets asks first (CMPR_ESTATE without them) */
 int cmpr_check_ready(cmpr_context *c);

@@ -1,0 +1,647 @@
+/*
+ * existence.hip -- the -x table without its zeros.  cmpr_existence_csr / cmpr_existence_csr_device: per query, the
+ * set-2 repertoires it has a match in and the integer cmpr_overlap_matrix() holds in that cell on a context with
+ * options.existence (overlap.cc:218-231), as CSR: row_start[n1 + 1], and the cells of row i in
+ * [row_start[i], row_start[i + 1]) in increasing order of the repertoire.  A post-pass over the neighbour rows of
+ * neighbors.hip; no probe kernel knows about it, and the n1 x R2 matrix exists nowhere.
+ *
+ *   edges    the count step, the sum and the fill step of cmpr_neighbors into temporaries (cmpr_neighbor_edges):
+ *            row i holds its hits in the order of arrival.  They are not put in order of the hit.
+ *   group    each row sorted in place by (rep2[hit], hit): the key rep << 32 | hit is gathered once and only its
+ *            low half is stored back, so a run of equal repertoires is a run of positions.  The cells of a row
+ *            are the positions whose repertoire differs from the one before (heads); their number goes where the
+ *            row's degree word was (zero since the fill step), counted by whoever sorted the row.
+ *   count    row_start = exclusive 64-bit sum of those n1 + 1 words (hipcub).  The cell count reaches the host
+ *            -- with the cell offsets of the rows beyond LDS -- in the call's one wait beyond those of the edges.
+ *   reduce   only when the cells fit `capacity`: the head of run number k of row i writes the repertoire to
+ *            row_start[i] + k, and the scores of the run's hits (kernels.h score_match with f = cnt1[i],
+ *            g = cnt2[hit], or 1) are summed into the value there.  Integer sums: the order of the hits inside a
+ *            run does not show.  cnt1 is scattered from the query records first (ex_cnt1_kernel; no per-query
+ *            array of the caller survives cmpr_set_queries), unless the counts are ignored.
+ *   copy-out for the host variant.
+ *
+ * Both passes over the rows take the paths of neighbors.hip, by the row's number of HITS n, with its thresholds:
+ *
+ *   n <= LANE_MAX = 8   one lane per row.  group: eight 64-bit keys in registers, the same 19 comparators;
+ *                       reduce: the lane walks its row.
+ *   n <= WAVE = 64      one hit per lane, the wave takes such rows of its 64 lanes one after the other.  group:
+ *                       the bitonic sort with 21 steps of two shuffles; reduce: heads by ballot, the run sums by a
+ *                       segmented scan of six shuffle steps, the last lane of a run stores.  No LDS, no atomics.
+ *   n <= LDS_MAX = 8192 one workgroup of 256 lanes per listed row.  group: bitonic in LDS.  The key is 64 bits, so
+ *                       8192 of them are 64 KiB -- what a workgroup may declare statically, and two such
+ *                       workgroups still fit the CU's 160 KiB; keeping the threshold of neighbors.hip keeps ONE
+ *                       census (the one the edges come with) for both files.  A lane reads s[t] and s[t ^ j] as
+ *                       8-byte words at consecutive t: a half-wave covers one 256-byte bank row, no conflict.
+ *                       reduce: 256 positions per round; a round's heads are counted per wave (ballot) and summed
+ *                       over the four waves through 16 bytes of LDS, which ranks every position; the segmented
+ *                       scan as above, and the last lane of a run INSIDE a wave adds its sum to the value with
+ *                       one atomicAdd (a run crosses waves and rounds).  These rows' values are zeroed by the
+ *                       workgroup first; nothing else of value_out is.
+ *   longer              on the host, row by row, the whole GPU for each: group = the repertoires gathered,
+ *                       hipcub::DeviceRadixSort::SortPairs (key: repertoire, on its significant bits; value: hit),
+ *                       the hits copied back, the heads counted; reduce = hipcub::DeviceReduce::ReduceByKey
+ *                       straight into the row's cells.  (Ties are not ordered by the hit here: a sum does not ask.)
+ *
+ * Device memory for the duration of the call: per query 4 bytes (degrees, then cells per row) and 8 (row offsets of
+ * the edges), 4 bytes per edge, 8 per query for cnt1 (not with ignore_counts), the sums' scratch, 4 bytes per row
+ * of more than 64 hits, and for rows of more than 8192 hits 24 bytes each plus 12 times the longest of them plus the
+ * scratch of the sort and of the reduction.  The host variant adds what the device variant is handed: 8 bytes per
+ * query, 12 per cell.  Everything is freed before the call returns, also when it fails.
+ */
+#include "context.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <chrono>
+#include <new>
+
+using namespace cmpr;
+
+namespace {
+
+constexpr uint32_t EX_WG = 256;
+constexpr uint32_t EX_WAVES = EX_WG / WAVE;
+constexpr uint32_t LANE_MAX = 8;
+constexpr uint32_t LDS_MAX = 8192;                 /* = neighbors.hip: the census of the edges counts by it */
+constexpr uint64_t EX_PAD = ~0ull;                 /* behind a row's end while it is sorted: above every key */
+
+template <typename T>
+struct Tmp {
+  DevBuf<T> b;
+  ~Tmp() { b.release(); }
+};
+
+struct U32To64 {
+  __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
+};
+
+/* what a hit adds to its cell: score_match (kernels.h) with f the query's count and g the hit's */
+struct ExScore {
+  const uint64_t *cnt1, *cnt2;          /* NULL with ignore_counts */
+  int32_t         score, ignore_counts;
+  __device__ __forceinline__ unsigned long long of(unsigned long long f, uint32_t hit) const
+  {
+    if (ignore_counts)
+      return 1;
+    const unsigned long long g = cnt2[hit];
+    switch (score) {
+    case CMPR_SCORE_MIN: case CMPR_SCORE_JACCARD: return f < g ? f : g;
+    case CMPR_SCORE_MAX:                          return f > g ? f : g;
+    case CMPR_SCORE_MEAN:                         return f + g;
+    default:                                      return f * g;
+    }
+  }
+  __device__ __forceinline__ unsigned long long count_of(uint64_t row) const
+  {
+    return ignore_counts ? 1ull : (unsigned long long)cnt1[row];
+  }
+};
+
+/* the long rows' values for hipcub: hit -> score, the query's count read where it lies */
+struct ExScoreOfHit {
+  ExScore         s;
+  const uint64_t *f;                    /* cnt1 + row, or NULL */
+  __device__ unsigned long long operator()(uint32_t hit) const { return s.of(f ? (unsigned long long)*f : 1ull, hit); }
+};
+
+/* cnt1[i] of the resident queries: lanes 0 .. nvalid - 1 of a tile are queries, the rest is padding */
+__global__ void __launch_bounds__(EX_WG)
+ex_cnt1_kernel(const TileDesc *tiles, const QueryRec *qrec, uint64_t nslots, uint64_t n1, uint64_t *cnt1)
+{
+  const uint64_t slot = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  if (slot >= nslots || (uint32_t)(slot % WAVE) >= tiles[slot / WAVE].nvalid)
+    return;
+  const uint32_t orig = qrec[slot].orig;
+  if (orig < n1)
+    cnt1[orig] = qrec[slot].cnt;
+}
+
+__device__ __forceinline__ void ex_cx(uint64_t &a, uint64_t &b)
+{
+  const uint64_t lo = a < b ? a : b, hi = a < b ? b : a;
+  a = lo;
+  b = hi;
+}
+
+__device__ __forceinline__ uint64_t ex_key(const uint32_t *rep2, uint32_t hit)
+{
+  return (uint64_t)rep2[hit] << 32 | hit;
+}
+
+/* bits 0 .. lane of a ballot */
+__device__ __forceinline__ uint64_t ex_upto(uint32_t lane)
+{
+  return ~0ull >> (63u - lane);
+}
+
+/* Inclusive sums of v over the lanes of a wave, starting anew at every lane whose bit is set in `heads` (lane 0's
+   is, or it starts a wave that continues a run): lane - off lies in the run of `lane` when no head lies in
+   (lane - off, lane]. */
+__device__ __forceinline__ unsigned long long ex_run_sums(unsigned long long v, uint64_t heads, uint32_t lane)
+{
+#pragma unroll
+  for (uint32_t off = 1; off < WAVE; off <<= 1) {
+    const unsigned long long below = __shfl_up(v, off, WAVE);
+    if (lane >= off && ((heads >> (lane - off + 1u)) & ((1ull << off) - 1ull)) == 0)
+      v += below;
+  }
+  return v;
+}
+
+/* group, one lane per row: rows of 2 .. LANE_MAX sorted by their lane, rows of up to WAVE by the wave, longer rows
+   listed (big_rows / long_desc: start, length, row), as nb_sort_short_kernel does.  ncell[i] = the heads of row i
+   for the rows handled here, 0 for the listed ones (their sorters add to it) and for the word behind the last row. */
+__global__ void __launch_bounds__(EX_WG)
+ex_group_short_kernel(const uint64_t *estart, uint32_t *hit, const uint32_t *rep2, uint64_t n, uint32_t *ncell,
+                      uint32_t *big_rows, uint64_t big_cap, unsigned long long *long_desc, uint64_t long_cap,
+                      unsigned long long *list_ctr)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint32_t lane = lane_id();
+  uint64_t start = 0, len = 0;
+  if (i < n) {
+    start = estart[i];
+    len = estart[i + 1] - start;
+  }
+  uint32_t cells = len == 1 ? 1u : 0u;
+  if (len >= 2 && len <= LANE_MAX) {
+    uint64_t v[LANE_MAX];
+#pragma unroll
+    for (uint32_t k = 0; k < LANE_MAX; k++)
+      v[k] = k < len ? ex_key(rep2, hit[start + k]) : EX_PAD;
+    /* 19 comparators in 6 layers (Knuth, TAOCP 3, 5.3.4) */
+    ex_cx(v[0], v[1]); ex_cx(v[2], v[3]); ex_cx(v[4], v[5]); ex_cx(v[6], v[7]);
+    ex_cx(v[0], v[2]); ex_cx(v[1], v[3]); ex_cx(v[4], v[6]); ex_cx(v[5], v[7]);
+    ex_cx(v[1], v[2]); ex_cx(v[5], v[6]); ex_cx(v[0], v[4]); ex_cx(v[3], v[7]);
+    ex_cx(v[1], v[5]); ex_cx(v[2], v[6]);
+    ex_cx(v[1], v[4]); ex_cx(v[3], v[6]);
+    ex_cx(v[2], v[4]); ex_cx(v[3], v[5]);
+    ex_cx(v[3], v[4]);
+    cells = 1;
+#pragma unroll
+    for (uint32_t k = 0; k < LANE_MAX; k++)
+      if (k < len) {
+        hit[start + k] = (uint32_t)v[k];
+        if (k > 0 && (v[k] >> 32) != (v[k - 1] >> 32))
+          cells++;
+      }
+  } else if (len > WAVE) {
+    if (len > LDS_MAX) {
+      const unsigned long long k = atomicAdd(list_ctr + 1, 1ull);
+      if (k < long_cap) {
+        long_desc[3 * k] = start;
+        long_desc[3 * k + 1] = len;
+        long_desc[3 * k + 2] = i;
+      }
+    } else {
+      const unsigned long long k = atomicAdd(list_ctr + 0, 1ull);
+      if (k < big_cap)
+        big_rows[k] = (uint32_t)i;
+    }
+  }
+  /* the wave's rows of LANE_MAX + 1 .. WAVE */
+  uint64_t todo = __ballot(len > LANE_MAX && len <= WAVE);
+  while (todo) {
+    const uint32_t src = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+    todo &= todo - 1;
+    const uint64_t s = __shfl(start, src, WAVE);
+    const uint32_t m = (uint32_t)__shfl(len, src, WAVE);
+    unsigned long long v = lane < m ? ex_key(rep2, hit[s + lane]) : EX_PAD;
+    for (uint32_t k = 2; k <= WAVE; k <<= 1)
+      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+        const unsigned long long other = __shfl_xor(v, j, WAVE);
+        const bool up = (lane & k) == 0, low = (lane & j) == 0;
+        v = (up == low) ? (v < other ? v : other) : (v < other ? other : v);
+      }
+    const unsigned long long before = __shfl_up(v, 1, WAVE);
+    const uint64_t heads = __ballot(lane < m && (lane == 0 || (v >> 32) != (before >> 32)));
+    if (lane < m)
+      hit[s + lane] = (uint32_t)v;
+    if (lane == src)
+      cells = (uint32_t)__popcll(heads);
+  }
+  if (i <= n)
+    ncell[i] = cells;
+}
+
+/* group, one workgroup per listed row of WAVE + 1 .. LDS_MAX hits: bitonic in LDS over the next power of two */
+__global__ void __launch_bounds__(EX_WG)
+ex_group_lds_kernel(const uint64_t *estart, uint32_t *hit, const uint32_t *rep2, const uint32_t *big_rows,
+                    uint32_t *ncell)
+{
+  __shared__ uint64_t s[LDS_MAX];
+  const uint32_t row = big_rows[blockIdx.x];
+  const uint64_t start = estart[row];
+  const uint64_t len64 = estart[row + 1] - start;
+  if (len64 > LDS_MAX)
+    return;                                  /* (the list holds no such row; nothing is indexed beyond s) */
+  const uint32_t len = (uint32_t)len64;
+  uint32_t np = 2 * WAVE;
+  while (np < len)
+    np <<= 1;
+  for (uint32_t t = threadIdx.x; t < np; t += EX_WG)
+    s[t] = t < len ? ex_key(rep2, hit[start + t]) : EX_PAD;
+  __syncthreads();
+  for (uint32_t k = 2; k <= np; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = threadIdx.x; t < np; t += EX_WG) {
+        const uint32_t u = t ^ j;
+        if (u > t) {
+          const uint64_t a = s[t], b = s[u];
+          if (((t & k) == 0) == (a > b)) {
+            s[t] = b;
+            s[u] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  uint32_t heads = 0;
+  for (uint32_t t = threadIdx.x; t < len; t += EX_WG) {
+    hit[start + t] = (uint32_t)s[t];
+    if (t == 0 || (s[t] >> 32) != (s[t - 1] >> 32))
+      heads++;
+  }
+#pragma unroll
+  for (uint32_t off = WAVE / 2; off > 0; off >>= 1)
+    heads += __shfl_xor(heads, off, WAVE);
+  if (lane_id() == 0 && heads)
+    atomicAdd(ncell + row, heads);           /* (zero since ex_group_short_kernel; four adders, integers) */
+}
+
+/* group, rows beyond LDS: the repertoires of a row's hits as sort keys ... */
+__global__ void __launch_bounds__(EX_WG)
+ex_gather_rep_kernel(const uint32_t *hit, uint64_t len, const uint32_t *rep2, uint32_t *key)
+{
+  const uint64_t p = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  if (p < len)
+    key[p] = rep2[hit[p]];
+}
+
+/* ... and the heads of the sorted keys */
+__global__ void __launch_bounds__(EX_WG)
+ex_count_heads_kernel(const uint32_t *key, uint64_t len, uint32_t *out)
+{
+  const uint64_t p = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint64_t heads = __ballot(p < len && (p == 0 || key[p] != key[p - 1]));
+  if (lane_id() == 0 && heads)
+    atomicAdd(out, (uint32_t)__popcll(heads));
+}
+
+/* reduce, one lane per row: rows of up to LANE_MAX walked by their lane, rows of up to WAVE by the wave */
+__global__ void __launch_bounds__(EX_WG)
+ex_reduce_short_kernel(const uint64_t *estart, const uint32_t *hit, const uint32_t *rep2, uint64_t n,
+                       const uint64_t *cstart, uint32_t *rep_out, unsigned long long *val_out, const ExScore S)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint32_t lane = lane_id();
+  uint64_t start = 0, len = 0, c = 0;
+  unsigned long long f = 1;
+  if (i < n) {
+    start = estart[i];
+    len = estart[i + 1] - start;
+    if (len) {
+      c = cstart[i];
+      f = S.count_of(i);
+    }
+  }
+  if (len >= 1 && len <= LANE_MAX) {
+    uint32_t cur = 0;
+    unsigned long long sum = 0;
+    uint64_t at = c;
+    for (uint32_t k = 0; k < (uint32_t)len; k++) {
+      const uint32_t h = hit[start + k], r = rep2[h];
+      if (k > 0 && r != cur) {
+        rep_out[at] = cur;
+        val_out[at] = sum;
+        at++;
+        sum = 0;
+      }
+      cur = r;
+      sum += S.of(f, h);
+    }
+    rep_out[at] = cur;
+    val_out[at] = sum;
+  }
+  uint64_t todo = __ballot(len > LANE_MAX && len <= WAVE);
+  while (todo) {
+    const uint32_t src = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+    todo &= todo - 1;
+    const uint64_t s = __shfl(start, src, WAVE), cs = __shfl(c, src, WAVE);
+    const uint32_t m = (uint32_t)__shfl(len, src, WAVE);
+    const unsigned long long fs = __shfl(f, src, WAVE);
+    const bool valid = lane < m;
+    uint32_t r = 0xffffffffu;
+    unsigned long long sc = 0;
+    if (valid) {
+      const uint32_t h = hit[s + lane];
+      r = rep2[h];
+      sc = S.of(fs, h);
+    }
+    const uint32_t before = __shfl_up(r, 1, WAVE);
+    const bool head = valid && (lane == 0 || r != before);
+    const uint64_t heads = __ballot(head);
+    const unsigned long long sum = ex_run_sums(sc, heads, lane);
+    const uint64_t at = cs + (uint32_t)__popcll(heads & ex_upto(lane)) - 1u;
+    if (head)
+      rep_out[at] = r;
+    if (valid && (lane + 1 == m || ((heads >> (lane + 1u)) & 1ull)))
+      val_out[at] = sum;
+  }
+}
+
+/* reduce, one workgroup per listed row of WAVE + 1 .. LDS_MAX hits, EX_WG positions per round */
+__global__ void __launch_bounds__(EX_WG)
+ex_reduce_lds_kernel(const uint64_t *estart, const uint32_t *hit, const uint32_t *rep2, const uint32_t *big_rows,
+                     const uint64_t *cstart, uint32_t *rep_out, unsigned long long *val_out, const ExScore S)
+{
+  __shared__ uint32_t wave_heads[2][EX_WAVES];
+  const uint32_t row = big_rows[blockIdx.x];
+  const uint64_t start = estart[row];
+  const uint64_t len64 = estart[row + 1] - start;
+  if (len64 > LDS_MAX)
+    return;
+  const uint32_t len = (uint32_t)len64;
+  const uint64_t c = cstart[row];
+  const uint32_t cells = (uint32_t)(cstart[row + 1] - c);
+  const unsigned long long f = S.count_of(row);
+  const uint32_t lane = lane_id(), wave = threadIdx.x / WAVE;
+  for (uint32_t t = threadIdx.x; t < cells; t += EX_WG)
+    val_out[c + t] = 0;
+  __syncthreads();                           /* (the zeros are in memory before any wave of this workgroup adds) */
+  uint32_t base = 0;                         /* heads of the rounds so far */
+  for (uint32_t t0 = 0, round = 0; t0 < len; t0 += EX_WG, round++) {
+    const uint32_t t = t0 + threadIdx.x;
+    const bool valid = t < len;
+    uint32_t r = 0xffffffffu;
+    unsigned long long sc = 0;
+    if (valid) {
+      const uint32_t h = hit[start + t];
+      r = rep2[h];
+      sc = S.of(f, h);
+    }
+    uint32_t before = __shfl_up(r, 1, WAVE);
+    if (lane == 0 && valid && t > 0)
+      before = rep2[hit[start + t - 1]];
+    const bool head = valid && (t == 0 || r != before);
+    const uint64_t heads = __ballot(head);
+    if (lane == 0)
+      wave_heads[round & 1u][wave] = (uint32_t)__popcll(heads);
+    __syncthreads();
+    uint32_t mine = base;
+#pragma unroll
+    for (uint32_t w = 0; w < EX_WAVES; w++) {
+      const uint32_t hw = wave_heads[round & 1u][w];
+      mine += w < wave ? hw : 0u;
+      base += hw;
+    }
+    /* a wave's first lane starts a sum whether or not it starts a run */
+    const unsigned long long sum = ex_run_sums(sc, heads | 1ull, lane);
+    const uint32_t rank = mine + (uint32_t)__popcll(heads & ex_upto(lane)) - 1u;
+    if (head && rank < cells)
+      rep_out[c + rank] = r;
+    if (valid && rank < cells && (lane + 1 == WAVE || t + 1 == len || ((heads >> (lane + 1u)) & 1ull)))
+      atomicAdd(val_out + c + rank, sum);
+  }
+}
+
+uint32_t blocks_for(uint64_t n)
+{
+  return (uint32_t)((n + EX_WG - 1) / EX_WG);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+/* a row beyond LDS as ex_group_short_kernel listed it, and where its cells go */
+struct LongRow {
+  uint64_t start, len, row, cell0;
+};
+
+int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *rep_out,
+                   uint64_t *value_out, uint64_t *n_cells_out, bool on_device)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  if (!n_cells_out)
+    return fail(c, CMPR_EINVAL, "cmpr_existence_csr: n_cells_out is NULL");
+  *n_cells_out = 0;
+  if (capacity && !rep_out)
+    return fail(c, CMPR_EINVAL, "cmpr_existence_csr: repertoire_out is NULL with a capacity");
+  if (capacity && !value_out)
+    return fail(c, CMPR_EINVAL, "cmpr_existence_csr: value_out is NULL with a capacity");
+  int rc;
+  if ((rc = cmpr_check_ready(c)))
+    return rc;
+  if (is_f64_score(c->opt))
+    return fail(c, CMPR_EINVAL, "cmpr_existence_csr: ratio score needs cmpr_overlap_matrix_f64");
+  if (c->work_shard_count > 1)
+    return fail(c, CMPR_EUNSUPPORTED, "cmpr_existence_csr: a work shard holds part of each row (work_shard_count > 1)");
+  if (c->routed)
+    return fail(c, CMPR_EUNSUPPORTED, "cmpr_existence_csr: a routed query set holds part of each row "
+                                      "(cmpr_set_queries_routed)");
+  const uint64_t n1 = c->n1;
+  for (double &t : c->ex_ms)
+    t = 0;
+
+  /* ---- edges ---- */
+  auto t0 = std::chrono::steady_clock::now();
+  NeighborEdges e;
+  if ((rc = cmpr_neighbor_edges(c, e)))
+    return rc;
+  c->ex_ms[0] = ms_since(t0);
+  const uint64_t total = e.total, n_big = e.n_big, n_long = e.n_long, longest = e.longest;
+  if (total == 0) {
+    /* no match at all: every row is empty */
+    if (row_start_out && on_device) {
+      HIP_TRY(c, hipMemsetAsync(row_start_out, 0, (size_t)(n1 + 1) * sizeof(uint64_t), c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (row_start_out) {
+      for (uint64_t i = 0; i <= n1; i++)
+        row_start_out[i] = 0;
+    }
+    return CMPR_OK;
+  }
+  const uint64_t *const estart = e.row_start.p;
+  uint32_t *const hit = e.hit.p;
+  uint32_t *const ncell = e.degree.p;         /* zero since the fill step */
+  const uint32_t *const rep2 = c->rep2.p;
+
+  /* ---- group ---- */
+  t0 = std::chrono::steady_clock::now();
+  Tmp<uint64_t> rows;
+  Tmp<uint32_t> big_rows, key_a, key_b, hit_b, runs;
+  Tmp<unsigned long long> long_desc;
+  Tmp<char> sort_tmp, reduce_tmp;
+  size_t sort_bytes = 0;
+  uint64_t *cstart = on_device ? row_start_out : nullptr;
+  if (!cstart) {
+    if ((rc = dev_alloc(c, rows.b, (size_t)(n1 + 1)))) return rc;
+    cstart = rows.b.p;
+  }
+  int rep_bits = 1;
+  while (rep_bits < 32 && (c->R2 - 1u) >> rep_bits)
+    rep_bits++;
+  if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
+  if (n_long) {
+    if ((rc = dev_alloc(c, long_desc.b, (size_t)(3 * n_long)))) return rc;
+    if ((rc = dev_alloc(c, key_a.b, (size_t)longest))) return rc;
+    if ((rc = dev_alloc(c, key_b.b, (size_t)longest))) return rc;
+    if ((rc = dev_alloc(c, hit_b.b, (size_t)longest))) return rc;
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                  (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)longest, 0,
+                                                  rep_bits, c->stream));
+    if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
+  }
+  unsigned long long *list_ctr = e.census.p + 3;       /* (zero since the census) */
+  hipLaunchKernelGGL(ex_group_short_kernel, dim3(blocks_for(n1 + 1)), dim3(EX_WG), 0, c->stream, estart, hit, rep2, n1,
+                     ncell, big_rows.b.p, n_big, long_desc.b.p, n_long, list_ctr);
+  HIP_TRY(c, hipGetLastError());
+  if (n_big) {
+    hipLaunchKernelGGL(ex_group_lds_kernel, dim3((uint32_t)n_big), dim3(EX_WG), 0, c->stream, estart, hit, rep2,
+                       big_rows.b.p, ncell);
+    HIP_TRY(c, hipGetLastError());
+  }
+  std::vector<LongRow> lr((size_t)n_long);
+  if (n_long) {
+    std::vector<unsigned long long> desc((size_t)(3 * n_long));
+    HIP_TRY(c, hipMemcpyAsync(desc.data(), long_desc.b.p, desc.size() * sizeof(unsigned long long),
+                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (uint64_t k = 0; k < n_long; k++) {
+      lr[k] = LongRow{desc[3 * k], desc[3 * k + 1], desc[3 * k + 2], 0};
+      const LongRow &r = lr[k];
+      if (r.len > longest || r.start + r.len > total || r.row >= n1)
+        return fail(c, CMPR_EDEVICE, "cmpr_existence_csr: a listed row lies outside the hits");
+      hipLaunchKernelGGL(ex_gather_rep_kernel, dim3(blocks_for(r.len)), dim3(EX_WG), 0, c->stream, hit + r.start, r.len,
+                         rep2, key_a.b.p);
+      HIP_TRY(c, hipGetLastError());
+      size_t b = sort_bytes;
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(sort_tmp.b.p, b, (const uint32_t *)key_a.b.p, key_b.b.p,
+                                                    (const uint32_t *)(hit + r.start), hit_b.b.p, (size_t)r.len, 0,
+                                                    rep_bits, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(hit + r.start, hit_b.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                c->stream));
+      hipLaunchKernelGGL(ex_count_heads_kernel, dim3(blocks_for(r.len)), dim3(EX_WG), 0, c->stream, key_b.b.p, r.len,
+                         ncell + r.row);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
+  c->ex_ms[1] = ms_since(t0);
+
+  /* ---- count ---- (the scratch of the edges' sum serves: the same n1 + 1 words of the same type) */
+  t0 = std::chrono::steady_clock::now();
+  hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> wide(ncell, U32To64());
+  size_t scan_bytes = e.scan_bytes;
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(e.scan_tmp.p, scan_bytes, wide, (unsigned long long *)cstart,
+                                              (size_t)(n1 + 1), c->stream));
+  unsigned long long cells = 0;
+  HIP_TRY(c, hipMemcpyAsync(&cells, cstart + n1, sizeof cells, hipMemcpyDeviceToHost, c->stream));
+  for (LongRow &r : lr)
+    HIP_TRY(c, hipMemcpyAsync(&r.cell0, cstart + r.row, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  if (!on_device && row_start_out)
+    HIP_TRY(c, hipMemcpyAsync(row_start_out, cstart, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->ex_ms[2] = ms_since(t0);
+  *n_cells_out = cells;
+  if (!rep_out || cells > capacity)
+    return CMPR_OK;
+
+  /* ---- reduce ---- */
+  t0 = std::chrono::steady_clock::now();
+  Tmp<uint64_t> cnt1, vals;
+  Tmp<uint32_t> reps;
+  uint32_t *d_rep = on_device ? rep_out : nullptr;
+  unsigned long long *d_val = on_device ? (unsigned long long *)value_out : nullptr;
+  if (!on_device) {
+    if ((rc = dev_alloc(c, reps.b, (size_t)cells))) return rc;
+    if ((rc = dev_alloc(c, vals.b, (size_t)cells))) return rc;
+    d_rep = reps.b.p;
+    d_val = (unsigned long long *)vals.b.p;
+  }
+  ExScore S{nullptr, nullptr, c->opt.score, c->opt.ignore_counts ? 1 : 0};
+  if (!S.ignore_counts) {
+    if (!c->cnt2.p)
+      return fail(c, CMPR_ESTATE, "cmpr_existence_csr: the reference set has no counts");
+    if ((rc = dev_alloc(c, cnt1.b, (size_t)n1))) return rc;
+    const uint64_t nslots = (uint64_t)c->ntiles * WAVE;
+    hipLaunchKernelGGL(ex_cnt1_kernel, dim3(blocks_for(nslots)), dim3(EX_WG), 0, c->stream, c->tiles.p, c->qrec.p,
+                       nslots, n1, cnt1.b.p);
+    HIP_TRY(c, hipGetLastError());
+    S.cnt1 = cnt1.b.p;
+    S.cnt2 = c->cnt2.p;
+  }
+  hipLaunchKernelGGL(ex_reduce_short_kernel, dim3(blocks_for(n1)), dim3(EX_WG), 0, c->stream, estart, hit, rep2, n1,
+                     cstart, d_rep, d_val, S);
+  HIP_TRY(c, hipGetLastError());
+  if (n_big) {
+    hipLaunchKernelGGL(ex_reduce_lds_kernel, dim3((uint32_t)n_big), dim3(EX_WG), 0, c->stream, estart, hit, rep2,
+                       big_rows.b.p, cstart, d_rep, d_val, S);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if (n_long) {
+    using ScoreIt = hipcub::TransformInputIterator<unsigned long long, ExScoreOfHit, const uint32_t *>;
+    size_t reduce_bytes = 0;
+    HIP_TRY(c, hipcub::DeviceReduce::ReduceByKey(nullptr, reduce_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                 ScoreIt(nullptr, ExScoreOfHit{S, nullptr}),
+                                                 (unsigned long long *)nullptr, (uint32_t *)nullptr, hipcub::Sum(),
+                                                 (size_t)longest, c->stream));
+    if ((rc = dev_alloc(c, reduce_tmp.b, reduce_bytes))) return rc;
+    if ((rc = dev_alloc(c, runs.b, 1))) return rc;
+    for (const LongRow &r : lr) {
+      if (r.cell0 > cells)
+        return fail(c, CMPR_EDEVICE, "cmpr_existence_csr: a listed row lies outside the cells");
+      hipLaunchKernelGGL(ex_gather_rep_kernel, dim3(blocks_for(r.len)), dim3(EX_WG), 0, c->stream, hit + r.start, r.len,
+                         rep2, key_a.b.p);
+      HIP_TRY(c, hipGetLastError());
+      size_t b = reduce_bytes;
+      HIP_TRY(c, hipcub::DeviceReduce::ReduceByKey(reduce_tmp.b.p, b, (const uint32_t *)key_a.b.p, d_rep + r.cell0,
+                                                   ScoreIt(hit + r.start, ExScoreOfHit{S, S.cnt1 ? S.cnt1 + r.row : nullptr}),
+                                                   d_val + r.cell0, runs.b.p, hipcub::Sum(), (size_t)r.len, c->stream));
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->ex_ms[3] = ms_since(t0);
+
+  /* ---- copy-out ---- */
+  if (!on_device && cells) {
+    t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipMemcpyAsync(rep_out, d_rep, (size_t)cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(value_out, d_val, (size_t)cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->ex_ms[4] = ms_since(t0);
+  }
+  return CMPR_OK;
+}
+
+/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
+template <typename F>
+int guarded(cmpr_context *c, F call)
+{
+  try {
+    return call();
+  } catch (const std::bad_alloc &) {
+    return fail(c, CMPR_ENOMEM, "out of host memory");
+  }
+}
+
+}  // namespace
+
+extern "C" int cmpr_existence_csr(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out,
+                                  uint32_t *repertoire_out, uint64_t *value_out, uint64_t *n_cells_out)
+{
+  return guarded(c, [&] {
+    return existence_impl(c, capacity, row_start_out, repertoire_out, value_out, n_cells_out, false);
+  });
+}
+
+extern "C" int cmpr_existence_csr_device(cmpr_context *c, uint64_t capacity, uint64_t *d_row_start_out,
+                                         uint32_t *d_repertoire_out, uint64_t *d_value_out, uint64_t *n_cells_out)
+{
+  return guarded(c, [&] {
+    return existence_impl(c, capacity, d_row_start_out, d_repertoire_out, d_value_out, n_cells_out, true);
+  });
+}

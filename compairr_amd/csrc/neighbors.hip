@@ -45,6 +45,9 @@
  * row beyond a wave, and for rows beyond LDS 16 bytes each plus the longest of them once plus the radix
  * sort's scratch.  The host variant adds what the device variant is handed: 8 bytes per query for row_start
  * and 4 per edge for the hits.  Everything is freed before the call returns, also when it fails.
+ *
+ * cmpr_neighbor_edges (context.h) hands count, scan and fill -- the rows not ordered -- to a caller inside the
+ * library that orders them its own way (existence.hip).
  */
 #include "context.h"
 
@@ -217,6 +220,77 @@ double ms_since(std::chrono::steady_clock::time_point t0)
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+/* ---- count; scan, census ---- the degrees and the scan's scratch are allocated here; row_start[n1 + 1] is device
+   memory, host_rows (or NULL) receives a copy in the same wait that brings the edge count and the census */
+int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *host_rows)
+{
+  int rc;
+  const uint64_t n1 = c->n1;
+  /* TEST ONLY (tunable "assume_never_overflows"): the pretence is used up by the first launch it meets; it is
+     renewed for the fill step, so that the repeat of either step can be provoked (tests/test_neighbors_gpu.py) */
+  e.pretend_no_redo = c->force_no_redo;
+  for (double &t : c->nb_ms)
+    t = 0;
+  if ((rc = dev_alloc(c, e.degree, (size_t)(n1 + 1)))) return rc;
+  if ((rc = dev_alloc(c, e.census, 5))) return rc;      /* [0..2] the census, [3..4] the list counters */
+  uint32_t *const degree = e.degree.p;
+  hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> wide(degree, U32To64());
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, e.scan_bytes, wide, (unsigned long long *)row_start,
+                                              (size_t)(n1 + 1), c->stream));
+  if ((rc = dev_alloc(c, e.scan_tmp, e.scan_bytes))) return rc;
+
+  auto t0 = std::chrono::steady_clock::now();
+  if ((rc = cmpr_neighbor_step(c, degree, nullptr, nullptr, [&]() -> int {
+         HIP_TRY(c, hipMemsetAsync(degree, 0, (size_t)(n1 + 1) * sizeof(uint32_t), c->stream));
+         return CMPR_OK;
+       })))
+    return rc;
+  c->nb_ms[0] = ms_since(t0);
+
+  t0 = std::chrono::steady_clock::now();
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(e.scan_tmp.p, e.scan_bytes, wide, (unsigned long long *)row_start,
+                                              (size_t)(n1 + 1), c->stream));
+  HIP_TRY(c, hipMemsetAsync(e.census.p, 0, 5 * sizeof(unsigned long long), c->stream));
+  if (n1) {
+    hipLaunchKernelGGL(nb_census_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, degree, n1, e.census.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  unsigned long long total = 0, seen[3] = {0, 0, 0};
+  HIP_TRY(c, hipMemcpyAsync(&total, row_start + n1, sizeof total, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(seen, e.census.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
+  if (host_rows)
+    HIP_TRY(c, hipMemcpyAsync(host_rows, row_start, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->nb_ms[1] = ms_since(t0);
+  e.total = total;
+  e.n_long = seen[1];
+  e.n_big = seen[0] - seen[1];
+  e.longest = seen[2];
+  return CMPR_OK;
+}
+
+/* ---- fill ---- every hit into its row, in the order of arrival */
+int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32_t *hit)
+{
+  int rc;
+  const uint64_t n1 = c->n1;
+  uint32_t *const degree = e.degree.p;
+  if (e.pretend_no_redo) {
+    c->force_no_redo = true;
+    c->usage_pending = false;
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  if ((rc = cmpr_neighbor_step(c, degree, row_start, hit, [&]() -> int {
+         hipLaunchKernelGGL(nb_cursor_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, row_start, degree, n1);
+         HIP_TRY(c, hipGetLastError());
+         return CMPR_OK;
+       })))
+    return rc;
+  c->nb_ms[2] = ms_since(t0);
+  return CMPR_OK;
+}
+
 int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out,
                    uint64_t *n_edges_out, bool on_device)
 {
@@ -236,71 +310,30 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     return fail(c, CMPR_EUNSUPPORTED, "cmpr_neighbors: a routed query set holds part of each row "
                                       "(cmpr_set_queries_routed)");
   const uint64_t n1 = c->n1;
-  /* TEST ONLY (tunable "assume_never_overflows"): the pretence is used up by the first launch it meets; it is
-     renewed for the fill step, so that the repeat of either step can be provoked (tests/test_neighbors_gpu.py) */
-  const bool pretend_no_redo = c->force_no_redo;
-  for (double &t : c->nb_ms)
-    t = 0;
 
-  /* ---- count ---- */
-  Tmp<uint32_t> degree;
-  Tmp<uint64_t> rows;
-  Tmp<unsigned long long> census;
-  Tmp<char> scan_tmp;
-  if ((rc = dev_alloc(c, degree.b, (size_t)(n1 + 1)))) return rc;
-  if ((rc = dev_alloc(c, census.b, 5))) return rc;      /* [0..2] the census, [3..4] the list counters */
+  NeighborEdges e;
   uint64_t *row_start = on_device ? row_start_out : nullptr;
   if (!row_start) {
-    if ((rc = dev_alloc(c, rows.b, (size_t)(n1 + 1)))) return rc;
-    row_start = rows.b.p;
+    if ((rc = dev_alloc(c, e.row_start, (size_t)(n1 + 1)))) return rc;
+    row_start = e.row_start.p;
   }
-  hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> wide(degree.b.p, U32To64());
-  size_t scan_bytes = 0;
-  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, wide, (unsigned long long *)row_start,
-                                              (size_t)(n1 + 1), c->stream));
-  if ((rc = dev_alloc(c, scan_tmp.b, scan_bytes))) return rc;
-
-  auto t0 = std::chrono::steady_clock::now();
-  if ((rc = cmpr_neighbor_step(c, degree.b.p, nullptr, nullptr, [&]() -> int {
-         HIP_TRY(c, hipMemsetAsync(degree.b.p, 0, (size_t)(n1 + 1) * sizeof(uint32_t), c->stream));
-         return CMPR_OK;
-       })))
+  if ((rc = nb_count(c, e, row_start, on_device ? nullptr : row_start_out)))
     return rc;
-  c->nb_ms[0] = ms_since(t0);
-
-  /* ---- scan, census ---- */
-  t0 = std::chrono::steady_clock::now();
-  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(scan_tmp.b.p, scan_bytes, wide, (unsigned long long *)row_start,
-                                              (size_t)(n1 + 1), c->stream));
-  HIP_TRY(c, hipMemsetAsync(census.b.p, 0, 5 * sizeof(unsigned long long), c->stream));
-  if (n1) {
-    hipLaunchKernelGGL(nb_census_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, degree.b.p, n1,
-                       census.b.p);
-    HIP_TRY(c, hipGetLastError());
-  }
-  unsigned long long total = 0, seen[3] = {0, 0, 0};
-  HIP_TRY(c, hipMemcpyAsync(&total, row_start + n1, sizeof total, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(seen, census.b.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
-  if (!on_device && row_start_out)
-    HIP_TRY(c, hipMemcpyAsync(row_start_out, row_start, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                              c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->nb_ms[1] = ms_since(t0);
+  const uint64_t total = e.total;
   *n_edges_out = total;
   /* degrees only, nothing to list, or no room for it: row_start says what to allocate */
   if (!hit_out || total == 0 || total > capacity)
     return CMPR_OK;
 
-  /* ---- fill ---- */
-  const uint64_t n_long = seen[1], n_big = seen[0] - seen[1], longest = seen[2];
-  Tmp<uint32_t> hits, big_rows, scratch;
+  const uint64_t n_long = e.n_long, n_big = e.n_big, longest = e.longest;
+  Tmp<uint32_t> big_rows, scratch;
   Tmp<unsigned long long> long_desc;
   Tmp<char> sort_tmp;
   size_t sort_bytes = 0;
   uint32_t *hit = on_device ? hit_out : nullptr;
   if (!hit) {
-    if ((rc = dev_alloc(c, hits.b, (size_t)total))) return rc;
-    hit = hits.b.p;
+    if ((rc = dev_alloc(c, e.hit, (size_t)total))) return rc;
+    hit = e.hit.p;
   }
   if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
   if (n_long) {
@@ -310,23 +343,12 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
                                                  (size_t)longest, 0, 32, c->stream));
     if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
   }
-  if (pretend_no_redo) {
-    c->force_no_redo = true;
-    c->usage_pending = false;
-  }
-  t0 = std::chrono::steady_clock::now();
-  if ((rc = cmpr_neighbor_step(c, degree.b.p, row_start, hit, [&]() -> int {
-         hipLaunchKernelGGL(nb_cursor_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, row_start,
-                            degree.b.p, n1);
-         HIP_TRY(c, hipGetLastError());
-         return CMPR_OK;
-       })))
+  if ((rc = nb_fill(c, e, row_start, hit)))
     return rc;
-  c->nb_ms[2] = ms_since(t0);
 
   /* ---- order the rows ---- */
-  t0 = std::chrono::steady_clock::now();
-  unsigned long long *list_ctr = census.b.p + 3;       /* (zero since the census) */
+  auto t0 = std::chrono::steady_clock::now();
+  unsigned long long *list_ctr = e.census.p + 3;       /* (zero since the census) */
   hipLaunchKernelGGL(nb_sort_short_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, row_start, hit, n1,
                      big_rows.b.p, n_big, long_desc.b.p, n_long, list_ctr);
   HIP_TRY(c, hipGetLastError());
@@ -370,6 +392,17 @@ int guarded(cmpr_context *c, F call)
 }
 
 }  // namespace
+
+int cmpr_neighbor_edges(cmpr_context *c, NeighborEdges &e)
+{
+  int rc;
+  if ((rc = dev_alloc(c, e.row_start, (size_t)(c->n1 + 1)))) return rc;
+  if ((rc = nb_count(c, e, e.row_start.p, nullptr))) return rc;
+  if (e.total == 0)
+    return CMPR_OK;
+  if ((rc = dev_alloc(c, e.hit, (size_t)e.total))) return rc;
+  return nb_fill(c, e, e.row_start.p, e.hit.p);
+}
 
 extern "C" int cmpr_neighbors(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out,
                               uint64_t *n_edges_out)

@@ -30,6 +30,7 @@ EXPORTS = [
     "cmpr_deduplicate", "cmpr_deduplicate_device",
     "cmpr_cluster", "cmpr_cluster_device",
     "cmpr_neighbors", "cmpr_neighbors_device",
+    "cmpr_existence_csr", "cmpr_existence_csr_device",
 ]
 
 
@@ -157,6 +158,10 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "cmpr_neighbors"):
         lib.cmpr_neighbors.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         lib.cmpr_neighbors_device.argtypes = lib.cmpr_neighbors.argtypes
+    if hasattr(lib, "cmpr_existence_csr"):         # (likewise: tools/existence_timing.py --against)
+        lib.cmpr_existence_csr.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_uint64)]
+        lib.cmpr_existence_csr_device.argtypes = lib.cmpr_existence_csr.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -404,6 +409,36 @@ class HipOverlap:
                                                     C.c_void_p(d_hits or None), C.byref(n)))
         return n.value
 
+    # ---- the -x table as CSR (include/compairr_hip.h: cmpr_existence_csr*) ----
+
+    def existence_csr(self):
+        """(row_start uint64[n1 + 1], repertoire uint32[C], value uint64[C]) of the resident sets: the nonzero
+        cells of the per-sequence table -- row i of overlap_matrix() on a context with existence=True -- are
+        repertoire[row_start[i]:row_start[i + 1]], in increasing order, with their values beside them.  Works on
+        a context without `existence`, which never holds the dense table.  One count-only call, then one with
+        the exact capacity."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_existence_csr(self._ctx, 0, None, None, None, C.byref(n)))
+        row_start = np.zeros(self._queries() + 1, dtype=np.uint64)
+        repertoire = np.zeros(n.value, dtype=np.uint32)
+        value = np.zeros(n.value, dtype=np.uint64)
+        self._check(self._lib.cmpr_existence_csr(self._ctx, n.value, row_start.ctypes.data,
+                                                 repertoire.ctypes.data if n.value else None,
+                                                 value.ctypes.data if n.value else None, C.byref(n)))
+        assert n.value == len(repertoire)
+        return row_start, repertoire, value
+
+    def existence_csr_device(self, capacity: int = 0, d_row_start: int = 0, d_repertoire: int = 0,
+                             d_value: int = 0) -> int:
+        """The same into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted), d_repertoire
+        (uint32[capacity]) and d_value (uint64[capacity]; both 0 with capacity 0: count only).  Returns the
+        number of cells; when it exceeds `capacity` nothing was written to the two cell arrays."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_existence_csr_device(self._ctx, capacity, C.c_void_p(d_row_start or None),
+                                                        C.c_void_p(d_repertoire or None),
+                                                        C.c_void_p(d_value or None), C.byref(n)))
+        return n.value
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -465,3 +500,14 @@ def neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: 
         h.set_reference(set2, set1.longest)
         h.set_queries(set1)
         return h.neighbors()
+
+
+def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
+    """Convenience: (row_start, repertoire, value) of set1 against set2 under `opt` (HipOverlap.existence_csr) on
+    a context of its own.  `tunables` are set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        h.set_reference(set2, set1.longest)
+        h.set_queries(set1)
+        return h.existence_csr()

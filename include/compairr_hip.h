@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_existence_csr*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -323,6 +323,60 @@ int cmpr_neighbors_device(cmpr_context *ctx, uint64_t capacity,
                           uint64_t *d_row_start_out, uint32_t *d_hit_out, uint64_t *n_edges_out);
 
 /*
+ * The -x table without its zeros: per query, the set-2 repertoires it has a match in and the cell's value, as CSR.
+ * The rows are the n1 sequences of the last cmpr_set_queries*(), in input order, WHATEVER options.existence is: a
+ * context created with existence = 0 never allocates the n1 x R2 matrix and is the intended caller; one created
+ * with existence = 1 gives the same answer.
+ *   row_start_out[n1 + 1]    row_start[0] == 0, row_start[i + 1] - row_start[i] = the number of cells of row i.
+ *                            Always written in full and always exact, whatever `capacity` is.  May be NULL when
+ *                            only *n_cells_out is wanted.
+ *   repertoire_out[capacity] row i occupies [row_start[i], row_start[i + 1]): set-2 repertoire numbers in strictly
+ *                            increasing order.
+ *   value_out[capacity]      beside each: exactly the integer that cell (i, r) of cmpr_overlap_matrix() holds on a
+ *                            context with options.existence = 1 and otherwise the same options -- the sums listed
+ *                            there (mean as count1 + count2, 1 per pair with ignore_counts; uint64 arithmetic,
+ *                            which wraps as the matrix's does).
+ *                            A cell is listed if and only if at least one verified pair falls in it (a cell whose
+ *                            sum wraps to zero is listed with 0), the (i, i) pair included when one set is resident
+ *                            as both; the call filters nothing.  When there are more cells than `capacity`, NOTHING
+ *                            is written to the two cell arrays: the call still returns CMPR_OK with
+ *                            *n_cells_out > capacity, and row_start says what to allocate.  capacity == 0 with both
+ *                            arrays NULL is the count-only call.  capacity > 0 with either array NULL is
+ *                            CMPR_EINVAL.  Elements behind the last cell are not the call's to write.
+ *   *n_cells_out             required (NULL: CMPR_EINVAL), a HOST pointer in both variants; == row_start[n1].
+ * cmpr_existence_csr_device() takes the three arrays as device memory on the context's device and writes only the
+ * elements named above; only the cell count crosses PCIe.
+ *
+ * Results are bit-identical from run to run, under every tunable, and with set 2 indexed in parts: a cell is a sum
+ * of integers over the row's hits in one repertoire, and the cells of a row are in order.  The call is a pass over
+ * the neighbour rows (compairr_amd/csrc/existence.hip): the count step, the sum and the fill step of
+ * cmpr_neighbors() into temporaries, each row sorted in place by (repertoire of the hit, hit) -- by a lane, a wave,
+ * a workgroup in LDS or the device-wide radix sort, by its number of hits --, the cells per row counted and summed
+ * into row_start, and, only when the cells fit `capacity`, each run of equal repertoires reduced to its cell.  The
+ * count-only call runs everything but that reduction.  cmpr_get_stats() afterwards describes the last step the call
+ * ran (cmpr_stats.matches = the number of edges).
+ *
+ * Device memory for the duration of the call, unlike the dense path PER EDGE: 4 bytes per edge; per query 4 bytes
+ * (degrees, then cells per row), 8 (row offsets of the edges) and 8 for the queries' counts (not with
+ * ignore_counts); the scratch of the sums; 4 bytes per row of more than 64 hits; and for rows of more than 8192
+ * hits 24 bytes each, 12 times the longest of them, and the scratch of its sort and reduction.  The host variant
+ * adds what the device variant is handed: 8 bytes per query and 12 per cell.  Everything is freed before the call
+ * returns, also when it fails.
+ *
+ * Synchronous; needs both resident sets (CMPR_ESTATE as for cmpr_overlap_matrix()).  CMPR_SCORE_RATIO (without
+ * ignore_counts) is not an integer sum: CMPR_EINVAL, use cmpr_overlap_matrix_f64().  With the tunable
+ * work_shard_count above 1, and after cmpr_set_queries_routed(), the call is CMPR_EUNSUPPORTED: such a context holds
+ * part of each row.  The resident sets, the plan and the other entry points are as usable afterwards as before; the
+ * call may be repeated.  An empty query set is CMPR_OK with row_start == {0} and no cells.
+ */
+int cmpr_existence_csr(cmpr_context *ctx, uint64_t capacity,
+                       uint64_t *row_start_out, uint32_t *repertoire_out, uint64_t *value_out,
+                       uint64_t *n_cells_out);
+int cmpr_existence_csr_device(cmpr_context *ctx, uint64_t capacity,
+                              uint64_t *d_row_start_out, uint32_t *d_repertoire_out, uint64_t *d_value_out,
+                              uint64_t *n_cells_out);
+
+/*
  * Exact duplicates inside one set: the number the reference reports as
  * "Warning: N duplicates detected in repertoire set K" -- sequences that repeat
  * an earlier one of the same repertoire with the same V, J (unless
@@ -554,7 +608,12 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    "never_overflows" (1: the redo pass is currently dropped) and, of the last
    cmpr_set_queries* / cmpr_route_queries in microseconds, "layout_total_us",
    "layout_upload_us" (host time inside the copy calls) and "layout_tail_us" (from the
-   last copy to the end: the device work the upload did not hide). */
+   last copy to the end: the device work the upload did not hide); host times of the parts of the last
+   cmpr_neighbors*() in microseconds, each part ending in a wait: "neighbors_count_us", "neighbors_scan_us",
+   "neighbors_fill_us", "neighbors_order_us" (a cmpr_existence_csr*() call sets the first three and zeroes the
+   fourth); and of the last cmpr_existence_csr*(): "existence_edges_us" (those three together),
+   "existence_group_us" (rows sorted by repertoire, cells per row), "existence_count_us" (their sum, the cell count
+   to the host), "existence_reduce_us" (the cells; 0 when they did not fit) and "existence_copy_us" (host variant). */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

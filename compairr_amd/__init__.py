@@ -8,7 +8,8 @@ no compute path of its own and no CPU fallback.
 """
 
 from .sets import RepertoireSet  # noqa: F401
-from .hip import HipOverlap, HipError, Options, Stats, cluster, deduplicate, existence_csr, library_path, neighbors  # noqa: F401
+from .hip import (HipOverlap, HipError, Options, Stats, cluster, cluster_table, deduplicate, existence_csr,  # noqa: F401
+                  library_path, neighbors)
 
-__all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "deduplicate",
+__all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "cluster_table", "deduplicate",
            "existence_csr", "library_path", "neighbors"]

@@ -19,9 +19,39 @@
  * Device memory beyond the resident sets: the forest (4 bytes per sequence; once the labels are flat it is
  * reused for the counts unless the caller's size array takes them) and the labels where the caller gave no
  * device array for them (4 bytes per sequence).
+ *
+ * cmpr_cluster_table / cmpr_cluster_table_device: the reference's -c table without the member order of its
+ * sweep -- the clusters numbered by (size descending, smallest member ascending), which is the reference's
+ * cluster_no - 1 (its qsort compares sizes only and the seeds arrive in increasing order, cluster.cc:53-63,
+ * :422), the members of every cluster as CSR, and the summed duplicate_count per cluster.  cluster_links()
+ * is the path above up to "labels and sizes flat on the device", shared by both calls; the table pass starts
+ * from those two arrays and the two words the host needs, K (the roots) and the largest size:
+ *
+ *   roots    the i with label[i] == i in increasing i (hipcub DeviceSelect over a counting iterator: it keeps
+ *            the order, so the tie-break needs no key bits); table_key_kernel: key = largest - size
+ *   order    hipcub's stable LSD radix sort of (key -> root) over the K roots and the bitlen(largest - 1)
+ *            bits the keys have
+ *   number   table_number_kernel: number[root] = rank, in the words of the size array (read for the last time
+ *            by the keys); cluster_start = the exclusive 64-bit sum of the K sorted sizes and a zero (hipcub);
+ *            table_of_kernel: cluster_of[i] = number[label[i]], and label[i] = i for the next sort
+ *   members  the stable sort of (cluster_of -> i) over bitlen(K - 1) bits, straight into the member array:
+ *            increasing inside a cluster because the sort is stable.  One giant cluster costs a sort nothing
+ *   counts   table_count_kernel over the members in table order: count[member[p]] of the reference's counts
+ *            (context.h cnt2: the set is resident), the run of one cluster summed inside the wave, one 64-bit
+ *            add per run and wave.  With ignore_counts the sorted sizes, widened (table_sizes_kernel)
+ *
+ * Device memory of the table pass beyond cmpr_cluster's 8 bytes per sequence, whose two arrays it reuses (the
+ * sizes become the numbers and then the sorted keys, the labels the sequence numbers): per sequence 4 bytes
+ * each for cluster_of and the members where the caller gave no device array, and the radix sort's scratch
+ * (hipcub: a second pair of arrays, 8 bytes, and its histograms); per cluster 16 bytes (roots and keys,
+ * before and behind their sort), 8 for cluster_start and 8 for the counts in the host variant.
  */
 #include "context.h"
 
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <chrono>
 #include <new>
 
 using namespace cmpr;
@@ -104,8 +134,19 @@ cluster_gather_kernel(const uint32_t *label, const uint32_t *cnt, uint32_t *size
     size[i] = cnt[label[i]];
 }
 
-int cluster_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *label_out,
-                 uint32_t *size_out, uint64_t *n_clusters_out)
+/* What cmpr_cluster and cmpr_cluster_table share: the refusals, the set as both sets, the link step, the
+   flat labels and (want_size) the sizes, all queued on the context's stream and NOT waited for.  d_label,
+   d_size: device arrays of the caller's to take them, or NULL -- the labels then go to an array of L's, the
+   sizes to where the forest was.  n == 0 leaves L.n == 0 and nothing queued. */
+struct Links {
+  Tmp<uint32_t> parent, labels;
+  Tmp<unsigned long long> roots;
+  uint32_t *label = nullptr, *size = nullptr;
+  uint64_t n = 0;
+};
+
+int cluster_links(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *d_label, uint32_t *d_size,
+                  bool want_size, uint64_t *n_clusters_out, Links &L)
 {
   if (!c)
     return CMPR_EINVAL;
@@ -128,44 +169,311 @@ int cluster_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32
     return CMPR_OK;
   HIP_TRY(c, hipSetDevice(c->device));
 
-  Tmp<uint32_t> parent, labels;
-  Tmp<unsigned long long> roots;
-  if ((rc = dev_alloc(c, parent.b, (size_t)n))) return rc;
-  if ((rc = dev_alloc(c, roots.b, 1))) return rc;
-  uint32_t *label = on_device ? label_out : nullptr;
+  if ((rc = dev_alloc(c, L.parent.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, L.roots.b, 1))) return rc;
+  uint32_t *label = d_label;
   if (!label) {
-    if ((rc = dev_alloc(c, labels.b, (size_t)n))) return rc;
-    label = labels.b.p;
+    if ((rc = dev_alloc(c, L.labels.b, (size_t)n))) return rc;
+    label = L.labels.b.p;
   }
+  uint32_t *const parent = L.parent.b.p;
   const dim3 grid((uint32_t)((n + CLUSTER_WG - 1) / CLUSTER_WG)), wg(CLUSTER_WG);
 
   /* once, before the step: its repeats and its redo pass only add links that are already implied */
-  hipLaunchKernelGGL(cluster_init_kernel, grid, wg, 0, c->stream, parent.b.p, n);
+  hipLaunchKernelGGL(cluster_init_kernel, grid, wg, 0, c->stream, parent, n);
   HIP_TRY(c, hipGetLastError());
-  if ((rc = cmpr_link_step(c, parent.b.p)))
+  if ((rc = cmpr_link_step(c, parent)))
     return rc;
 
-  HIP_TRY(c, hipMemsetAsync(roots.b.p, 0, sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(cluster_flatten_kernel, grid, wg, 0, c->stream, parent.b.p, label, n, roots.b.p);
+  HIP_TRY(c, hipMemsetAsync(L.roots.b.p, 0, sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(cluster_flatten_kernel, grid, wg, 0, c->stream, parent, label, n, L.roots.b.p);
   HIP_TRY(c, hipGetLastError());
-  if (size_out) {
+  if (want_size) {
     /* the counts go where the sizes will be (a device array of the caller) or where the forest was */
-    uint32_t *cnt = on_device ? size_out : parent.b.p;
+    uint32_t *cnt = d_size ? d_size : parent;
     HIP_TRY(c, hipMemsetAsync(cnt, 0, n * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(cluster_count_kernel, grid, wg, 0, c->stream, label, cnt, n);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(cluster_gather_kernel, grid, wg, 0, c->stream, label, cnt, cnt, n);
     HIP_TRY(c, hipGetLastError());
-    if (!on_device)
-      HIP_TRY(c, hipMemcpyAsync(size_out, cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    L.size = cnt;
   }
+  L.label = label;
+  L.n = n;
+  return CMPR_OK;
+}
+
+int cluster_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *label_out,
+                 uint32_t *size_out, uint64_t *n_clusters_out)
+{
+  Links L;
+  int rc;
+  if ((rc = cluster_links(c, s, on_device, on_device ? label_out : nullptr, on_device ? size_out : nullptr,
+                          size_out != nullptr, n_clusters_out, L)))
+    return rc;
+  const uint64_t n = L.n;
+  if (n == 0)
+    return CMPR_OK;
+  if (!on_device && size_out)
+    HIP_TRY(c, hipMemcpyAsync(size_out, L.size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   if (!on_device && label_out)
-    HIP_TRY(c, hipMemcpyAsync(label_out, label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(label_out, L.label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   unsigned long long clusters = 0;
-  HIP_TRY(c, hipMemcpyAsync(&clusters, roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (n_clusters_out)
     *n_clusters_out = clusters;
+  return CMPR_OK;
+}
+
+/* ---- the table pass ---- */
+
+struct IsRoot {
+  const uint32_t *label;
+  __host__ __device__ bool operator()(uint32_t i) const { return label[i] == i; }
+};
+
+/* the size of cluster k from its sorted key; a zero behind the last, so that the sum's last word is n */
+struct SizeAt {
+  const uint32_t *key_sorted;
+  uint64_t K;
+  uint32_t largest;
+  __host__ __device__ unsigned long long operator()(uint64_t k) const { return k < K ? largest - key_sorted[k] : 0u; }
+};
+
+__global__ void __launch_bounds__(CLUSTER_WG)
+table_key_kernel(const uint32_t *root, const uint32_t *size, uint32_t largest, uint32_t *key, uint64_t K)
+{
+  const uint64_t k = (uint64_t)blockIdx.x * CLUSTER_WG + threadIdx.x;
+  if (k < K)
+    key[k] = largest - size[root[k]];
+}
+
+__global__ void __launch_bounds__(CLUSTER_WG)
+table_number_kernel(const uint32_t *root_sorted, uint32_t *number, uint64_t K)
+{
+  const uint64_t r = (uint64_t)blockIdx.x * CLUSTER_WG + threadIdx.x;
+  if (r < K)
+    number[root_sorted[r]] = (uint32_t)r;
+}
+
+/* label[i] is read and then overwritten by its own lane only: the labels become the values of the next sort */
+__global__ void __launch_bounds__(CLUSTER_WG)
+table_of_kernel(uint32_t *label, const uint32_t *number, uint32_t *cluster_of, uint64_t n)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * CLUSTER_WG + threadIdx.x;
+  if (i < n) {
+    cluster_of[i] = number[label[i]];
+    label[i] = (uint32_t)i;
+  }
+}
+
+__global__ void __launch_bounds__(CLUSTER_WG)
+table_sizes_kernel(const uint32_t *key_sorted, uint32_t largest, unsigned long long *count, uint64_t K)
+{
+  const uint64_t k = (uint64_t)blockIdx.x * CLUSTER_WG + threadIdx.x;
+  if (k < K)
+    count[k] = largest - key_sorted[k];
+}
+
+/* count[cluster] += cnt[member] over the members in table order.  The members of a cluster are neighbours now:
+   a run of lanes with one cluster is summed inside the wave (every lane takes what lies `off` lanes above it
+   while that is still inside its run; after six rounds the run's first lane holds the run's sum) and added
+   once.  Integer sums: the order of the adds does not show. */
+__global__ void __launch_bounds__(CLUSTER_WG)
+table_count_kernel(const uint32_t *cluster_at, const uint32_t *member, const uint64_t *cnt,
+                   unsigned long long *count, uint64_t n)
+{
+  const uint64_t p = (uint64_t)blockIdx.x * CLUSTER_WG + threadIdx.x;
+  const uint32_t lane = lane_id();
+  const bool valid = p < n;
+  const uint32_t mine = valid ? cluster_at[p] : 0u;
+  unsigned long long v = valid ? cnt[member[p]] : 0ull;
+  const uint32_t prev = __shfl_up(mine, 1, WAVE);
+  const bool head = valid && (lane == 0 || prev != mine);
+  const uint64_t heads = __ballot(head), valids = __ballot(valid);
+  /* the lane's run ends before the next head, or with the last valid lane */
+  const uint64_t above = lane == WAVE - 1 ? 0ull : heads >> (lane + 1);
+  const uint32_t end = above ? lane + 1 + (uint32_t)__ffsll((unsigned long long)above) - 1
+                             : (uint32_t)__popcll(valids);
+  for (uint32_t off = 1; off < WAVE; off <<= 1) {
+    const unsigned long long other = __shfl_down(v, off, WAVE);
+    if (lane + off < end)
+      v += other;
+  }
+  if (head)
+    atomicAdd(count + mine, v);
+}
+
+uint32_t grid_for(uint64_t n)
+{
+  return (uint32_t)((n + CLUSTER_WG - 1) / CLUSTER_WG);
+}
+
+double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int bit_length(uint64_t x)
+{
+  return x ? 64 - __builtin_clzll(x) : 0;
+}
+
+int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *cluster_of_out,
+               uint64_t *cluster_start_out, uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out)
+{
+  auto t0 = std::chrono::steady_clock::now();
+  if (c)
+    c->cl_ms[0] = c->cl_ms[1] = 0;
+  Links L;
+  int rc;
+  if ((rc = cluster_links(c, s, on_device, nullptr, nullptr, true, n_clusters_out, L)))
+    return rc;
+  const uint64_t n = L.n;
+  if (n == 0) {
+    if (cluster_start_out && on_device) {
+      HIP_TRY(c, hipSetDevice(c->device));
+      HIP_TRY(c, hipMemsetAsync(cluster_start_out, 0, sizeof(uint64_t), c->stream));
+      HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (cluster_start_out) {
+      cluster_start_out[0] = 0;
+    }
+    return CMPR_OK;
+  }
+
+  /* ---- the two words the host needs: the number of roots, the largest size ---- */
+  Tmp<uint32_t> largest_word;
+  Tmp<char> scratch;
+  size_t scratch_bytes = 0;
+  if ((rc = dev_alloc(c, largest_word.b, 1))) return rc;
+  HIP_TRY(c, hipcub::DeviceReduce::Max(nullptr, scratch_bytes, (const uint32_t *)L.size, largest_word.b.p, n, c->stream));
+  if ((rc = dev_alloc(c, scratch.b, scratch_bytes))) return rc;
+  HIP_TRY(c, hipcub::DeviceReduce::Max(scratch.b.p, scratch_bytes, (const uint32_t *)L.size, largest_word.b.p, n, c->stream));
+  unsigned long long clusters = 0;
+  uint32_t largest = 0;
+  HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&largest, largest_word.b.p, sizeof largest, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->cl_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  const uint64_t K = clusters;
+  if (K == 0 || K > n || largest == 0 || largest > n)
+    return fail(c, CMPR_EDEVICE, "cmpr_cluster_table: the labels and sizes do not describe a partition");
+  if (n_clusters_out)
+    *n_clusters_out = K;
+
+  /* what has to be made for what was asked for */
+  const bool sum_counts = count_out && !c->opt.ignore_counts;
+  const bool want_members = member_out || sum_counts;
+  const bool want_of = cluster_of_out || want_members;
+  if (!want_of && !cluster_start_out && !count_out)
+    return CMPR_OK;
+  if (sum_counts && !c->cnt2.p)
+    return fail(c, CMPR_ESTATE, "cmpr_cluster_table: the resident set has no counts");
+
+  Tmp<uint32_t> root, key, root_sorted, key_sorted, of_tmp, member_tmp;
+  Tmp<uint64_t> start_tmp, count_tmp;
+  Tmp<unsigned long long> selected;      /* DeviceSelect's count, never read: K is the flatten kernel's */
+  if ((rc = dev_alloc(c, root.b, (size_t)K))) return rc;
+  if ((rc = dev_alloc(c, key.b, (size_t)K))) return rc;
+  if ((rc = dev_alloc(c, root_sorted.b, (size_t)K))) return rc;
+  if ((rc = dev_alloc(c, key_sorted.b, (size_t)K))) return rc;
+  if ((rc = dev_alloc(c, selected.b, 1))) return rc;
+  uint32_t *cluster_of = on_device ? cluster_of_out : nullptr, *member = on_device ? member_out : nullptr;
+  unsigned long long *cluster_start = on_device ? (unsigned long long *)cluster_start_out : nullptr;
+  unsigned long long *count = on_device ? (unsigned long long *)count_out : nullptr;
+  if (want_of && !cluster_of) {
+    if ((rc = dev_alloc(c, of_tmp.b, (size_t)n))) return rc;
+    cluster_of = of_tmp.b.p;
+  }
+  if (want_members && !member) {
+    if ((rc = dev_alloc(c, member_tmp.b, (size_t)n))) return rc;
+    member = member_tmp.b.p;
+  }
+  if (cluster_start_out && !cluster_start) {
+    if ((rc = dev_alloc(c, start_tmp.b, (size_t)(K + 1)))) return rc;
+    cluster_start = (unsigned long long *)start_tmp.b.p;
+  }
+  if (count_out && !count) {
+    if ((rc = dev_alloc(c, count_tmp.b, (size_t)K))) return rc;
+    count = (unsigned long long *)count_tmp.b.p;
+  }
+
+  /* one scratch buffer for the four hipcub calls, which run one after the other */
+  const int size_bits = std::max(1, bit_length(largest - 1)), number_bits = std::max(1, bit_length(K - 1));
+  const hipcub::CountingInputIterator<uint32_t> numbers(0);
+  const hipcub::TransformInputIterator<unsigned long long, SizeAt, hipcub::CountingInputIterator<uint64_t>>
+      sorted_sizes(hipcub::CountingInputIterator<uint64_t>(0), SizeAt{key_sorted.b.p, K, largest});
+  size_t select_bytes = 0, order_bytes = 0, scan_bytes = 0, member_bytes = 0;
+  HIP_TRY(c, hipcub::DeviceSelect::If(nullptr, select_bytes, numbers, root.b.p, selected.b.p, (int64_t)n,
+                                      IsRoot{L.label}, c->stream));
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, order_bytes, (const uint32_t *)key.b.p, key_sorted.b.p,
+                                                (const uint32_t *)root.b.p, root_sorted.b.p, (size_t)K, 0, size_bits,
+                                                c->stream));
+  if (cluster_start)
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sorted_sizes, cluster_start, (size_t)(K + 1),
+                                                c->stream));
+  if (want_members)
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, member_bytes, (const uint32_t *)cluster_of, L.size,
+                                                  (const uint32_t *)L.label, member, (size_t)n, 0, number_bits,
+                                                  c->stream));
+  scratch_bytes = std::max(std::max(select_bytes, order_bytes), std::max(scan_bytes, member_bytes));
+  if ((rc = dev_alloc(c, scratch.b, scratch_bytes))) return rc;
+
+  /* ---- roots and keys; the cluster order ---- */
+  HIP_TRY(c, hipcub::DeviceSelect::If(scratch.b.p, select_bytes, numbers, root.b.p, selected.b.p, (int64_t)n,
+                                      IsRoot{L.label}, c->stream));
+  hipLaunchKernelGGL(table_key_kernel, dim3(grid_for(K)), dim3(CLUSTER_WG), 0, c->stream, root.b.p, L.size, largest,
+                     key.b.p, K);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, order_bytes, (const uint32_t *)key.b.p, key_sorted.b.p,
+                                                (const uint32_t *)root.b.p, root_sorted.b.p, (size_t)K, 0, size_bits,
+                                                c->stream));
+
+  /* ---- numbering ---- */
+  if (cluster_start)
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(scratch.b.p, scan_bytes, sorted_sizes, cluster_start, (size_t)(K + 1),
+                                                c->stream));
+  if (want_of) {
+    uint32_t *const number = L.size;             /* (the keys have read the sizes: their words are free) */
+    hipLaunchKernelGGL(table_number_kernel, dim3(grid_for(K)), dim3(CLUSTER_WG), 0, c->stream, root_sorted.b.p, number, K);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(table_of_kernel, dim3(grid_for(n)), dim3(CLUSTER_WG), 0, c->stream, L.label, number, cluster_of, n);
+    HIP_TRY(c, hipGetLastError());
+  }
+
+  /* ---- members: (cluster_of -> i), stable; the sorted keys (the cluster at every place) take the numbers' words ---- */
+  if (want_members)
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, member_bytes, (const uint32_t *)cluster_of, L.size,
+                                                  (const uint32_t *)L.label, member, (size_t)n, 0, number_bits,
+                                                  c->stream));
+
+  /* ---- counts ---- */
+  if (sum_counts) {
+    HIP_TRY(c, hipMemsetAsync(count, 0, (size_t)K * sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(table_count_kernel, dim3(grid_for(n)), dim3(CLUSTER_WG), 0, c->stream, L.size, member,
+                       c->cnt2.p, count, n);
+    HIP_TRY(c, hipGetLastError());
+  } else if (count) {
+    hipLaunchKernelGGL(table_sizes_kernel, dim3(grid_for(K)), dim3(CLUSTER_WG), 0, c->stream, key_sorted.b.p, largest,
+                       count, K);
+    HIP_TRY(c, hipGetLastError());
+  }
+
+  if (!on_device) {
+    if (cluster_of_out)
+      HIP_TRY(c, hipMemcpyAsync(cluster_of_out, cluster_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (cluster_start_out)
+      HIP_TRY(c, hipMemcpyAsync(cluster_start_out, cluster_start, (size_t)(K + 1) * sizeof(uint64_t),
+                                hipMemcpyDeviceToHost, c->stream));
+    if (member_out)
+      HIP_TRY(c, hipMemcpyAsync(member_out, member, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (count_out)
+      HIP_TRY(c, hipMemcpyAsync(count_out, count, (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->cl_ms[1] = ms_since(t0);
   return CMPR_OK;
 }
 
@@ -192,4 +500,22 @@ extern "C" int cmpr_cluster_device(cmpr_context *c, const cmpr_set_view *d_set, 
                                    uint32_t *d_size_out, uint64_t *n_clusters_out)
 {
   return guarded(c, [&] { return cluster_impl(c, d_set, true, d_label_out, d_size_out, n_clusters_out); });
+}
+
+extern "C" int cmpr_cluster_table(cmpr_context *c, const cmpr_set_view *set, uint32_t *cluster_of_out,
+                                  uint64_t *cluster_start_out, uint32_t *member_out, uint64_t *count_out,
+                                  uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    return table_impl(c, set, false, cluster_of_out, cluster_start_out, member_out, count_out, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_cluster_table_device(cmpr_context *c, const cmpr_set_view *d_set, uint32_t *d_cluster_of_out,
+                                         uint64_t *d_cluster_start_out, uint32_t *d_member_out, uint64_t *d_count_out,
+                                         uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    return table_impl(c, d_set, true, d_cluster_of_out, d_cluster_start_out, d_member_out, d_count_out, n_clusters_out);
+  });
 }

@@ -478,6 +478,8 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "existence_count_us") *value = (int64_t)(c->ex_ms[2] * 1e3);
   else if (n == "existence_reduce_us") *value = (int64_t)(c->ex_ms[3] * 1e3);
   else if (n == "existence_copy_us") *value = (int64_t)(c->ex_ms[4] * 1e3);
+  else if (n == "cluster_links_us") *value = (int64_t)(c->cl_ms[0] * 1e3);
+  else if (n == "cluster_table_us") *value = (int64_t)(c->cl_ms[1] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
   else if (n == "heavy_buckets") {
     *value = 0;

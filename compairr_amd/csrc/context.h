@@ -344,6 +344,7 @@ struct cmpr_context {
   const uint64_t     *nb_row_start = nullptr;
   double              nb_ms[4] = {};   /* host time of the last cmpr_neighbors: count | scan | fill | order */
   double              ex_ms[5] = {};   /* ... of the last cmpr_existence_csr: edges | group | count | reduce | copy-out */
+  double              cl_ms[2] = {};   /* ... of the last cmpr_cluster_table: labels and sizes | the table */
 };
 
 

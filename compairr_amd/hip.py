@@ -31,6 +31,7 @@ EXPORTS = [
     "cmpr_cluster", "cmpr_cluster_device",
     "cmpr_neighbors", "cmpr_neighbors_device",
     "cmpr_existence_csr", "cmpr_existence_csr_device",
+    "cmpr_cluster_table", "cmpr_cluster_table_device",
 ]
 
 
@@ -162,6 +163,10 @@ def load_library() -> C.CDLL:
         lib.cmpr_existence_csr.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(C.c_uint64)]
         lib.cmpr_existence_csr_device.argtypes = lib.cmpr_existence_csr.argtypes
+    if hasattr(lib, "cmpr_cluster_table"):         # (likewise: tools/cluster_table_timing.py --against)
+        lib.cmpr_cluster_table.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.cmpr_cluster_table_device.argtypes = lib.cmpr_cluster_table.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -385,6 +390,36 @@ class HipOverlap:
                                                   C.c_void_p(d_size or None), C.byref(clusters)))
         return clusters.value
 
+    # ---- the clusters numbered and grouped (include/compairr_hip.h: cmpr_cluster_table*) ----
+
+    def cluster_table(self, s: RepertoireSet):
+        """(cluster_of uint32[n], cluster_start uint64[K + 1], members uint32[n], count uint64[K]): the clusters
+        of `s` numbered by (size descending, smallest member ascending) -- the reference's cluster_no - 1 --, the
+        members of cluster k, increasing, in members[cluster_start[k]:cluster_start[k + 1]], and its summed
+        duplicate_count (with ignore_counts its size).  Afterwards `s` is resident as both sets."""
+        v = _view(s)
+        cluster_of = np.zeros(s.n, dtype=np.uint32)
+        cluster_start = np.zeros(s.n + 1, dtype=np.uint64)
+        members = np.zeros(s.n, dtype=np.uint32)
+        count = np.zeros(s.n, dtype=np.uint64)
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_cluster_table(self._ctx, C.byref(v), cluster_of.ctypes.data,
+                                                 cluster_start.ctypes.data, members.ctypes.data, count.ctypes.data,
+                                                 C.byref(clusters)))
+        k = clusters.value
+        return cluster_of, cluster_start[:k + 1].copy(), members, count[:k].copy()
+
+    def cluster_table_device(self, view: _SetView, d_cluster_of: int = 0, d_cluster_start: int = 0,
+                             d_member: int = 0, d_count: int = 0) -> int:
+        """The same for a view of device pointers (device_view), into device arrays: d_cluster_of and d_member
+        (uint32[n]), d_cluster_start (uint64[n + 1], K + 1 written) and d_count (uint64[n], K written); 0: not
+        wanted.  Returns K."""
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_cluster_table_device(
+            self._ctx, C.byref(view), C.c_void_p(d_cluster_of or None), C.c_void_p(d_cluster_start or None),
+            C.c_void_p(d_member or None), C.c_void_p(d_count or None), C.byref(clusters)))
+        return clusters.value
+
     # ---- the pairs as neighbour lists in CSR (include/compairr_hip.h: cmpr_neighbors*) ----
 
     def neighbors(self):
@@ -489,6 +524,15 @@ def cluster(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
         for name, value in (tunables or {}).items():
             h.set_tunable(name, value)
         return h.cluster(s)
+
+
+def cluster_table(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
+    """Convenience: (cluster_of, cluster_start, members, count) of `s` under `opt` (HipOverlap.cluster_table) on
+    a context of its own.  `tunables` are set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        return h.cluster_table(s)
 
 
 def neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

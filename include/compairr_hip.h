@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_existence_csr*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_existence_csr*, cmpr_cluster_table*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -439,8 +439,8 @@ int cmpr_deduplicate_device(cmpr_context *ctx, const cmpr_set_view *d_set, uint6
  *                    takes the seeds in increasing order, prints the cluster at;
  *   size_out[i]      the number of members of that cluster: the reference's cluster_size column;
  *   *n_clusters_out  the number of i with label_out[i] == i: the reference's "Clusters:" figure.
- * (The reference numbers its clusters by size descending, then by that smallest number ascending: a sort of
- * the i with label_out[i] == i by (-size_out[i], i).)  Any of the three may be NULL; n_clusters_out is a
+ * (The reference numbers its clusters by size descending, then by that smallest number ascending:
+ * cmpr_cluster_table() below gives that numbering and the members of every cluster.)  Any of the three may be NULL; n_clusters_out is a
  * HOST pointer in both variants.  n == 0 is CMPR_OK with zero clusters.  Results are identical from run to
  * run and do not depend on any tunable (the smallest number of a component does not depend on the schedule).
  *
@@ -467,6 +467,49 @@ int cmpr_cluster(cmpr_context *ctx, const cmpr_set_view *set,
                  uint32_t *label_out, uint32_t *size_out, uint64_t *n_clusters_out);
 int cmpr_cluster_device(cmpr_context *ctx, const cmpr_set_view *d_set,
                         uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out);
+
+/*
+ * The clusters of one set as the reference's --cluster prints them, without the member order of its sweep: the
+ * partition of cmpr_cluster() on the same set and context -- the same links, the same options, the same
+ * independence from tunables and from a reference indexed in parts -- numbered and grouped on the device.
+ * The K clusters are numbered 0 .. K-1 by (number of members descending, smallest member ascending); number k
+ * is the reference's cluster_no k + 1 (its qsort compares sizes only, and equal sizes stay in the order of
+ * their seeds, which is increasing: cluster.cc:53-63, :422).
+ *   cluster_of_out[n]     the number of the cluster of sequence i;
+ *   cluster_start_out     the caller provides n + 1 elements (K <= n: no capacity to guess or ask for); the first
+ *                         K + 1 are written, the rest are not the call's to write.  cluster_start[0] == 0,
+ *                         cluster_start[K] == n, and cluster_start[k + 1] - cluster_start[k] is the cluster_size
+ *                         of cluster k, non-increasing in k;
+ *   member_out[n]         cluster k occupies [cluster_start[k], cluster_start[k + 1]): its sequence numbers in
+ *                         strictly increasing order, so the first is the cluster's label in the sense of
+ *                         cmpr_cluster().  (The reference lists the members in the breadth-first order of its
+ *                         sweep, which is not reproduced.)
+ *   count_out             the caller provides n elements, K are written: the sum of duplicate_count over the
+ *                         members of cluster k, with ignore_counts the number of its members; uint64 arithmetic,
+ *                         as cmpr_deduplicate()'s count_out;
+ *   *n_clusters_out       K, a HOST pointer in both variants.
+ * Any of the five may be NULL.  cmpr_cluster_table_device() takes a DEVICE view as cmpr_cluster_device() does and
+ * writes the four arrays -- device memory on the context's device -- where they lie: only what
+ * cmpr_cluster_device() already moves, K and the largest cluster's size cross PCIe.
+ *
+ * Everything else is as for cmpr_cluster(), word for word: the same validation of the set, the same refusals
+ * with the same codes and texts (NULL set, options.existence, work_shard_count > 1; d > 2 at cmpr_create);
+ * n == 0 is CMPR_OK with K = 0 and nothing written but cluster_start[0] = 0; AFTERWARDS `set` IS RESIDENT AS
+ * BOTH SETS; synchronous; every temporary is freed before the call returns, also when it fails.  Results are
+ * identical from run to run (stable sorts, integer sums).
+ *
+ * Footprint beyond the two resident sets, for the duration of the call: the 8 bytes per sequence of
+ * cmpr_cluster() (forest and labels, both reused by the table pass), 4 each for cluster_of and the members
+ * unless they go to the caller's device arrays, 8 and a few histograms for the radix sort's scratch; per
+ * cluster 16 bytes (roots and keys, before and behind their sort), and in the host variant 8 each for
+ * cluster_start and the counts.
+ */
+int cmpr_cluster_table(cmpr_context *ctx, const cmpr_set_view *set,
+                       uint32_t *cluster_of_out, uint64_t *cluster_start_out,
+                       uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out);
+int cmpr_cluster_table_device(cmpr_context *ctx, const cmpr_set_view *d_set,
+                              uint32_t *d_cluster_of_out, uint64_t *d_cluster_start_out,
+                              uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out);
 
 /*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
@@ -613,7 +656,10 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    "neighbors_fill_us", "neighbors_order_us" (a cmpr_existence_csr*() call sets the first three and zeroes the
    fourth); and of the last cmpr_existence_csr*(): "existence_edges_us" (those three together),
    "existence_group_us" (rows sorted by repertoire, cells per row), "existence_count_us" (their sum, the cell count
-   to the host), "existence_reduce_us" (the cells; 0 when they did not fit) and "existence_copy_us" (host variant). */
+   to the host), "existence_reduce_us" (the cells; 0 when they did not fit) and "existence_copy_us" (host variant);
+   and of the last cmpr_cluster_table*(), host times, each part ending in a wait: "cluster_links_us" (the set as
+   both sets, the link step, labels and sizes flat on the device) and "cluster_table_us" (everything after: the
+   numbering, the members, the counts and, in the host variant, their copies). */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

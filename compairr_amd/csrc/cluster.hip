@@ -52,19 +52,12 @@
 
 #include <algorithm>
 #include <chrono>
-#include <new>
 
 using namespace cmpr;
 
 namespace {
 
 constexpr uint32_t CLUSTER_WG = 256;
-
-template <typename T>
-struct Tmp {
-  DevBuf<T> b;
-  ~Tmp() { b.release(); }
-};
 
 __global__ void __launch_bounds__(CLUSTER_WG)
 cluster_init_kernel(uint32_t *parent, uint64_t n)
@@ -305,16 +298,6 @@ table_count_kernel(const uint32_t *cluster_at, const uint32_t *member, const uin
     atomicAdd(count + mine, v);
 }
 
-uint32_t grid_for(uint64_t n)
-{
-  return (uint32_t)((n + CLUSTER_WG - 1) / CLUSTER_WG);
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 int bit_length(uint64_t x)
 {
   return x ? 64 - __builtin_clzll(x) : 0;
@@ -424,8 +407,8 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   /* ---- roots and keys; the cluster order ---- */
   HIP_TRY(c, hipcub::DeviceSelect::If(scratch.b.p, select_bytes, numbers, root.b.p, selected.b.p, (int64_t)n,
                                       IsRoot{L.label}, c->stream));
-  hipLaunchKernelGGL(table_key_kernel, dim3(grid_for(K)), dim3(CLUSTER_WG), 0, c->stream, root.b.p, L.size, largest,
-                     key.b.p, K);
+  hipLaunchKernelGGL(table_key_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
+                     root.b.p, L.size, largest, key.b.p, K);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, order_bytes, (const uint32_t *)key.b.p, key_sorted.b.p,
                                                 (const uint32_t *)root.b.p, root_sorted.b.p, (size_t)K, 0, size_bits,
@@ -437,9 +420,11 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
                                                 c->stream));
   if (want_of) {
     uint32_t *const number = L.size;             /* (the keys have read the sizes: their words are free) */
-    hipLaunchKernelGGL(table_number_kernel, dim3(grid_for(K)), dim3(CLUSTER_WG), 0, c->stream, root_sorted.b.p, number, K);
+    hipLaunchKernelGGL(table_number_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
+                       root_sorted.b.p, number, K);
     HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(table_of_kernel, dim3(grid_for(n)), dim3(CLUSTER_WG), 0, c->stream, L.label, number, cluster_of, n);
+    hipLaunchKernelGGL(table_of_kernel, dim3(blocks_for(n, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
+                       L.label, number, cluster_of, n);
     HIP_TRY(c, hipGetLastError());
   }
 
@@ -452,12 +437,12 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   /* ---- counts ---- */
   if (sum_counts) {
     HIP_TRY(c, hipMemsetAsync(count, 0, (size_t)K * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(table_count_kernel, dim3(grid_for(n)), dim3(CLUSTER_WG), 0, c->stream, L.size, member,
-                       c->cnt2.p, count, n);
+    hipLaunchKernelGGL(table_count_kernel, dim3(blocks_for(n, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
+                       L.size, member, c->cnt2.p, count, n);
     HIP_TRY(c, hipGetLastError());
   } else if (count) {
-    hipLaunchKernelGGL(table_sizes_kernel, dim3(grid_for(K)), dim3(CLUSTER_WG), 0, c->stream, key_sorted.b.p, largest,
-                       count, K);
+    hipLaunchKernelGGL(table_sizes_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
+                       key_sorted.b.p, largest, count, K);
     HIP_TRY(c, hipGetLastError());
   }
 
@@ -475,17 +460,6 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->cl_ms[1] = ms_since(t0);
   return CMPR_OK;
-}
-
-/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-template <typename F>
-int guarded(cmpr_context *c, F call)
-{
-  try {
-    return call();
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
 }
 
 }  // namespace

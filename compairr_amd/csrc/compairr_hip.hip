@@ -1402,14 +1402,11 @@ extern "C" int cmpr_get_stats(cmpr_context *c, cmpr_stats *out)
 
 static int set_reference_guarded(cmpr_context *c, const cmpr_set_view *s, uint32_t longest_query, bool on_device)
 {
-  /* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-  try {
+  return guarded(c, [&] {
     if (c)
       invalidate_plan(c);
     return cmpr_build_reference(c, s, longest_query, on_device);
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
+  });
 }
 
 extern "C" int cmpr_set_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longest_query)
@@ -1556,12 +1553,7 @@ extern "C" int cmpr_warm_up_sized(const cmpr_options *o, uint64_t n_queries_hint
 
 static int set_queries_guarded(cmpr_context *c, const LayoutSource &src)
 {
-  /* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-  try {
-    return cmpr_set_queries_impl(c, src);
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
+  return guarded(c, [&] { return cmpr_set_queries_impl(c, src); });
 }
 
 extern "C" int cmpr_set_queries(cmpr_context *c, const cmpr_set_view *s)
@@ -1599,7 +1591,7 @@ extern "C" int cmpr_route_queries(cmpr_context *c, const cmpr_set_view *share, u
 {
   if (!c)
     return CMPR_EINVAL;
-  try {
+  return guarded(c, [&]() -> int {
     if (!c->have_ref)
       return fail(c, CMPR_ESTATE, "cmpr_set_reference must be called first");
     if (!counts_out || !record_bytes_out)
@@ -1632,9 +1624,7 @@ extern "C" int cmpr_route_queries(cmpr_context *c, const cmpr_set_view *share, u
       for (uint32_t r = 0; r < share->n_repertoires; r++)
         rep_totals_out[r] = c->route.rep_totals[r];
     return CMPR_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
+  });
 }
 
 extern "C" int cmpr_route_pack(cmpr_context *c, void *d_send, uint64_t capacity_bytes)
@@ -1646,10 +1636,5 @@ extern "C" int cmpr_route_pack(cmpr_context *c, void *d_send, uint64_t capacity_
 
 extern "C" int cmpr_overlap_matrix_f64(cmpr_context *c, double *out)
 {
-  /* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-  try {
-    return cmpr_overlap_matrix_f64_impl(c, out);
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
+  return guarded(c, [&] { return cmpr_overlap_matrix_f64_impl(c, out); });
 }

@@ -12,8 +12,10 @@
 
 #include "select.h"
 
+#include <chrono>
 #include <functional>
 #include <map>
+#include <new>
 #include <set>
 #include <string>
 #include <vector>
@@ -393,6 +395,41 @@ int dev_alloc(cmpr_context *c, DevBuf<T> &b, size_t n)
   b.n = n;
   b.cap = n;
   return CMPR_OK;
+}
+
+/* a device temporary of one call: freed when the call returns, also when it fails */
+template <typename T>
+struct Tmp {
+  DevBuf<T> b;
+  ~Tmp() { b.release(); }
+};
+
+/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
+template <typename F>
+int guarded(cmpr_context *c, F call)
+{
+  try {
+    return call();
+  } catch (const std::bad_alloc &) {
+    return fail(c, CMPR_ENOMEM, "out of host memory");
+  }
+}
+
+inline double ms_since(std::chrono::steady_clock::time_point t0)
+{
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+/* 32-bit words summed or scanned as 64 bits (hipcub::TransformInputIterator) */
+struct U32To64 {
+  __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
+};
+
+/* workgroups of wg lanes for n items, one lane each: 0 for n = 0 (the callers skip such a launch).  The one-argument
+   blocks_for(n) that query_layout.hip and ref_index.hip keep for themselves answers 1 there. */
+inline uint32_t blocks_for(uint64_t n, uint32_t wg)
+{
+  return (uint32_t)((n + wg - 1) / wg);
 }
 
 /* The host waits for a launch on a retired query set that may still run on a caller's stream

@@ -1,0 +1,263 @@
+/*
+ * csr_rows.h -- the passes over CSR rows of hits that neighbors.hip and existence.hip share: every row sorted in
+ * place by a key of its hits, on one of four paths by the row's length n.  The thresholds are what each path
+ * holds, and this is their only definition: the census that sizes the lists (neighbors.hip nb_census_kernel)
+ * counts by them.
+ *
+ *   n <= 1              nothing.  Real data: most rows.
+ *   n <= LANE_MAX = 8   one lane per row, the row in eight registers, a 19-comparator network
+ *                       (rows_sort_short_kernel).  Eight is where real data ends (20 000 CDR3 against themselves,
+ *                       d = 1 -i: longest row 9), a network of 16 costs 60 comparators for every lane of a
+ *                       wave that has one such row, and neighbouring lanes read neighbouring rows.
+ *   n <= WAVE = 64      one element per lane, a bitonic sort with 21 shuffle steps (two shuffles each for a 64-bit
+ *                       key); the wave takes the rows of its 64 lanes that need it one after the other (same
+ *                       kernel).  No LDS, no workgroup.
+ *   n <= LDS_MAX = 8192 one workgroup of 256 lanes per row, bitonic in LDS over the next power of two
+ *                       (rows_sort_lds_kernel).  With 32-bit keys that is 32 KiB of the CU's 160, which leaves room
+ *                       for four such workgroups per CU (with 40 960 words one would fit); at 8192 words a
+ *                       single-workgroup bitonic sort is 91 passes of 32 elements per lane, and beyond that the
+ *                       device-wide radix sort, which has the whole GPU for one row, is the better tool.  With
+ *                       64-bit keys 8192 of them are 64 KiB -- what a workgroup may declare statically, and two
+ *                       such workgroups still fit the CU; a lane reads s[t] and s[t ^ j] as 8-byte words at
+ *                       consecutive t: a half-wave covers one 256-byte bank row, no conflict.  These rows are
+ *                       listed by the short-row kernel (big_rows: the census sized the list exactly), so rows of 0
+ *                       and 1 cost a lane, not a workgroup.
+ *   longer              no limit: the rows' (start, length, row) are listed too, come to the host (24 bytes per
+ *                       such row, rows_fetch_long) and the caller hands each to hipcub, the whole GPU for one row.
+ *                       A handful of rows in skewed data.
+ *
+ * What differs between the callers is a policy struct `Rows`, passed to the kernels by value:
+ *
+ *   Key, PAD            the sort key of a hit, and a value above every key (behind a row's end while it is sorted)
+ *   key_of(hit), hit_of(key)
+ *   COUNT_HEADS         whether the sorted row's heads -- the positions p with !same_run(key[p - 1], key[p]), and
+ *                       position 0 -- are counted into ncell[row].  With it the short kernel runs over n + 1 lanes
+ *                       and writes every word of ncell[0 .. n]: the heads of the rows it sorted, 0 for the listed
+ *                       rows (the LDS kernel adds theirs) and for the word behind the last row.
+ */
+#ifndef COMPAIRR_AMD_CSR_ROWS_H
+#define COMPAIRR_AMD_CSR_ROWS_H
+
+#include "context.h"
+
+namespace cmpr {
+
+constexpr uint32_t ROW_WG = 256;
+constexpr uint32_t LANE_MAX = 8;
+constexpr uint32_t LDS_MAX = 8192;
+constexpr uint32_t LONG_WORDS = 3;      /* of a long_desc entry: start, length, row */
+
+/* the lists of the rows beyond a wave, as the kernels see them: big_cap and long_cap are what the census counted,
+   ctr[0] / ctr[1] the entries taken so far (zero before the short kernel) */
+struct RowLists {
+  uint32_t           *big_rows;
+  uint64_t            big_cap;
+  unsigned long long *long_desc;
+  uint64_t            long_cap;
+  unsigned long long *ctr;
+};
+
+template <typename Key>
+__device__ __forceinline__ void row_cx(Key &a, Key &b)
+{
+  const Key lo = a < b ? a : b, hi = a < b ? b : a;
+  a = lo;
+  b = hi;
+}
+
+/* 19 comparators in 6 layers (Knuth, TAOCP 3, 5.3.4) */
+template <typename Key>
+__device__ __forceinline__ void row_sort8(Key (&v)[LANE_MAX])
+{
+  row_cx(v[0], v[1]); row_cx(v[2], v[3]); row_cx(v[4], v[5]); row_cx(v[6], v[7]);
+  row_cx(v[0], v[2]); row_cx(v[1], v[3]); row_cx(v[4], v[6]); row_cx(v[5], v[7]);
+  row_cx(v[1], v[2]); row_cx(v[5], v[6]); row_cx(v[0], v[4]); row_cx(v[3], v[7]);
+  row_cx(v[1], v[5]); row_cx(v[2], v[6]);
+  row_cx(v[1], v[4]); row_cx(v[3], v[6]);
+  row_cx(v[2], v[4]); row_cx(v[3], v[5]);
+  row_cx(v[3], v[4]);
+}
+
+/* one key per lane in, the wave's keys in increasing order of the lane out */
+template <typename Key>
+__device__ __forceinline__ Key wave_sort(Key v, uint32_t lane)
+{
+  for (uint32_t k = 2; k <= WAVE; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      const Key other = __shfl_xor(v, j, WAVE);
+      const bool up = (lane & k) == 0, low = (lane & j) == 0;
+      v = (up == low) ? (v < other ? v : other) : (v < other ? other : v);
+    }
+  return v;
+}
+
+/* Every lane brings its row.  The rows of this wave's lanes whose length lies in (LANE_MAX, WAVE], one after the
+   other and by the whole wave: f(the row's lane, its start, its length). */
+template <typename F>
+__device__ __forceinline__ void for_each_wave_row(uint64_t start, uint64_t len, F f)
+{
+  uint64_t todo = __ballot(len > LANE_MAX && len <= WAVE);
+  while (todo) {
+    const uint32_t src = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
+    todo &= todo - 1;
+    const uint64_t s = __shfl(start, src, WAVE);
+    f(src, s, (uint32_t)__shfl(len, src, WAVE));
+  }
+}
+
+/* One lane per row.  Rows of 2 .. LANE_MAX: sorted by their lane.  Rows of up to WAVE: by the wave, one after the
+   other.  Longer rows: listed for rows_sort_lds_kernel (big_rows, as many as the census counted) or, beyond LDS,
+   with start, length and row for the host (long_desc); the order of the lists is that of arrival and does not
+   show in the result. */
+template <typename Rows>
+__global__ void __launch_bounds__(ROW_WG)
+rows_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, const RowLists L, const Rows R)
+{
+  using Key = typename Rows::Key;
+  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
+  const uint32_t lane = lane_id();
+  uint64_t start = 0, len = 0;
+  if (i < n) {
+    start = row_start[i];
+    len = row_start[i + 1] - start;
+  }
+  [[maybe_unused]] uint32_t cells = len == 1 ? 1u : 0u;
+  if (len >= 2 && len <= LANE_MAX) {
+    Key v[LANE_MAX];
+#pragma unroll
+    for (uint32_t k = 0; k < LANE_MAX; k++)
+      v[k] = k < len ? R.key_of(hit[start + k]) : Rows::PAD;
+    row_sort8(v);
+    cells = 1;
+#pragma unroll
+    for (uint32_t k = 0; k < LANE_MAX; k++)
+      if (k < len) {
+        hit[start + k] = Rows::hit_of(v[k]);
+        if constexpr (Rows::COUNT_HEADS)
+          if (k > 0 && !Rows::same_run(v[k - 1], v[k]))
+            cells++;
+      }
+  } else if (len > WAVE) {
+    if (len > LDS_MAX) {
+      const unsigned long long k = atomicAdd(L.ctr + 1, 1ull);
+      if (k < L.long_cap) {
+        L.long_desc[LONG_WORDS * k] = start;
+        L.long_desc[LONG_WORDS * k + 1] = len;
+        L.long_desc[LONG_WORDS * k + 2] = i;
+      }
+    } else {
+      const unsigned long long k = atomicAdd(L.ctr + 0, 1ull);
+      if (k < L.big_cap)
+        L.big_rows[k] = (uint32_t)i;
+    }
+  }
+  for_each_wave_row(start, len, [&](uint32_t src, uint64_t s, uint32_t m) {
+    const Key v = wave_sort(lane < m ? R.key_of(hit[s + lane]) : Rows::PAD, lane);
+    if constexpr (Rows::COUNT_HEADS) {
+      const Key before = __shfl_up(v, 1, WAVE);
+      const uint64_t heads = __ballot(lane < m && (lane == 0 || !Rows::same_run(before, v)));
+      if (lane == src)
+        cells = (uint32_t)__popcll(heads);
+    }
+    if (lane < m)
+      hit[s + lane] = Rows::hit_of(v);
+  });
+  if constexpr (Rows::COUNT_HEADS)
+    if (i <= n)
+      R.ncell[i] = cells;
+}
+
+/* One workgroup per listed row of WAVE + 1 .. LDS_MAX hits: bitonic in LDS over the next power of two. */
+template <typename Rows>
+__global__ void __launch_bounds__(ROW_WG)
+rows_sort_lds_kernel(const uint64_t *row_start, uint32_t *hit, const uint32_t *big_rows, const Rows R)
+{
+  using Key = typename Rows::Key;
+  __shared__ Key s[LDS_MAX];
+  const uint32_t row = big_rows[blockIdx.x];
+  const uint64_t start = row_start[row];
+  const uint64_t len64 = row_start[row + 1] - start;
+  if (len64 > LDS_MAX)
+    return;                                  /* (the list holds no such row; nothing is indexed beyond s) */
+  const uint32_t len = (uint32_t)len64;
+  uint32_t np = 2 * WAVE;
+  while (np < len)
+    np <<= 1;
+  for (uint32_t t = threadIdx.x; t < np; t += ROW_WG)
+    s[t] = t < len ? R.key_of(hit[start + t]) : Rows::PAD;
+  __syncthreads();
+  for (uint32_t k = 2; k <= np; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = threadIdx.x; t < np; t += ROW_WG) {
+        const uint32_t u = t ^ j;
+        if (u > t) {
+          const Key a = s[t], b = s[u];
+          if (((t & k) == 0) == (a > b)) {
+            s[t] = b;
+            s[u] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  [[maybe_unused]] uint32_t heads = 0;
+  for (uint32_t t = threadIdx.x; t < len; t += ROW_WG) {
+    hit[start + t] = Rows::hit_of(s[t]);
+    if constexpr (Rows::COUNT_HEADS)
+      if (t == 0 || !Rows::same_run(s[t - 1], s[t]))
+        heads++;
+  }
+  if constexpr (Rows::COUNT_HEADS) {
+#pragma unroll
+    for (uint32_t off = WAVE / 2; off > 0; off >>= 1)
+      heads += __shfl_xor(heads, off, WAVE);
+    if (lane_id() == 0 && heads)
+      atomicAdd(R.ncell + row, heads);         /* (zero since the short kernel; four adders, integers) */
+  }
+}
+
+/* ---- host ---- */
+
+/* both kernels over the n rows; L.ctr is zero */
+template <typename Rows>
+int rows_sort(cmpr_context *c, const uint64_t *row_start, uint32_t *hit, uint64_t n, const RowLists &L, const Rows &R)
+{
+  const uint64_t lanes = n + (Rows::COUNT_HEADS ? 1 : 0);
+  hipLaunchKernelGGL(rows_sort_short_kernel<Rows>, dim3(blocks_for(lanes, ROW_WG)), dim3(ROW_WG), 0, c->stream,
+                     row_start, hit, n, L, R);
+  HIP_TRY(c, hipGetLastError());
+  if (L.big_cap) {
+    hipLaunchKernelGGL(rows_sort_lds_kernel<Rows>, dim3((uint32_t)L.big_cap), dim3(ROW_WG), 0, c->stream, row_start,
+                       hit, L.big_rows, R);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return CMPR_OK;
+}
+
+/* a row beyond LDS as rows_sort_short_kernel listed it */
+struct LongRow {
+  uint64_t start, len, row;
+};
+
+/* The listed long rows on the host (one wait), each checked against what the census and the sum said: no longer
+   than `longest`, inside the `total` hits, a row of the n rows.  `who`: the entry point, for the message. */
+inline int rows_fetch_long(cmpr_context *c, const RowLists &L, uint64_t longest, uint64_t total, uint64_t n,
+                           const char *who, std::vector<LongRow> &out)
+{
+  std::vector<unsigned long long> desc((size_t)(LONG_WORDS * L.long_cap));
+  HIP_TRY(c, hipMemcpyAsync(desc.data(), L.long_desc, desc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                            c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  out.clear();
+  for (uint64_t k = 0; k < L.long_cap; k++) {
+    const LongRow r{desc[LONG_WORDS * k], desc[LONG_WORDS * k + 1], desc[LONG_WORDS * k + 2]};
+    if (r.len > longest || r.start + r.len > total || r.row >= n)
+      return fail(c, CMPR_EDEVICE, std::string(who) + ": a listed row lies outside the hits");
+    out.push_back(r);
+  }
+  return CMPR_OK;
+}
+
+}  // namespace cmpr
+
+#endif

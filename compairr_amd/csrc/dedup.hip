@@ -21,7 +21,6 @@
 #include "context.h"
 
 #include <algorithm>
-#include <new>
 #include <string>
 #include <vector>
 
@@ -33,12 +32,6 @@ constexpr uint32_t DEDUP_WG = 256;                        /* threads per workgro
 constexpr uint32_t DEDUP_SCAN_WG = 1024;
 constexpr unsigned long long DEDUP_EMPTY = ~0ull;         /* (tag << 32) | index is never this: index < 2^32 - 64 */
 constexpr size_t DEDUP_ZOB_LDS_BYTES = 12288;             /* the Zobrist keys go to LDS up to this (query_layout.hip) */
-
-template <typename T>
-struct Tmp {
-  DevBuf<T> b;
-  ~Tmp() { b.release(); }
-};
 
 /* the entries of a set and the keys they are hashed with */
 struct EntrySet {
@@ -522,17 +515,6 @@ int count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, uint64_t *out
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   *out = hc;
   return CMPR_OK;
-}
-
-/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-template <typename F>
-int guarded(cmpr_context *c, F call)
-{
-  try {
-    return call();
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
 }
 
 }  // namespace

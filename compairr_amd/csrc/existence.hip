@@ -20,18 +20,14 @@
  *            array of the caller survives cmpr_set_queries), unless the counts are ignored.
  *   copy-out for the host variant.
  *
- * Both passes over the rows take the paths of neighbors.hip, by the row's number of HITS n, with its thresholds:
+ * Both passes over the rows take the paths of csr_rows.h, by the row's number of HITS n, with its thresholds (one
+ * census, the one the edges come with, serves both files):
  *
- *   n <= LANE_MAX = 8   one lane per row.  group: eight 64-bit keys in registers, the same 19 comparators;
- *                       reduce: the lane walks its row.
+ *   n <= LANE_MAX = 8   one lane per row.  group: rows_sort with the 64-bit key; reduce: the lane walks its row.
  *   n <= WAVE = 64      one hit per lane, the wave takes such rows of its 64 lanes one after the other.  group:
- *                       the bitonic sort with 21 steps of two shuffles; reduce: heads by ballot, the run sums by a
- *                       segmented scan of six shuffle steps, the last lane of a run stores.  No LDS, no atomics.
- *   n <= LDS_MAX = 8192 one workgroup of 256 lanes per listed row.  group: bitonic in LDS.  The key is 64 bits, so
- *                       8192 of them are 64 KiB -- what a workgroup may declare statically, and two such
- *                       workgroups still fit the CU's 160 KiB; keeping the threshold of neighbors.hip keeps ONE
- *                       census (the one the edges come with) for both files.  A lane reads s[t] and s[t ^ j] as
- *                       8-byte words at consecutive t: a half-wave covers one 256-byte bank row, no conflict.
+ *                       rows_sort; reduce: heads by ballot, the run sums by a segmented scan of six shuffle steps,
+ *                       the last lane of a run stores.  No LDS, no atomics.
+ *   n <= LDS_MAX = 8192 one workgroup of 256 lanes per listed row.  group: rows_sort, 64 KiB of LDS.
  *                       reduce: 256 positions per round; a round's heads are counted per wave (ballot) and summed
  *                       over the four waves through 16 bytes of LDS, which ranks every position; the segmented
  *                       scan as above, and the last lane of a run INSIDE a wave adds its sum to the value with
@@ -48,31 +44,26 @@
  * scratch of the sort and of the reduction.  The host variant adds what the device variant is handed: 8 bytes per
  * query, 12 per cell.  Everything is freed before the call returns, also when it fails.
  */
-#include "context.h"
+#include "csr_rows.h"
 
 #include <hipcub/hipcub.hpp>
-
-#include <chrono>
-#include <new>
 
 using namespace cmpr;
 
 namespace {
 
-constexpr uint32_t EX_WG = 256;
-constexpr uint32_t EX_WAVES = EX_WG / WAVE;
-constexpr uint32_t LANE_MAX = 8;
-constexpr uint32_t LDS_MAX = 8192;                 /* = neighbors.hip: the census of the edges counts by it */
-constexpr uint64_t EX_PAD = ~0ull;                 /* behind a row's end while it is sorted: above every key */
+constexpr uint32_t EX_WAVES = ROW_WG / WAVE;
 
-template <typename T>
-struct Tmp {
-  DevBuf<T> b;
-  ~Tmp() { b.release(); }
-};
-
-struct U32To64 {
-  __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
+/* the rows grouped by the repertoire of the hit, each row's heads -- its cells -- counted (csr_rows.h) */
+struct ExRows {
+  using Key = unsigned long long;
+  static constexpr Key  PAD = ~0ull;
+  static constexpr bool COUNT_HEADS = true;
+  const uint32_t *rep2;
+  uint32_t       *ncell;
+  __device__ Key key_of(uint32_t hit) const { return (Key)rep2[hit] << 32 | hit; }
+  __device__ static uint32_t hit_of(Key key) { return (uint32_t)key; }
+  __device__ static bool same_run(Key a, Key b) { return (a >> 32) == (b >> 32); }
 };
 
 /* what a hit adds to its cell: score_match (kernels.h) with f the query's count and g the hit's */
@@ -105,27 +96,15 @@ struct ExScoreOfHit {
 };
 
 /* cnt1[i] of the resident queries: lanes 0 .. nvalid - 1 of a tile are queries, the rest is padding */
-__global__ void __launch_bounds__(EX_WG)
+__global__ void __launch_bounds__(ROW_WG)
 ex_cnt1_kernel(const TileDesc *tiles, const QueryRec *qrec, uint64_t nslots, uint64_t n1, uint64_t *cnt1)
 {
-  const uint64_t slot = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint64_t slot = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
   if (slot >= nslots || (uint32_t)(slot % WAVE) >= tiles[slot / WAVE].nvalid)
     return;
   const uint32_t orig = qrec[slot].orig;
   if (orig < n1)
     cnt1[orig] = qrec[slot].cnt;
-}
-
-__device__ __forceinline__ void ex_cx(uint64_t &a, uint64_t &b)
-{
-  const uint64_t lo = a < b ? a : b, hi = a < b ? b : a;
-  a = lo;
-  b = hi;
-}
-
-__device__ __forceinline__ uint64_t ex_key(const uint32_t *rep2, uint32_t hit)
-{
-  return (uint64_t)rep2[hit] << 32 | hit;
 }
 
 /* bits 0 .. lane of a ballot */
@@ -148,152 +127,31 @@ __device__ __forceinline__ unsigned long long ex_run_sums(unsigned long long v, 
   return v;
 }
 
-/* group, one lane per row: rows of 2 .. LANE_MAX sorted by their lane, rows of up to WAVE by the wave, longer rows
-   listed (big_rows / long_desc: start, length, row), as nb_sort_short_kernel does.  ncell[i] = the heads of row i
-   for the rows handled here, 0 for the listed ones (their sorters add to it) and for the word behind the last row. */
-__global__ void __launch_bounds__(EX_WG)
-ex_group_short_kernel(const uint64_t *estart, uint32_t *hit, const uint32_t *rep2, uint64_t n, uint32_t *ncell,
-                      uint32_t *big_rows, uint64_t big_cap, unsigned long long *long_desc, uint64_t long_cap,
-                      unsigned long long *list_ctr)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
-  const uint32_t lane = lane_id();
-  uint64_t start = 0, len = 0;
-  if (i < n) {
-    start = estart[i];
-    len = estart[i + 1] - start;
-  }
-  uint32_t cells = len == 1 ? 1u : 0u;
-  if (len >= 2 && len <= LANE_MAX) {
-    uint64_t v[LANE_MAX];
-#pragma unroll
-    for (uint32_t k = 0; k < LANE_MAX; k++)
-      v[k] = k < len ? ex_key(rep2, hit[start + k]) : EX_PAD;
-    /* 19 comparators in 6 layers (Knuth, TAOCP 3, 5.3.4) */
-    ex_cx(v[0], v[1]); ex_cx(v[2], v[3]); ex_cx(v[4], v[5]); ex_cx(v[6], v[7]);
-    ex_cx(v[0], v[2]); ex_cx(v[1], v[3]); ex_cx(v[4], v[6]); ex_cx(v[5], v[7]);
-    ex_cx(v[1], v[2]); ex_cx(v[5], v[6]); ex_cx(v[0], v[4]); ex_cx(v[3], v[7]);
-    ex_cx(v[1], v[5]); ex_cx(v[2], v[6]);
-    ex_cx(v[1], v[4]); ex_cx(v[3], v[6]);
-    ex_cx(v[2], v[4]); ex_cx(v[3], v[5]);
-    ex_cx(v[3], v[4]);
-    cells = 1;
-#pragma unroll
-    for (uint32_t k = 0; k < LANE_MAX; k++)
-      if (k < len) {
-        hit[start + k] = (uint32_t)v[k];
-        if (k > 0 && (v[k] >> 32) != (v[k - 1] >> 32))
-          cells++;
-      }
-  } else if (len > WAVE) {
-    if (len > LDS_MAX) {
-      const unsigned long long k = atomicAdd(list_ctr + 1, 1ull);
-      if (k < long_cap) {
-        long_desc[3 * k] = start;
-        long_desc[3 * k + 1] = len;
-        long_desc[3 * k + 2] = i;
-      }
-    } else {
-      const unsigned long long k = atomicAdd(list_ctr + 0, 1ull);
-      if (k < big_cap)
-        big_rows[k] = (uint32_t)i;
-    }
-  }
-  /* the wave's rows of LANE_MAX + 1 .. WAVE */
-  uint64_t todo = __ballot(len > LANE_MAX && len <= WAVE);
-  while (todo) {
-    const uint32_t src = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
-    todo &= todo - 1;
-    const uint64_t s = __shfl(start, src, WAVE);
-    const uint32_t m = (uint32_t)__shfl(len, src, WAVE);
-    unsigned long long v = lane < m ? ex_key(rep2, hit[s + lane]) : EX_PAD;
-    for (uint32_t k = 2; k <= WAVE; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        const unsigned long long other = __shfl_xor(v, j, WAVE);
-        const bool up = (lane & k) == 0, low = (lane & j) == 0;
-        v = (up == low) ? (v < other ? v : other) : (v < other ? other : v);
-      }
-    const unsigned long long before = __shfl_up(v, 1, WAVE);
-    const uint64_t heads = __ballot(lane < m && (lane == 0 || (v >> 32) != (before >> 32)));
-    if (lane < m)
-      hit[s + lane] = (uint32_t)v;
-    if (lane == src)
-      cells = (uint32_t)__popcll(heads);
-  }
-  if (i <= n)
-    ncell[i] = cells;
-}
-
-/* group, one workgroup per listed row of WAVE + 1 .. LDS_MAX hits: bitonic in LDS over the next power of two */
-__global__ void __launch_bounds__(EX_WG)
-ex_group_lds_kernel(const uint64_t *estart, uint32_t *hit, const uint32_t *rep2, const uint32_t *big_rows,
-                    uint32_t *ncell)
-{
-  __shared__ uint64_t s[LDS_MAX];
-  const uint32_t row = big_rows[blockIdx.x];
-  const uint64_t start = estart[row];
-  const uint64_t len64 = estart[row + 1] - start;
-  if (len64 > LDS_MAX)
-    return;                                  /* (the list holds no such row; nothing is indexed beyond s) */
-  const uint32_t len = (uint32_t)len64;
-  uint32_t np = 2 * WAVE;
-  while (np < len)
-    np <<= 1;
-  for (uint32_t t = threadIdx.x; t < np; t += EX_WG)
-    s[t] = t < len ? ex_key(rep2, hit[start + t]) : EX_PAD;
-  __syncthreads();
-  for (uint32_t k = 2; k <= np; k <<= 1)
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < np; t += EX_WG) {
-        const uint32_t u = t ^ j;
-        if (u > t) {
-          const uint64_t a = s[t], b = s[u];
-          if (((t & k) == 0) == (a > b)) {
-            s[t] = b;
-            s[u] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  uint32_t heads = 0;
-  for (uint32_t t = threadIdx.x; t < len; t += EX_WG) {
-    hit[start + t] = (uint32_t)s[t];
-    if (t == 0 || (s[t] >> 32) != (s[t - 1] >> 32))
-      heads++;
-  }
-#pragma unroll
-  for (uint32_t off = WAVE / 2; off > 0; off >>= 1)
-    heads += __shfl_xor(heads, off, WAVE);
-  if (lane_id() == 0 && heads)
-    atomicAdd(ncell + row, heads);           /* (zero since ex_group_short_kernel; four adders, integers) */
-}
-
 /* group, rows beyond LDS: the repertoires of a row's hits as sort keys ... */
-__global__ void __launch_bounds__(EX_WG)
+__global__ void __launch_bounds__(ROW_WG)
 ex_gather_rep_kernel(const uint32_t *hit, uint64_t len, const uint32_t *rep2, uint32_t *key)
 {
-  const uint64_t p = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint64_t p = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
   if (p < len)
     key[p] = rep2[hit[p]];
 }
 
 /* ... and the heads of the sorted keys */
-__global__ void __launch_bounds__(EX_WG)
+__global__ void __launch_bounds__(ROW_WG)
 ex_count_heads_kernel(const uint32_t *key, uint64_t len, uint32_t *out)
 {
-  const uint64_t p = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint64_t p = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
   const uint64_t heads = __ballot(p < len && (p == 0 || key[p] != key[p - 1]));
   if (lane_id() == 0 && heads)
     atomicAdd(out, (uint32_t)__popcll(heads));
 }
 
 /* reduce, one lane per row: rows of up to LANE_MAX walked by their lane, rows of up to WAVE by the wave */
-__global__ void __launch_bounds__(EX_WG)
+__global__ void __launch_bounds__(ROW_WG)
 ex_reduce_short_kernel(const uint64_t *estart, const uint32_t *hit, const uint32_t *rep2, uint64_t n,
                        const uint64_t *cstart, uint32_t *rep_out, unsigned long long *val_out, const ExScore S)
 {
-  const uint64_t i = (uint64_t)blockIdx.x * EX_WG + threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
   const uint32_t lane = lane_id();
   uint64_t start = 0, len = 0, c = 0;
   unsigned long long f = 1;
@@ -323,12 +181,8 @@ ex_reduce_short_kernel(const uint64_t *estart, const uint32_t *hit, const uint32
     rep_out[at] = cur;
     val_out[at] = sum;
   }
-  uint64_t todo = __ballot(len > LANE_MAX && len <= WAVE);
-  while (todo) {
-    const uint32_t src = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
-    todo &= todo - 1;
-    const uint64_t s = __shfl(start, src, WAVE), cs = __shfl(c, src, WAVE);
-    const uint32_t m = (uint32_t)__shfl(len, src, WAVE);
+  for_each_wave_row(start, len, [&](uint32_t src, uint64_t s, uint32_t m) {
+    const uint64_t cs = __shfl(c, src, WAVE);
     const unsigned long long fs = __shfl(f, src, WAVE);
     const bool valid = lane < m;
     uint32_t r = 0xffffffffu;
@@ -347,11 +201,11 @@ ex_reduce_short_kernel(const uint64_t *estart, const uint32_t *hit, const uint32
       rep_out[at] = r;
     if (valid && (lane + 1 == m || ((heads >> (lane + 1u)) & 1ull)))
       val_out[at] = sum;
-  }
+  });
 }
 
-/* reduce, one workgroup per listed row of WAVE + 1 .. LDS_MAX hits, EX_WG positions per round */
-__global__ void __launch_bounds__(EX_WG)
+/* reduce, one workgroup per listed row of WAVE + 1 .. LDS_MAX hits, ROW_WG positions per round */
+__global__ void __launch_bounds__(ROW_WG)
 ex_reduce_lds_kernel(const uint64_t *estart, const uint32_t *hit, const uint32_t *rep2, const uint32_t *big_rows,
                      const uint64_t *cstart, uint32_t *rep_out, unsigned long long *val_out, const ExScore S)
 {
@@ -366,11 +220,11 @@ ex_reduce_lds_kernel(const uint64_t *estart, const uint32_t *hit, const uint32_t
   const uint32_t cells = (uint32_t)(cstart[row + 1] - c);
   const unsigned long long f = S.count_of(row);
   const uint32_t lane = lane_id(), wave = threadIdx.x / WAVE;
-  for (uint32_t t = threadIdx.x; t < cells; t += EX_WG)
+  for (uint32_t t = threadIdx.x; t < cells; t += ROW_WG)
     val_out[c + t] = 0;
   __syncthreads();                           /* (the zeros are in memory before any wave of this workgroup adds) */
   uint32_t base = 0;                         /* heads of the rounds so far */
-  for (uint32_t t0 = 0, round = 0; t0 < len; t0 += EX_WG, round++) {
+  for (uint32_t t0 = 0, round = 0; t0 < len; t0 += ROW_WG, round++) {
     const uint32_t t = t0 + threadIdx.x;
     const bool valid = t < len;
     uint32_t r = 0xffffffffu;
@@ -404,21 +258,6 @@ ex_reduce_lds_kernel(const uint64_t *estart, const uint32_t *hit, const uint32_t
       atomicAdd(val_out + c + rank, sum);
   }
 }
-
-uint32_t blocks_for(uint64_t n)
-{
-  return (uint32_t)((n + EX_WG - 1) / EX_WG);
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-/* a row beyond LDS as ex_group_short_kernel listed it, and where its cells go */
-struct LongRow {
-  uint64_t start, len, row, cell0;
-};
 
 int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *rep_out,
                    uint64_t *value_out, uint64_t *n_cells_out, bool on_device)
@@ -486,7 +325,7 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     rep_bits++;
   if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
   if (n_long) {
-    if ((rc = dev_alloc(c, long_desc.b, (size_t)(3 * n_long)))) return rc;
+    if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
     if ((rc = dev_alloc(c, key_a.b, (size_t)longest))) return rc;
     if ((rc = dev_alloc(c, key_b.b, (size_t)longest))) return rc;
     if ((rc = dev_alloc(c, hit_b.b, (size_t)longest))) return rc;
@@ -495,28 +334,16 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
                                                   rep_bits, c->stream));
     if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
   }
-  unsigned long long *list_ctr = e.census.p + 3;       /* (zero since the census) */
-  hipLaunchKernelGGL(ex_group_short_kernel, dim3(blocks_for(n1 + 1)), dim3(EX_WG), 0, c->stream, estart, hit, rep2, n1,
-                     ncell, big_rows.b.p, n_big, long_desc.b.p, n_long, list_ctr);
-  HIP_TRY(c, hipGetLastError());
-  if (n_big) {
-    hipLaunchKernelGGL(ex_group_lds_kernel, dim3((uint32_t)n_big), dim3(EX_WG), 0, c->stream, estart, hit, rep2,
-                       big_rows.b.p, ncell);
-    HIP_TRY(c, hipGetLastError());
-  }
-  std::vector<LongRow> lr((size_t)n_long);
+  const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, e.census.p + 3};   /* (counters: zero) */
+  if ((rc = rows_sort(c, estart, hit, n1, lists, ExRows{rep2, ncell})))
+    return rc;
+  std::vector<LongRow> lr;
   if (n_long) {
-    std::vector<unsigned long long> desc((size_t)(3 * n_long));
-    HIP_TRY(c, hipMemcpyAsync(desc.data(), long_desc.b.p, desc.size() * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint64_t k = 0; k < n_long; k++) {
-      lr[k] = LongRow{desc[3 * k], desc[3 * k + 1], desc[3 * k + 2], 0};
-      const LongRow &r = lr[k];
-      if (r.len > longest || r.start + r.len > total || r.row >= n1)
-        return fail(c, CMPR_EDEVICE, "cmpr_existence_csr: a listed row lies outside the hits");
-      hipLaunchKernelGGL(ex_gather_rep_kernel, dim3(blocks_for(r.len)), dim3(EX_WG), 0, c->stream, hit + r.start, r.len,
-                         rep2, key_a.b.p);
+    if ((rc = rows_fetch_long(c, lists, longest, total, n1, "cmpr_existence_csr", lr)))
+      return rc;
+    for (const LongRow &r : lr) {
+      hipLaunchKernelGGL(ex_gather_rep_kernel, dim3(blocks_for(r.len, ROW_WG)), dim3(ROW_WG), 0, c->stream, hit + r.start,
+                         r.len, rep2, key_a.b.p);
       HIP_TRY(c, hipGetLastError());
       size_t b = sort_bytes;
       HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(sort_tmp.b.p, b, (const uint32_t *)key_a.b.p, key_b.b.p,
@@ -524,8 +351,8 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
                                                     rep_bits, c->stream));
       HIP_TRY(c, hipMemcpyAsync(hit + r.start, hit_b.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                                 c->stream));
-      hipLaunchKernelGGL(ex_count_heads_kernel, dim3(blocks_for(r.len)), dim3(EX_WG), 0, c->stream, key_b.b.p, r.len,
-                         ncell + r.row);
+      hipLaunchKernelGGL(ex_count_heads_kernel, dim3(blocks_for(r.len, ROW_WG)), dim3(ROW_WG), 0, c->stream, key_b.b.p,
+                         r.len, ncell + r.row);
       HIP_TRY(c, hipGetLastError());
     }
   }
@@ -539,8 +366,9 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
                                               (size_t)(n1 + 1), c->stream));
   unsigned long long cells = 0;
   HIP_TRY(c, hipMemcpyAsync(&cells, cstart + n1, sizeof cells, hipMemcpyDeviceToHost, c->stream));
-  for (LongRow &r : lr)
-    HIP_TRY(c, hipMemcpyAsync(&r.cell0, cstart + r.row, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  std::vector<uint64_t> cell0(lr.size());              /* where the cells of the rows beyond LDS go */
+  for (size_t k = 0; k < lr.size(); k++)
+    HIP_TRY(c, hipMemcpyAsync(&cell0[k], cstart + lr[k].row, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
   if (!on_device && row_start_out)
     HIP_TRY(c, hipMemcpyAsync(row_start_out, cstart, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
                               c->stream));
@@ -568,17 +396,17 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
       return fail(c, CMPR_ESTATE, "cmpr_existence_csr: the reference set has no counts");
     if ((rc = dev_alloc(c, cnt1.b, (size_t)n1))) return rc;
     const uint64_t nslots = (uint64_t)c->ntiles * WAVE;
-    hipLaunchKernelGGL(ex_cnt1_kernel, dim3(blocks_for(nslots)), dim3(EX_WG), 0, c->stream, c->tiles.p, c->qrec.p,
-                       nslots, n1, cnt1.b.p);
+    hipLaunchKernelGGL(ex_cnt1_kernel, dim3(blocks_for(nslots, ROW_WG)), dim3(ROW_WG), 0, c->stream, c->tiles.p,
+                       c->qrec.p, nslots, n1, cnt1.b.p);
     HIP_TRY(c, hipGetLastError());
     S.cnt1 = cnt1.b.p;
     S.cnt2 = c->cnt2.p;
   }
-  hipLaunchKernelGGL(ex_reduce_short_kernel, dim3(blocks_for(n1)), dim3(EX_WG), 0, c->stream, estart, hit, rep2, n1,
-                     cstart, d_rep, d_val, S);
+  hipLaunchKernelGGL(ex_reduce_short_kernel, dim3(blocks_for(n1, ROW_WG)), dim3(ROW_WG), 0, c->stream, estart, hit, rep2,
+                     n1, cstart, d_rep, d_val, S);
   HIP_TRY(c, hipGetLastError());
   if (n_big) {
-    hipLaunchKernelGGL(ex_reduce_lds_kernel, dim3((uint32_t)n_big), dim3(EX_WG), 0, c->stream, estart, hit, rep2,
+    hipLaunchKernelGGL(ex_reduce_lds_kernel, dim3((uint32_t)n_big), dim3(ROW_WG), 0, c->stream, estart, hit, rep2,
                        big_rows.b.p, cstart, d_rep, d_val, S);
     HIP_TRY(c, hipGetLastError());
   }
@@ -591,16 +419,17 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
                                                  (size_t)longest, c->stream));
     if ((rc = dev_alloc(c, reduce_tmp.b, reduce_bytes))) return rc;
     if ((rc = dev_alloc(c, runs.b, 1))) return rc;
-    for (const LongRow &r : lr) {
-      if (r.cell0 > cells)
+    for (size_t k = 0; k < lr.size(); k++) {
+      const LongRow &r = lr[k];
+      if (cell0[k] > cells)
         return fail(c, CMPR_EDEVICE, "cmpr_existence_csr: a listed row lies outside the cells");
-      hipLaunchKernelGGL(ex_gather_rep_kernel, dim3(blocks_for(r.len)), dim3(EX_WG), 0, c->stream, hit + r.start, r.len,
-                         rep2, key_a.b.p);
+      hipLaunchKernelGGL(ex_gather_rep_kernel, dim3(blocks_for(r.len, ROW_WG)), dim3(ROW_WG), 0, c->stream, hit + r.start,
+                         r.len, rep2, key_a.b.p);
       HIP_TRY(c, hipGetLastError());
       size_t b = reduce_bytes;
-      HIP_TRY(c, hipcub::DeviceReduce::ReduceByKey(reduce_tmp.b.p, b, (const uint32_t *)key_a.b.p, d_rep + r.cell0,
+      HIP_TRY(c, hipcub::DeviceReduce::ReduceByKey(reduce_tmp.b.p, b, (const uint32_t *)key_a.b.p, d_rep + cell0[k],
                                                    ScoreIt(hit + r.start, ExScoreOfHit{S, S.cnt1 ? S.cnt1 + r.row : nullptr}),
-                                                   d_val + r.cell0, runs.b.p, hipcub::Sum(), (size_t)r.len, c->stream));
+                                                   d_val + cell0[k], runs.b.p, hipcub::Sum(), (size_t)r.len, c->stream));
     }
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -615,17 +444,6 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     c->ex_ms[4] = ms_since(t0);
   }
   return CMPR_OK;
-}
-
-/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-template <typename F>
-int guarded(cmpr_context *c, F call)
-{
-  try {
-    return call();
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
 }
 
 }  // namespace

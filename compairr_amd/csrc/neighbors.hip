@@ -20,67 +20,43 @@
  * row lengths again (fill, nb_cursor_kernel).
  *
  * Ordering the rows.  Which hit takes which place of its row depends on the schedule; the set of hits of a
- * row does not, and a row never holds a sequence twice, so sorting the rows makes the result unique.  Four
- * paths by row length n, the thresholds being what each path holds:
- *
- *   n <= 1              nothing.  Real data: most rows.
- *   n <= LANE_MAX = 8   one lane per row, the row in eight registers, a 19-comparator network
- *                       (nb_sort_short_kernel).  Eight is where real data ends (20 000 CDR3 against themselves,
- *                       d = 1 -i: longest row 9), a network of 16 costs 60 comparators for every lane of a
- *                       wave that has one such row, and neighbouring lanes read neighbouring rows.
- *   n <= WAVE = 64      one element per lane, a bitonic sort with 21 shuffle steps; the wave takes the rows
- *                       of its 64 lanes that need it one after the other (same kernel).  No LDS, no workgroup.
- *   n <= LDS_MAX = 8192 one workgroup of 256 lanes per row, bitonic in 32 KiB of LDS over the next power of
- *                       two (nb_sort_lds_kernel).  32 KiB of the CU's 160 leaves room for four such workgroups
- *                       per CU (with 40 960 words one would fit); at 8192 words a single-workgroup bitonic
- *                       sort is 91 passes of 32 elements per lane, and beyond that the device-wide radix
- *                       sort, which has the whole GPU for one row, is the better tool.  These rows are listed
- *                       by the short-row kernel (big_rows: the census sized the list exactly), so rows of 0 and
- *                       1 cost a lane, not a workgroup.
- *   longer              no limit: the rows' (start, length) are listed too, come to the host (16 bytes per
- *                       such row) and each goes through hipcub::DeviceRadixSort into a scratch buffer the
- *                       size of the longest of them and back.  A handful of rows in skewed data.
+ * row does not, and a row never holds a sequence twice, so sorting the rows makes the result unique.  The four
+ * paths by row length and their thresholds (8, 64, 8192) are those of csr_rows.h, with the hit itself as the key:
+ * rows of up to 8192 hits by rows_sort (a lane, a wave, a workgroup in 32 KiB of LDS), and each longer row
+ * through hipcub::DeviceRadixSort into a scratch buffer the size of the longest of them and back.
  *
  * Device memory for the duration of the call: 4 bytes per query (degrees), the scan's scratch, 4 bytes per
- * row beyond a wave, and for rows beyond LDS 16 bytes each plus the longest of them once plus the radix
+ * row beyond a wave, and for rows beyond LDS 24 bytes each plus the longest of them once plus the radix
  * sort's scratch.  The host variant adds what the device variant is handed: 8 bytes per query for row_start
  * and 4 per edge for the hits.  Everything is freed before the call returns, also when it fails.
  *
  * cmpr_neighbor_edges (context.h) hands count, scan and fill -- the rows not ordered -- to a caller inside the
  * library that orders them its own way (existence.hip).
  */
-#include "context.h"
+#include "csr_rows.h"
 
 #include <hipcub/hipcub.hpp>
-
-#include <chrono>
-#include <new>
 
 using namespace cmpr;
 
 namespace {
 
-constexpr uint32_t NB_WG = 256;
-constexpr uint32_t LANE_MAX = 8;
-constexpr uint32_t LDS_MAX = 8192;
-constexpr uint32_t NB_PAD = 0xffffffffu;   /* behind a row's end while it is sorted: no sequence number (n2 < 2^32 - 64) */
-
-template <typename T>
-struct Tmp {
-  DevBuf<T> b;
-  ~Tmp() { b.release(); }
-};
-
-struct U32To64 {
-  __host__ __device__ unsigned long long operator()(uint32_t v) const { return v; }
+/* the rows ordered by the hit: nothing to gather, nothing kept (csr_rows.h) */
+struct NbRows {
+  using Key = uint32_t;
+  static constexpr Key  PAD = 0xffffffffu;   /* no sequence number (n2 < 2^32 - 64) */
+  static constexpr bool COUNT_HEADS = false;
+  __device__ Key key_of(uint32_t hit) const { return hit; }
+  __device__ static uint32_t hit_of(Key key) { return key; }
+  __device__ static bool same_run(Key, Key) { return true; }
 };
 
 /* census[0] rows longer than a wave, [1] of those the rows longer than LDS, [2] the longest row when it is
    longer than LDS.  Real data has no such row: a wave that sees none touches nothing. */
-__global__ void __launch_bounds__(NB_WG)
+__global__ void __launch_bounds__(ROW_WG)
 nb_census_kernel(const uint32_t *degree, uint64_t n, unsigned long long *census)
 {
-  const uint64_t i = (uint64_t)blockIdx.x * NB_WG + threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
   const uint32_t d = i < n ? degree[i] : 0u;
   const uint64_t big = __ballot(d > WAVE);
   if (!big)
@@ -96,128 +72,12 @@ nb_census_kernel(const uint32_t *degree, uint64_t n, unsigned long long *census)
 }
 
 /* the fill step's cursors: the hits of row i still to come */
-__global__ void __launch_bounds__(NB_WG)
+__global__ void __launch_bounds__(ROW_WG)
 nb_cursor_kernel(const uint64_t *row_start, uint32_t *degree, uint64_t n)
 {
-  const uint64_t i = (uint64_t)blockIdx.x * NB_WG + threadIdx.x;
+  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
   if (i < n)
     degree[i] = (uint32_t)(row_start[i + 1] - row_start[i]);
-}
-
-__device__ __forceinline__ void nb_cx(uint32_t &a, uint32_t &b)
-{
-  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
-  a = lo;
-  b = hi;
-}
-
-/* One lane per row.  Rows of 2 .. LANE_MAX: sorted by their lane.  Rows of up to WAVE: by the wave, one after
-   the other.  Longer rows: listed for nb_sort_lds_kernel (big_rows, as many as the census counted) or, beyond
-   LDS, with start and length for the host (long_desc); the order of the lists is that of arrival and does not
-   show in the result. */
-__global__ void __launch_bounds__(NB_WG)
-nb_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, uint32_t *big_rows, uint64_t big_cap,
-                     unsigned long long *long_desc, uint64_t long_cap, unsigned long long *list_ctr)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * NB_WG + threadIdx.x;
-  const uint32_t lane = lane_id();
-  uint64_t start = 0, len = 0;
-  if (i < n) {
-    start = row_start[i];
-    len = row_start[i + 1] - start;
-  }
-  if (len >= 2 && len <= LANE_MAX) {
-    uint32_t v[LANE_MAX];
-#pragma unroll
-    for (uint32_t k = 0; k < LANE_MAX; k++)
-      v[k] = k < len ? hit[start + k] : NB_PAD;
-    /* 19 comparators in 6 layers (Knuth, TAOCP 3, 5.3.4) */
-    nb_cx(v[0], v[1]); nb_cx(v[2], v[3]); nb_cx(v[4], v[5]); nb_cx(v[6], v[7]);
-    nb_cx(v[0], v[2]); nb_cx(v[1], v[3]); nb_cx(v[4], v[6]); nb_cx(v[5], v[7]);
-    nb_cx(v[1], v[2]); nb_cx(v[5], v[6]); nb_cx(v[0], v[4]); nb_cx(v[3], v[7]);
-    nb_cx(v[1], v[5]); nb_cx(v[2], v[6]);
-    nb_cx(v[1], v[4]); nb_cx(v[3], v[6]);
-    nb_cx(v[2], v[4]); nb_cx(v[3], v[5]);
-    nb_cx(v[3], v[4]);
-#pragma unroll
-    for (uint32_t k = 0; k < LANE_MAX; k++)
-      if (k < len)
-        hit[start + k] = v[k];
-  } else if (len > WAVE) {
-    if (len > LDS_MAX) {
-      const unsigned long long k = atomicAdd(list_ctr + 1, 1ull);
-      if (k < long_cap) {
-        long_desc[2 * k] = start;
-        long_desc[2 * k + 1] = len;
-      }
-    } else {
-      const unsigned long long k = atomicAdd(list_ctr + 0, 1ull);
-      if (k < big_cap)
-        big_rows[k] = (uint32_t)i;
-    }
-  }
-  /* the wave's rows of LANE_MAX + 1 .. WAVE */
-  uint64_t todo = __ballot(len > LANE_MAX && len <= WAVE);
-  while (todo) {
-    const uint32_t src = (uint32_t)__ffsll((unsigned long long)todo) - 1u;
-    todo &= todo - 1;
-    const uint64_t s = __shfl(start, src, WAVE);
-    const uint32_t m = (uint32_t)__shfl(len, src, WAVE);
-    uint32_t v = lane < m ? hit[s + lane] : NB_PAD;
-    for (uint32_t k = 2; k <= WAVE; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        const uint32_t other = __shfl_xor(v, j, WAVE);
-        const bool up = (lane & k) == 0, low = (lane & j) == 0;
-        v = (up == low) ? (v < other ? v : other) : (v < other ? other : v);
-      }
-    if (lane < m)
-      hit[s + lane] = v;
-  }
-}
-
-/* One workgroup per listed row of WAVE + 1 .. LDS_MAX hits: bitonic in LDS over the next power of two. */
-__global__ void __launch_bounds__(NB_WG)
-nb_sort_lds_kernel(const uint64_t *row_start, uint32_t *hit, const uint32_t *big_rows)
-{
-  __shared__ uint32_t s[LDS_MAX];
-  const uint32_t row = big_rows[blockIdx.x];
-  const uint64_t start = row_start[row];
-  const uint64_t len64 = row_start[row + 1] - start;
-  if (len64 > LDS_MAX)
-    return;                                  /* (the list holds no such row; nothing is indexed beyond s) */
-  const uint32_t len = (uint32_t)len64;
-  uint32_t np = 2 * WAVE;
-  while (np < len)
-    np <<= 1;
-  for (uint32_t t = threadIdx.x; t < np; t += NB_WG)
-    s[t] = t < len ? hit[start + t] : NB_PAD;
-  __syncthreads();
-  for (uint32_t k = 2; k <= np; k <<= 1)
-    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-      for (uint32_t t = threadIdx.x; t < np; t += NB_WG) {
-        const uint32_t u = t ^ j;
-        if (u > t) {
-          const uint32_t a = s[t], b = s[u];
-          if (((t & k) == 0) == (a > b)) {
-            s[t] = b;
-            s[u] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  for (uint32_t t = threadIdx.x; t < len; t += NB_WG)
-    hit[start + t] = s[t];
-}
-
-uint32_t blocks_for(uint64_t n)
-{
-  return (uint32_t)((n + NB_WG - 1) / NB_WG);
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0)
-{
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 /* ---- count; scan, census ---- the degrees and the scan's scratch are allocated here; row_start[n1 + 1] is device
@@ -252,7 +112,7 @@ int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *h
                                               (size_t)(n1 + 1), c->stream));
   HIP_TRY(c, hipMemsetAsync(e.census.p, 0, 5 * sizeof(unsigned long long), c->stream));
   if (n1) {
-    hipLaunchKernelGGL(nb_census_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, degree, n1, e.census.p);
+    hipLaunchKernelGGL(nb_census_kernel, dim3(blocks_for(n1, ROW_WG)), dim3(ROW_WG), 0, c->stream, degree, n1, e.census.p);
     HIP_TRY(c, hipGetLastError());
   }
   unsigned long long total = 0, seen[3] = {0, 0, 0};
@@ -282,7 +142,7 @@ int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32
   }
   const auto t0 = std::chrono::steady_clock::now();
   if ((rc = cmpr_neighbor_step(c, degree, row_start, hit, [&]() -> int {
-         hipLaunchKernelGGL(nb_cursor_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, row_start, degree, n1);
+         hipLaunchKernelGGL(nb_cursor_kernel, dim3(blocks_for(n1, ROW_WG)), dim3(ROW_WG), 0, c->stream, row_start, degree, n1);
          HIP_TRY(c, hipGetLastError());
          return CMPR_OK;
        })))
@@ -337,7 +197,7 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   }
   if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
   if (n_long) {
-    if ((rc = dev_alloc(c, long_desc.b, (size_t)(2 * n_long)))) return rc;
+    if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
     if ((rc = dev_alloc(c, scratch.b, (size_t)longest))) return rc;
     HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
                                                  (size_t)longest, 0, 32, c->stream));
@@ -348,28 +208,18 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
 
   /* ---- order the rows ---- */
   auto t0 = std::chrono::steady_clock::now();
-  unsigned long long *list_ctr = e.census.p + 3;       /* (zero since the census) */
-  hipLaunchKernelGGL(nb_sort_short_kernel, dim3(blocks_for(n1)), dim3(NB_WG), 0, c->stream, row_start, hit, n1,
-                     big_rows.b.p, n_big, long_desc.b.p, n_long, list_ctr);
-  HIP_TRY(c, hipGetLastError());
-  if (n_big) {
-    hipLaunchKernelGGL(nb_sort_lds_kernel, dim3((uint32_t)n_big), dim3(NB_WG), 0, c->stream, row_start, hit,
-                       big_rows.b.p);
-    HIP_TRY(c, hipGetLastError());
-  }
+  const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, e.census.p + 3};   /* (counters: zero) */
+  if ((rc = rows_sort(c, row_start, hit, n1, lists, NbRows{})))
+    return rc;
   if (n_long) {
-    std::vector<unsigned long long> desc((size_t)(2 * n_long));
-    HIP_TRY(c, hipMemcpyAsync(desc.data(), long_desc.b.p, desc.size() * sizeof(unsigned long long),
-                              hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (uint64_t k = 0; k < n_long; k++) {
-      const uint64_t start = desc[2 * k], len = desc[2 * k + 1];
-      if (len > longest || start + len > total)
-        return fail(c, CMPR_EDEVICE, "cmpr_neighbors: a listed row lies outside the hits");
+    std::vector<LongRow> lr;
+    if ((rc = rows_fetch_long(c, lists, longest, total, n1, "cmpr_neighbors", lr)))
+      return rc;
+    for (const LongRow &r : lr) {
       size_t b = sort_bytes;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + start), scratch.b.p,
-                                                   (size_t)len, 0, 32, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(hit + start, scratch.b.p, (size_t)len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
+                                                   (size_t)r.len, 0, 32, c->stream));
+      HIP_TRY(c, hipMemcpyAsync(hit + r.start, scratch.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                                 c->stream));
     }
   }
@@ -378,17 +228,6 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->nb_ms[3] = ms_since(t0);
   return CMPR_OK;
-}
-
-/* the header promises CMPR_ENOMEM, not an exception across the C boundary */
-template <typename F>
-int guarded(cmpr_context *c, F call)
-{
-  try {
-    return call();
-  } catch (const std::bad_alloc &) {
-    return fail(c, CMPR_ENOMEM, "out of host memory");
-  }
 }
 
 }  // namespace

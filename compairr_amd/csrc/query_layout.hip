@@ -2039,12 +2039,6 @@ unpack_kernel(const unsigned char *rec, uint64_t n, uint32_t record_bytes, const
   }
 }
 
-template <typename T>
-struct Tmp {
-  DevBuf<T> b;
-  ~Tmp() { b.release(); }
-};
-
 inline uint32_t blocks_for(uint64_t n)
 {
   return (uint32_t)std::max<uint64_t>(1, (n + 255) / 256);
@@ -2211,10 +2205,6 @@ static int arena_fit(cmpr_context *c, DevArena &A, size_t bytes)
   A.cap = want;
   return CMPR_OK;
 }
-
-struct U32To64 {
-  __host__ __device__ unsigned long long operator()(const uint32_t &x) const { return x; }
-};
 
 /* sum of n uint32 as 64 bits into *out (the 32-bit prefix sums beside it may not wrap
    unnoticed: ADVICE r2) */

@@ -26,12 +26,6 @@ inline uint32_t blocks_for(uint64_t n)
   return (uint32_t)std::max<uint64_t>(1, (n + 255) / 256);
 }
 
-template <typename T>
-struct Tmp {
-  DevBuf<T> b;
-  ~Tmp() { b.release(); }
-};
-
 /* lengths: one counter per length (LDS copy per workgroup when they fit) */
 __global__ void __launch_bounds__(256)
 length_hist_kernel(const uint64_t *off, uint64_t n, uint32_t nh, uint32_t *hist)

@@ -308,7 +308,7 @@ int cmpr_overlap_pairs(cmpr_context *ctx, uint64_t capacity, uint32_t *query_out
  * into its row, and sorts each row in place (compairr_amd/csrc/neighbors.hip): two steps where
  * cmpr_overlap_pairs() runs one, and no per-edge memory beyond the caller's hit_out (the host variant holds the
  * two arrays on the device for the duration of the call).  Temporaries: 4 bytes per query, the scratch of the
- * sum, 4 bytes per row of more than 64 hits, and for rows of more than 8192 hits 16 bytes each plus the longest
+ * sum, 4 bytes per row of more than 64 hits, and for rows of more than 8192 hits 24 bytes each plus the longest
  * of them once.  Everything is freed before the call returns, also when it fails.
  *
  * Synchronous; needs both resident sets (CMPR_ESTATE as for cmpr_overlap_matrix()).  With the tunable

@@ -142,6 +142,31 @@ def hub_want(n_rep, d):
     return oracle_cell_csr(s1, s2, hub_options(d))
 
 
+# ---- 3. rows of exactly the lengths at which the path changes ----
+
+EDGE_REPS = [1, 200]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_sets(n_rep):
+    """_neighbors.edge_rows() with its set 2 renumbered into n_rep repertoires (1: one run per row, across every
+    wave and round of the row of 8192 hits) and both sets given counts of 1 .. 9"""
+    s1, s2 = _neighbors.edge_rows()
+    rng = np.random.default_rng(173)
+    rep = rng.integers(0, n_rep, size=s2.n, dtype=np.uint32)
+    rep[:n_rep] = np.arange(n_rep)
+    cnt2 = rng.integers(1, 10, size=s2.n).astype(np.uint64)
+    cnt1 = rng.integers(1, 10, size=s1.n).astype(np.uint64)
+    return (dataclasses.replace(s1, count=cnt1),
+            dataclasses.replace(s2, repertoire=rep, count=cnt2,
+                                repertoire_ids=["H%d" % (k + 1) for k in range(n_rep)]))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_want(n_rep):
+    return oracle_cell_csr(*edge_sets(n_rep), _neighbors.edge_options())
+
+
 # ---- the yardstick a second way: the neighbour lists reduced by repertoire in numpy ----
 
 def cells_of_neighbors(set1, set2, opt):

@@ -97,12 +97,8 @@ def _set_of_rows(rows, seed, n_rep):
                          ["H%d" % (k + 1) for k in range(n_rep)], ["V0"], ["J0"], AA)
 
 
-@functools.lru_cache(maxsize=None)
-def hub_sets():
-    """set 2: every sequence within Hamming distance 2 of HUB (1 + 16 x 19 + 120 x 361 = 43 625) and 1 375
-    uniform random strangers, shuffled; set 1: the hub, a sequence at distance 1, one at distance 2, and 61
-    random strangers.  One V gene, one J gene, three repertoires."""
-    hub = np.array([AA.index(ch) for ch in HUB], dtype=np.uint8)
+def ball_of(hub):
+    """every sequence within Hamming distance 2 of `hub`, the hub first"""
     L = len(hub)
     ball = [hub.copy()]
     for p in range(L):
@@ -118,7 +114,18 @@ def hub_sets():
         block[:, p], block[:, q] = rs[:, 0], rs[:, 1]
         ball.extend(block)
     ball = np.array(ball, dtype=np.uint8)
-    assert len(ball) == 43_625
+    assert len(ball) == 1 + L * 19 + L * (L - 1) // 2 * 361
+    return ball
+
+
+@functools.lru_cache(maxsize=None)
+def hub_sets():
+    """set 2: every sequence within Hamming distance 2 of HUB (1 + 16 x 19 + 120 x 361 = 43 625) and 1 375
+    uniform random strangers, shuffled; set 1: the hub, a sequence at distance 1, one at distance 2, and 61
+    random strangers.  One V gene, one J gene, three repertoires."""
+    hub = np.array([AA.index(ch) for ch in HUB], dtype=np.uint8)
+    L = len(hub)
+    ball = ball_of(hub)
     rng = np.random.default_rng(16)
     rows2 = np.concatenate([ball, rng.integers(0, 20, size=(1_375, L), dtype=np.uint8)])
     rows2 = rows2[rng.permutation(len(rows2))]
@@ -136,3 +143,38 @@ def hamming_csr(set1, set2, d):
     b = set2.residues.reshape(-1, L)
     q, h = np.nonzero((a[:, None, :] != b[None, :, :]).sum(axis=2) <= d)
     return csr_of_pairs(set1.n, np.stack([q, h], axis=1))
+
+
+# ---- 3. rows of exactly the lengths at which the sorting path changes ----
+
+EDGE_ROWS = [0, 1, 2, 8, 9, 64, 65, 8192, 8193]      # either side of 1, LANE_MAX = 8, WAVE = 64, LDS_MAX = 8192
+
+
+def edge_options(**more):
+    return Options(differences=2, n_v_genes=1, n_j_genes=1, **more)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_rows():
+    """set 1: nine hubs (random 16-mers, pairwise at Hamming distance >= 5: their radius-2 balls are disjoint, so
+    at d = 2 a query matches only members of its own ball), then 61 random strangers -- two waves, the rows of 9
+    and of 64 in one; set 2: of the ball of hub k its first EDGE_ROWS[k] members in a seeded order, and 1 000
+    random strangers, shuffled.  One V gene, one J gene, three repertoires, every count 1."""
+    rng = np.random.default_rng(17)
+    L = len(HUB)
+    hubs = rng.integers(0, 20, size=(len(EDGE_ROWS), L), dtype=np.uint8)
+    apart = (hubs[:, None, :] != hubs[None, :, :]).sum(axis=2)
+    assert (apart[~np.eye(len(hubs), dtype=bool)] >= 5).all()
+    members = []
+    for hub, n in zip(hubs, EDGE_ROWS):
+        ball = ball_of(hub)
+        members.append(ball[rng.permutation(len(ball))[:n]])
+    rows2 = np.concatenate(members + [rng.integers(0, 20, size=(1_000, L), dtype=np.uint8)])
+    rows2 = rows2[rng.permutation(len(rows2))]
+    rows1 = np.concatenate([hubs, rng.integers(0, 20, size=(61, L), dtype=np.uint8)])
+    return _set_of_rows(rows1, 171, 3), _set_of_rows(rows2, 172, 3)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_want():
+    return oracle_csr(*edge_rows(), edge_options())

@@ -83,6 +83,22 @@ def test_the_two_yardsticks_agree_on_the_long_row_with_counts():
     assert np.array_equal(_existence.oracle_cells(s1, s2, opt), _existence.cells_of_neighbors(s1, s2, opt))
 
 
+@pytest.mark.parametrize("n_rep", _existence.EDGE_REPS)
+def test_oracle_figures_of_the_rows_at_the_thresholds(n_rep):
+    s1, s2 = _existence.edge_sets(n_rep)
+    opt = _neighbors.edge_options()
+    assert s2.n_repertoires == n_rep
+    edges = _neighbors.oracle_csr(s1, s2, opt)[0]
+    assert np.diff(edges.astype(np.int64)).tolist() == _neighbors.EDGE_ROWS + [0] * 61
+    want = _existence.edge_want(n_rep)
+    _existence.assert_is_cell_csr(*want, s1.n, n_rep)
+    second = _existence.csr_of_dense(_existence.cells_of_neighbors(s1, s2, opt))
+    for a, b in zip(want, second):
+        assert np.array_equal(a, b)
+    if n_rep == 1:
+        assert np.diff(want[0].astype(np.int64)).tolist() == [0] + [1] * 8 + [0] * 61
+
+
 def test_header_binding_and_library_carry_the_entry_points():
     with open(HEADER) as fh:
         text = fh.read()

@@ -100,6 +100,18 @@ def test_the_long_row(n_rep, d):
     assert_equal_cells(got, want, s1.n, n_rep)
 
 
+@pytest.mark.parametrize("n_rep", _existence.EDGE_REPS)
+def test_rows_at_the_thresholds(n_rep):
+    """rows of exactly 0, 1, 2, 8, 9, 64, 65, 8192 and 8193 hits (_neighbors.edge_rows), in both passes.  One
+    repertoire: one run per row, across every wave and round of the row of 8192 hits; 200: ranks beyond a round."""
+    s1, s2 = _existence.edge_sets(n_rep)
+    want = _existence.edge_want(n_rep)
+    with resident(_neighbors.edge_options(device=0), s1, s2) as h:
+        got = h.existence_csr()
+        assert h.stats().matches == sum(_neighbors.EDGE_ROWS)
+    assert_equal_cells(got, want, s1.n, n_rep)
+
+
 # ---- 3. the capacity protocol ----
 
 def raw_existence(h, capacity, row_start=None, rep=None, val=None, want_count=True):

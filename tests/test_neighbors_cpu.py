@@ -55,6 +55,16 @@ def test_oracle_equals_brute_force_on_the_long_row():
         assert np.diff(want[0].astype(np.int64)).tolist() == rows + [0] * 61
 
 
+def test_rows_at_the_thresholds_have_the_stated_lengths():
+    """no stranger lies in a ball and no ball touches another: the rows are exactly EDGE_ROWS, then 61 empty ones"""
+    s1, s2 = _neighbors.edge_rows()
+    assert s1.n == 70 and s2.n == sum(_neighbors.EDGE_ROWS) + 1_000
+    want = _neighbors.edge_want()
+    brute = _neighbors.hamming_csr(s1, s2, 2)
+    assert np.array_equal(want[0], brute[0]) and np.array_equal(want[1], brute[1])
+    assert np.diff(want[0].astype(np.int64)).tolist() == _neighbors.EDGE_ROWS + [0] * 61
+
+
 def test_header_binding_and_library_carry_the_entry_points():
     with open(HEADER) as fh:
         text = fh.read()

@@ -74,6 +74,15 @@ def test_one_row_longer_than_lds(d, rows):
     assert_equal_csr(compairr_amd.neighbors(s1, s2, opt), want, s1.n)
 
 
+def test_rows_at_the_thresholds():
+    """rows of exactly 0, 1, 2, 8, 9, 64, 65, 8192 and 8193 hits: either side of every length at which the sorting
+    path changes (csr_rows.h), the rows of 9 and 64 hits in one wave"""
+    s1, s2 = _neighbors.edge_rows()
+    want = _neighbors.edge_want()
+    assert np.diff(want[0].astype(np.int64)).tolist() == _neighbors.EDGE_ROWS + [0] * 61
+    assert_equal_csr(compairr_amd.neighbors(s1, s2, _neighbors.edge_options(device=0)), want, s1.n)
+
+
 # ---- 3. the capacity protocol ----
 
 def raw_neighbors(h, capacity, row_start=None, hits=None, want_count=True):

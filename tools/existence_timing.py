@@ -21,6 +21,9 @@ profiles/r12/existence.txt).  The one condition is that of (a); the rest is a re
         * the route that exists without the call: a context with options.existence, cmpr_overlap_matrix_device
           into an n x R2 torch buffer, torch.nonzero and a gather; the two results must be equal.
 
+Without --against, (a) is skipped and (b) times the library the environment names (COMPAIRR_HIP_LIB, e.g. the parent
+commit's build, for the same report of the parent), or this tree's when it names none.
+
 Every step that uses the GPU is a child process under its own time limit; a step that fails ends the run."""
 
 import argparse
@@ -147,6 +150,11 @@ def main():
         return p.returncode or 1
 
     branch_env = {k: v for k, v in os.environ.items() if k != "COMPAIRR_HIP_LIB"}
+    # (b) times this tree's library beside a comparison; without --against, whichever library the caller's
+    # environment names (COMPAIRR_HIP_LIB: the parent commit's build, for the same report of the parent)
+    timed_env = branch_env if args.against else dict(os.environ)
+    if not args.against and os.environ.get("COMPAIRR_HIP_LIB"):
+        lines.append("(b) is of the library COMPAIRR_HIP_LIB names, not of this tree's")
 
     # (a) bench.py, parent and branch in turn
     if args.against:
@@ -181,7 +189,7 @@ def main():
     for n in [int(x) for x in args.sizes.split(",") if x]:
         for n_rep in [int(x) for x in args.reps_of_set.split(",") if x]:
             p = subprocess.run(["timeout", "-k", "10", "400"] + me + ["--measure", "%d,%d" % (n, n_rep), "--reps", str(args.reps)],
-                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=branch_env)
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=timed_env)
             if p.returncode != 0:
                 return failed("timing child (n = %d, %d repertoires)" % (n, n_rep), p)
             r = json.loads(p.stdout.decode().strip().splitlines()[-1])

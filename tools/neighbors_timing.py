@@ -19,6 +19,9 @@ that of (a); the rest is a report.
         * the route to the same CSR that exists without it: cmpr_overlap_pairs to the host (count, then list),
           np.lexsort, np.bincount + np.cumsum -- clocked in its parts; the two results must be equal.
 
+Without --against, (a) is skipped and (b) times the library the environment names (COMPAIRR_HIP_LIB, e.g. the parent
+commit's build, for the same report of the parent), or this tree's when it names none.
+
 Every step that uses the GPU is a child process under its own time limit; a step that fails ends the run."""
 
 import argparse
@@ -131,6 +134,11 @@ def main():
         return p.returncode or 1
 
     branch_env = {k: v for k, v in os.environ.items() if k != "COMPAIRR_HIP_LIB"}
+    # (b) times this tree's library beside a comparison; without --against, whichever library the caller's
+    # environment names (COMPAIRR_HIP_LIB: the parent commit's build, for the same report of the parent)
+    timed_env = branch_env if args.against else dict(os.environ)
+    if not args.against and os.environ.get("COMPAIRR_HIP_LIB"):
+        lines.append("(b) is of the library COMPAIRR_HIP_LIB names, not of this tree's")
 
     # (a) bench.py, parent and branch in turn
     if args.against:
@@ -164,7 +172,7 @@ def main():
     me = [sys.executable, os.path.abspath(__file__)]
     for n in [int(x) for x in args.sizes.split(",") if x]:
         p = subprocess.run(["timeout", "-k", "10", "500"] + me + ["--measure", str(n), "--reps", str(args.reps)],
-                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=branch_env)
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=timed_env)
         if p.returncode != 0:
             return failed("timing child (n = %d)" % n, p)
         r = json.loads(p.stdout.decode().strip().splitlines()[-1])

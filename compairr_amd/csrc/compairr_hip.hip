@@ -949,6 +949,7 @@ int issue_step(cmpr_context *c, const StepArgs &a, hipStream_t st, hipEvent_t ev
     P.nb_degree = c->nb_degree;
     P.nb_row_start = c->nb_row_start;
     P.nb_hit = c->nb_hit;
+    P.nb_dist = c->nb_dist;
     if (S.deferred)
       P.pos_ctr = c->ctr_cur;
     if (c->rows && S.deferred)
@@ -1300,7 +1301,7 @@ int cmpr_check_ready(cmpr_context *c)
   return check_ready(c);
 }
 
-int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit,
+int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit, uint8_t *dist,
                        const std::function<int()> &before)
 {
   int rc = check_ready(c);
@@ -1310,7 +1311,13 @@ int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_st
      Unlike a link, a count or a placement must not be made twice: the hook runs before every attempt. */
   struct Cleanup {
     cmpr_context *c;
-    ~Cleanup() { c->pair_count = nullptr; c->nb_degree = c->nb_hit = nullptr; c->nb_row_start = nullptr; }
+    ~Cleanup()
+    {
+      c->pair_count = nullptr;
+      c->nb_degree = c->nb_hit = nullptr;
+      c->nb_row_start = nullptr;
+      c->nb_dist = nullptr;
+    }
   } cleanup{c};
   c->pair_q = c->pair_h = nullptr;
   c->pair_cap = 0;
@@ -1319,6 +1326,7 @@ int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_st
   c->nb_degree = degree;
   c->nb_row_start = row_start;
   c->nb_hit = hit;
+  c->nb_dist = hit ? dist : nullptr;
   return run_step_and_wait(c, c->matrix.p, before, no_hook);
 }
 

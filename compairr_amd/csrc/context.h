@@ -344,6 +344,7 @@ struct cmpr_context {
      ProbeParams::nb_*): the degrees / row cursors, and for the fill step the row offsets and the hits */
   uint32_t           *nb_degree = nullptr, *nb_hit = nullptr;
   const uint64_t     *nb_row_start = nullptr;
+  uint8_t            *nb_dist = nullptr;   /* fill step of cmpr_neighbors_distance only */
   double              nb_ms[4] = {};   /* host time of the last cmpr_neighbors: count | scan | fill | order */
   double              ex_ms[5] = {};   /* ... of the last cmpr_existence_csr: edges | group | count | reduce | copy-out */
   double              cl_ms[2] = {};   /* ... of the last cmpr_cluster_table: labels and sizes | the table */
@@ -531,9 +532,10 @@ int cmpr_link_step(cmpr_context *c, uint32_t *parent);
 
 /* compairr_hip.hip: the synchronous step in neighbour mode (cmpr_neighbors, neighbors.hip).  hit == NULL: the
    count step, every match adds one to degree[its query]; otherwise the fill step, every match takes a place of
-   its query's row in `hit` (kernels.h score_match).  `before` queues on the context's stream what EVERY attempt
+   its query's row in `hit` (kernels.h score_match) and, when `dist` is not NULL, writes the pair's distance to the
+   same place of `dist` (cmpr_neighbors_distance).  `before` queues on the context's stream what EVERY attempt
    of run_step_and_wait needs in front of its kernels: the degrees zeroed, or set to the row lengths. */
-int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit,
+int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_start, uint32_t *hit, uint8_t *dist,
                        const std::function<int()> &before);
 
 /* neighbors.hip: the edges of the resident sets for a caller inside the library (cmpr_existence_csr,

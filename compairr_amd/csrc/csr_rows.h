@@ -26,10 +26,12 @@
  *                       such row, rows_fetch_long) and the caller hands each to hipcub, the whole GPU for one row.
  *                       A handful of rows in skewed data.
  *
- * What differs between the callers is a policy struct `Rows`, passed to the kernels by value:
+ * What differs between the callers is a policy struct `Rows`, passed to the kernels by value.  It owns the arrays of
+ * the edges -- the hits, and whatever lies beside each hit -- and the passes know positions only:
  *
- *   Key, PAD            the sort key of a hit, and a value above every key (behind a row's end while it is sorted)
- *   key_of(hit), hit_of(key)
+ *   Key, PAD            the sort key of a position, and a value above every key (behind a row's end while it is sorted)
+ *   load(pos)           the key of what lies at position `pos` of the edges
+ *   store(pos, key)     the element that key stands for, put at `pos`
  *   COUNT_HEADS         whether the sorted row's heads -- the positions p with !same_run(key[p - 1], key[p]), and
  *                       position 0 -- are counted into ncell[row].  With it the short kernel runs over n + 1 lanes
  *                       and writes every word of ncell[0 .. n]: the heads of the rows it sorted, 0 for the listed
@@ -111,7 +113,7 @@ __device__ __forceinline__ void for_each_wave_row(uint64_t start, uint64_t len, 
    show in the result. */
 template <typename Rows>
 __global__ void __launch_bounds__(ROW_WG)
-rows_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, const RowLists L, const Rows R)
+rows_sort_short_kernel(const uint64_t *row_start, uint64_t n, const RowLists L, const Rows R)
 {
   using Key = typename Rows::Key;
   const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
@@ -126,13 +128,13 @@ rows_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, con
     Key v[LANE_MAX];
 #pragma unroll
     for (uint32_t k = 0; k < LANE_MAX; k++)
-      v[k] = k < len ? R.key_of(hit[start + k]) : Rows::PAD;
+      v[k] = k < len ? R.load(start + k) : Rows::PAD;
     row_sort8(v);
     cells = 1;
 #pragma unroll
     for (uint32_t k = 0; k < LANE_MAX; k++)
       if (k < len) {
-        hit[start + k] = Rows::hit_of(v[k]);
+        R.store(start + k, v[k]);
         if constexpr (Rows::COUNT_HEADS)
           if (k > 0 && !Rows::same_run(v[k - 1], v[k]))
             cells++;
@@ -152,7 +154,7 @@ rows_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, con
     }
   }
   for_each_wave_row(start, len, [&](uint32_t src, uint64_t s, uint32_t m) {
-    const Key v = wave_sort(lane < m ? R.key_of(hit[s + lane]) : Rows::PAD, lane);
+    const Key v = wave_sort(lane < m ? R.load(s + lane) : Rows::PAD, lane);
     if constexpr (Rows::COUNT_HEADS) {
       const Key before = __shfl_up(v, 1, WAVE);
       const uint64_t heads = __ballot(lane < m && (lane == 0 || !Rows::same_run(before, v)));
@@ -160,7 +162,7 @@ rows_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, con
         cells = (uint32_t)__popcll(heads);
     }
     if (lane < m)
-      hit[s + lane] = Rows::hit_of(v);
+      R.store(s + lane, v);
   });
   if constexpr (Rows::COUNT_HEADS)
     if (i <= n)
@@ -170,7 +172,7 @@ rows_sort_short_kernel(const uint64_t *row_start, uint32_t *hit, uint64_t n, con
 /* One workgroup per listed row of WAVE + 1 .. LDS_MAX hits: bitonic in LDS over the next power of two. */
 template <typename Rows>
 __global__ void __launch_bounds__(ROW_WG)
-rows_sort_lds_kernel(const uint64_t *row_start, uint32_t *hit, const uint32_t *big_rows, const Rows R)
+rows_sort_lds_kernel(const uint64_t *row_start, const uint32_t *big_rows, const Rows R)
 {
   using Key = typename Rows::Key;
   __shared__ Key s[LDS_MAX];
@@ -184,7 +186,7 @@ rows_sort_lds_kernel(const uint64_t *row_start, uint32_t *hit, const uint32_t *b
   while (np < len)
     np <<= 1;
   for (uint32_t t = threadIdx.x; t < np; t += ROW_WG)
-    s[t] = t < len ? R.key_of(hit[start + t]) : Rows::PAD;
+    s[t] = t < len ? R.load(start + t) : Rows::PAD;
   __syncthreads();
   for (uint32_t k = 2; k <= np; k <<= 1)
     for (uint32_t j = k >> 1; j > 0; j >>= 1) {
@@ -202,7 +204,7 @@ rows_sort_lds_kernel(const uint64_t *row_start, uint32_t *hit, const uint32_t *b
     }
   [[maybe_unused]] uint32_t heads = 0;
   for (uint32_t t = threadIdx.x; t < len; t += ROW_WG) {
-    hit[start + t] = Rows::hit_of(s[t]);
+    R.store(start + t, s[t]);
     if constexpr (Rows::COUNT_HEADS)
       if (t == 0 || !Rows::same_run(s[t - 1], s[t]))
         heads++;
@@ -220,15 +222,15 @@ rows_sort_lds_kernel(const uint64_t *row_start, uint32_t *hit, const uint32_t *b
 
 /* both kernels over the n rows; L.ctr is zero */
 template <typename Rows>
-int rows_sort(cmpr_context *c, const uint64_t *row_start, uint32_t *hit, uint64_t n, const RowLists &L, const Rows &R)
+int rows_sort(cmpr_context *c, const uint64_t *row_start, uint64_t n, const RowLists &L, const Rows &R)
 {
   const uint64_t lanes = n + (Rows::COUNT_HEADS ? 1 : 0);
   hipLaunchKernelGGL(rows_sort_short_kernel<Rows>, dim3(blocks_for(lanes, ROW_WG)), dim3(ROW_WG), 0, c->stream,
-                     row_start, hit, n, L, R);
+                     row_start, n, L, R);
   HIP_TRY(c, hipGetLastError());
   if (L.big_cap) {
     hipLaunchKernelGGL(rows_sort_lds_kernel<Rows>, dim3((uint32_t)L.big_cap), dim3(ROW_WG), 0, c->stream, row_start,
-                       hit, L.big_rows, R);
+                       L.big_rows, R);
     HIP_TRY(c, hipGetLastError());
   }
   return CMPR_OK;

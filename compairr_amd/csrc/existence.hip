@@ -59,10 +59,15 @@ struct ExRows {
   using Key = unsigned long long;
   static constexpr Key  PAD = ~0ull;
   static constexpr bool COUNT_HEADS = true;
+  uint32_t       *hit;
   const uint32_t *rep2;
   uint32_t       *ncell;
-  __device__ Key key_of(uint32_t hit) const { return (Key)rep2[hit] << 32 | hit; }
-  __device__ static uint32_t hit_of(Key key) { return (uint32_t)key; }
+  __device__ Key load(uint64_t pos) const
+  {
+    const uint32_t h = hit[pos];
+    return (Key)rep2[h] << 32 | h;
+  }
+  __device__ void store(uint64_t pos, Key key) const { hit[pos] = (uint32_t)key; }
   __device__ static bool same_run(Key a, Key b) { return (a >> 32) == (b >> 32); }
 };
 
@@ -335,7 +340,7 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
   }
   const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, e.census.p + 3};   /* (counters: zero) */
-  if ((rc = rows_sort(c, estart, hit, n1, lists, ExRows{rep2, ncell})))
+  if ((rc = rows_sort(c, estart, n1, lists, ExRows{hit, rep2, ncell})))
     return rc;
   std::vector<LongRow> lr;
   if (n_long) {

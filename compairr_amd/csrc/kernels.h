@@ -380,12 +380,23 @@ __device__ __forceinline__ void link_pair(uint32_t *parent, uint32_t a, uint32_t
   }
 }
 
+/* The reference's --distance of a verified pair (overlap.cc:491-502: the Hamming distance of two sequences of one
+   length, else 1) from the kind its variant was made as (`ca` of the candidate).  A variant never puts a residue
+   where the query has it already -- the generators leave the own residue out, and the sequence itself is K_SAME --,
+   so a substitution is a position that differs, and a step finds a pair once: under one kind. */
+__device__ __forceinline__ uint32_t kind_distance(uint32_t ca)
+{
+  const uint32_t kind = ca & 7u;
+  return kind == K_SAME ? 0u : (kind == K_SUB2 ? 2u : 1u);
+}
+
 /* One verified (query, hit) pair: list it (pairs mode), link its two sequences (link mode) or count / place it
    in the query's row (neighbour mode) -- both inside the pairs branch: the matrix path does not see them --,
-   or add its score to the matrix cell (overlap.cc:218-245). */
+   or add its score to the matrix cell (overlap.cc:218-245).  `dist` (kind_distance) is looked at only by the
+   fill step of cmpr_neighbors_distance. */
 __device__ __forceinline__ void score_match(const ProbeParams &P, uint32_t qs, uint32_t hit,
                                             uint64_t cell, unsigned long long f,
-                                            unsigned long long g, unsigned long long *mat_lds)
+                                            unsigned long long g, unsigned long long *mat_lds, uint32_t dist)
 {
   if (P.pair_count) {
     if (P.link_parent) {
@@ -405,8 +416,11 @@ __device__ __forceinline__ void score_match(const ProbeParams &P, uint32_t qs, u
         atomicAdd(P.nb_degree + q, 1u);
       } else {
         const uint64_t slot = P.nb_row_start[q] + (uint64_t)(atomicSub(P.nb_degree + q, 1u) - 1u);
-        if (slot < P.nb_row_start[q + 1])
+        if (slot < P.nb_row_start[q + 1]) {
           P.nb_hit[slot] = hit;
+          if (P.nb_dist)
+            P.nb_dist[slot] = (uint8_t)dist;
+        }
       }
       return;
     }
@@ -468,7 +482,7 @@ __device__ void resolve_one(const ProbeParams &P, uint64_t hash, uint32_t qs, ui
       if (ok && variant_matches_hit(P, td, ql, q_len, ca, cb, rec, P.res2 + P.off2[rec.idx],
                                     P.rec_tiles ? qrec : nullptr)) {
         st.matches++;
-        score_match(P, qs, rec.idx, (uint64_t)P.R2 * q_rep + rec.rep, q_cnt, rec.cnt, mat_lds);
+        score_match(P, qs, rec.idx, (uint64_t)P.R2 * q_rep + rec.rep, q_cnt, rec.cnt, mat_lds, kind_distance(ca));
       }
     }
     if (last)
@@ -632,7 +646,7 @@ __device__ __forceinline__ bool verify_candidate(const ProbeParams &P, uint32_t 
   }
   if (ok && bad == 0) {
     st.matches++;
-    score_match(P, qs, rec.idx, (uint64_t)P.R2 * q_rep + rec.rep, q_cnt, rec.cnt, mat_lds);
+    score_match(P, qs, rec.idx, (uint64_t)P.R2 * q_rep + rec.rep, q_cnt, rec.cnt, mat_lds, kind_distance(ca));
   }
   return more;
 }

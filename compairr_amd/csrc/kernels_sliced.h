@@ -112,7 +112,7 @@ __device__ __forceinline__ void resolve_inline_slow(SProber &W, int first, int n
         if (ok) {
           W.st.matches++;
           score_match(P, qs, ri, (uint64_t)P.R2 * P.qrec[qs].rep + rec->rep,
-                      P.ignore_counts ? 1ull : P.qrec[qs].cnt, rec->cnt, W.mat_lds);
+                      P.ignore_counts ? 1ull : P.qrec[qs].cnt, rec->cnt, W.mat_lds, kind_distance(ca));
         }
       }
     }

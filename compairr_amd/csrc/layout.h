@@ -432,6 +432,8 @@ struct ProbeParams {
   uint32_t           *nb_degree;    /* NULL everywhere but in cmpr_neighbors: one word per query */
   const uint64_t     *nb_row_start; /* fill step: n1 + 1 row offsets into nb_hit */
   uint32_t           *nb_hit;
+  uint8_t            *nb_dist;      /* NULL everywhere but in the fill step of cmpr_neighbors_distance: beside
+                                       nb_hit[slot], the pair's distance (kernels.h kind_distance) */
   /* sliced mode */
   SliceGeom       geom;
   const Chunk    *chunks;

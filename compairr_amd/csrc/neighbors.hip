@@ -30,6 +30,14 @@
  * sort's scratch.  The host variant adds what the device variant is handed: 8 bytes per query for row_start
  * and 4 per edge for the hits.  Everything is freed before the call returns, also when it fails.
  *
+ * cmpr_neighbors_distance / _device: the same call with one byte beside every hit, the reference's --distance of
+ * the pair (overlap.cc:491-502).  Count, scan and census are the same code; the fill step also has nb_dist, and the
+ * lane that places a hit writes the distance of the kind its variant was verified as beside it (kernels.h
+ * kind_distance); the rows are ordered by the 64-bit key hit << 8 | distance (NdRows: 64 KiB of LDS on the workgroup
+ * path, as existence.hip), and the rows beyond LDS through hipcub::DeviceRadixSort::SortPairs -- key the hit, value
+ * the byte -- and back.  On top of the figures above: one byte per edge (the host variant holds them on the device
+ * for the call), and for rows beyond LDS one byte per hit of the longest of them and the scratch of the pair sort.
+ *
  * cmpr_neighbor_edges (context.h) hands count, scan and fill -- the rows not ordered -- to a caller inside the
  * library that orders them its own way (existence.hip).
  */
@@ -46,8 +54,26 @@ struct NbRows {
   using Key = uint32_t;
   static constexpr Key  PAD = 0xffffffffu;   /* no sequence number (n2 < 2^32 - 64) */
   static constexpr bool COUNT_HEADS = false;
-  __device__ Key key_of(uint32_t hit) const { return hit; }
-  __device__ static uint32_t hit_of(Key key) { return key; }
+  uint32_t *hit;
+  __device__ Key load(uint64_t pos) const { return hit[pos]; }
+  __device__ void store(uint64_t pos, Key key) const { hit[pos] = key; }
+  __device__ static bool same_run(Key, Key) { return true; }
+};
+
+/* the same order with the distance of each edge carried along: a row never holds a hit twice, so the low byte of
+   the key never decides (cmpr_neighbors_distance) */
+struct NdRows {
+  using Key = unsigned long long;
+  static constexpr Key  PAD = ~0ull;
+  static constexpr bool COUNT_HEADS = false;
+  uint32_t *hit;
+  uint8_t  *dist;
+  __device__ Key load(uint64_t pos) const { return (Key)hit[pos] << 8 | dist[pos]; }
+  __device__ void store(uint64_t pos, Key key) const
+  {
+    hit[pos] = (uint32_t)(key >> 8);
+    dist[pos] = (uint8_t)key;
+  }
   __device__ static bool same_run(Key, Key) { return true; }
 };
 
@@ -100,7 +126,7 @@ int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *h
   if ((rc = dev_alloc(c, e.scan_tmp, e.scan_bytes))) return rc;
 
   auto t0 = std::chrono::steady_clock::now();
-  if ((rc = cmpr_neighbor_step(c, degree, nullptr, nullptr, [&]() -> int {
+  if ((rc = cmpr_neighbor_step(c, degree, nullptr, nullptr, nullptr, [&]() -> int {
          HIP_TRY(c, hipMemsetAsync(degree, 0, (size_t)(n1 + 1) * sizeof(uint32_t), c->stream));
          return CMPR_OK;
        })))
@@ -130,8 +156,8 @@ int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *h
   return CMPR_OK;
 }
 
-/* ---- fill ---- every hit into its row, in the order of arrival */
-int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32_t *hit)
+/* ---- fill ---- every hit into its row, in the order of arrival; dist (or NULL): its distance beside it */
+int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32_t *hit, uint8_t *dist)
 {
   int rc;
   const uint64_t n1 = c->n1;
@@ -141,7 +167,7 @@ int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32
     c->usage_pending = false;
   }
   const auto t0 = std::chrono::steady_clock::now();
-  if ((rc = cmpr_neighbor_step(c, degree, row_start, hit, [&]() -> int {
+  if ((rc = cmpr_neighbor_step(c, degree, row_start, hit, dist, [&]() -> int {
          hipLaunchKernelGGL(nb_cursor_kernel, dim3(blocks_for(n1, ROW_WG)), dim3(ROW_WG), 0, c->stream, row_start, degree, n1);
          HIP_TRY(c, hipGetLastError());
          return CMPR_OK;
@@ -151,24 +177,27 @@ int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32
   return CMPR_OK;
 }
 
-int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out,
-                   uint64_t *n_edges_out, bool on_device)
+/* with_dist: cmpr_neighbors_distance, dist_out beside hit_out; otherwise dist_out is NULL */
+int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out, uint8_t *dist_out,
+                   uint64_t *n_edges_out, bool on_device, bool with_dist)
 {
   if (!c)
     return CMPR_EINVAL;
+  const std::string who = with_dist ? "cmpr_neighbors_distance" : "cmpr_neighbors";
   if (!n_edges_out)
-    return fail(c, CMPR_EINVAL, "cmpr_neighbors: n_edges_out is NULL");
+    return fail(c, CMPR_EINVAL, who + ": n_edges_out is NULL");
   *n_edges_out = 0;
   if (capacity && !hit_out)
-    return fail(c, CMPR_EINVAL, "cmpr_neighbors: hit_out is NULL with a capacity");
+    return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
+  if (with_dist && capacity && !dist_out)
+    return fail(c, CMPR_EINVAL, who + ": distance_out is NULL with a capacity");
   int rc;
   if ((rc = cmpr_check_ready(c)))
     return rc;
   if (c->work_shard_count > 1)
-    return fail(c, CMPR_EUNSUPPORTED, "cmpr_neighbors: a work shard holds part of each row (work_shard_count > 1)");
+    return fail(c, CMPR_EUNSUPPORTED, who + ": a work shard holds part of each row (work_shard_count > 1)");
   if (c->routed)
-    return fail(c, CMPR_EUNSUPPORTED, "cmpr_neighbors: a routed query set holds part of each row "
-                                      "(cmpr_set_queries_routed)");
+    return fail(c, CMPR_EUNSUPPORTED, who + ": a routed query set holds part of each row (cmpr_set_queries_routed)");
   const uint64_t n1 = c->n1;
 
   NeighborEdges e;
@@ -182,12 +211,13 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   const uint64_t total = e.total;
   *n_edges_out = total;
   /* degrees only, nothing to list, or no room for it: row_start says what to allocate */
-  if (!hit_out || total == 0 || total > capacity)
+  if (!hit_out || (with_dist && !dist_out) || total == 0 || total > capacity)
     return CMPR_OK;
 
   const uint64_t n_long = e.n_long, n_big = e.n_big, longest = e.longest;
   Tmp<uint32_t> big_rows, scratch;
   Tmp<unsigned long long> long_desc;
+  Tmp<uint8_t> dist_tmp, dist_scratch;
   Tmp<char> sort_tmp;
   size_t sort_bytes = 0;
   uint32_t *hit = on_device ? hit_out : nullptr;
@@ -195,36 +225,59 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     if ((rc = dev_alloc(c, e.hit, (size_t)total))) return rc;
     hit = e.hit.p;
   }
+  uint8_t *dist = on_device ? dist_out : nullptr;
+  if (with_dist && !dist) {
+    if ((rc = dev_alloc(c, dist_tmp.b, (size_t)total))) return rc;
+    dist = dist_tmp.b.p;
+  }
   if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
   if (n_long) {
     if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
     if ((rc = dev_alloc(c, scratch.b, (size_t)longest))) return rc;
-    HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                 (size_t)longest, 0, 32, c->stream));
+    if (with_dist) {
+      if ((rc = dev_alloc(c, dist_scratch.b, (size_t)longest))) return rc;
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                    (const uint8_t *)nullptr, (uint8_t *)nullptr, (size_t)longest, 0,
+                                                    32, c->stream));
+    } else {
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                   (size_t)longest, 0, 32, c->stream));
+    }
     if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
   }
-  if ((rc = nb_fill(c, e, row_start, hit)))
+  if ((rc = nb_fill(c, e, row_start, hit, dist)))
     return rc;
 
   /* ---- order the rows ---- */
   auto t0 = std::chrono::steady_clock::now();
   const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, e.census.p + 3};   /* (counters: zero) */
-  if ((rc = rows_sort(c, row_start, hit, n1, lists, NbRows{})))
+  if ((rc = with_dist ? rows_sort(c, row_start, n1, lists, NdRows{hit, dist})
+                      : rows_sort(c, row_start, n1, lists, NbRows{hit})))
     return rc;
   if (n_long) {
     std::vector<LongRow> lr;
-    if ((rc = rows_fetch_long(c, lists, longest, total, n1, "cmpr_neighbors", lr)))
+    if ((rc = rows_fetch_long(c, lists, longest, total, n1, who.c_str(), lr)))
       return rc;
     for (const LongRow &r : lr) {
       size_t b = sort_bytes;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
-                                                   (size_t)r.len, 0, 32, c->stream));
+      if (with_dist) {
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
+                                                      (const uint8_t *)(dist + r.start), dist_scratch.b.p,
+                                                      (size_t)r.len, 0, 32, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(dist + r.start, dist_scratch.b.p, (size_t)r.len, hipMemcpyDeviceToDevice, c->stream));
+      } else {
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
+                                                     (size_t)r.len, 0, 32, c->stream));
+      }
       HIP_TRY(c, hipMemcpyAsync(hit + r.start, scratch.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
                                 c->stream));
     }
   }
-  if (!on_device)
+  if (!on_device) {
     HIP_TRY(c, hipMemcpyAsync(hit_out, hit, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (with_dist)
+      HIP_TRY(c, hipMemcpyAsync(dist_out, dist, (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->nb_ms[3] = ms_since(t0);
   return CMPR_OK;
@@ -240,17 +293,35 @@ int cmpr_neighbor_edges(cmpr_context *c, NeighborEdges &e)
   if (e.total == 0)
     return CMPR_OK;
   if ((rc = dev_alloc(c, e.hit, (size_t)e.total))) return rc;
-  return nb_fill(c, e, e.row_start.p, e.hit.p);
+  return nb_fill(c, e, e.row_start.p, e.hit.p, nullptr);
 }
 
 extern "C" int cmpr_neighbors(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out,
                               uint64_t *n_edges_out)
 {
-  return guarded(c, [&] { return neighbors_impl(c, capacity, row_start_out, hit_out, n_edges_out, false); });
+  return guarded(c, [&] { return neighbors_impl(c, capacity, row_start_out, hit_out, nullptr, n_edges_out, false, false); });
 }
 
 extern "C" int cmpr_neighbors_device(cmpr_context *c, uint64_t capacity, uint64_t *d_row_start_out,
                                      uint32_t *d_hit_out, uint64_t *n_edges_out)
 {
-  return guarded(c, [&] { return neighbors_impl(c, capacity, d_row_start_out, d_hit_out, n_edges_out, true); });
+  return guarded(c, [&] {
+    return neighbors_impl(c, capacity, d_row_start_out, d_hit_out, nullptr, n_edges_out, true, false);
+  });
+}
+
+extern "C" int cmpr_neighbors_distance(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out,
+                                       uint8_t *distance_out, uint64_t *n_edges_out)
+{
+  return guarded(c, [&] {
+    return neighbors_impl(c, capacity, row_start_out, hit_out, distance_out, n_edges_out, false, true);
+  });
+}
+
+extern "C" int cmpr_neighbors_distance_device(cmpr_context *c, uint64_t capacity, uint64_t *d_row_start_out,
+                                              uint32_t *d_hit_out, uint8_t *d_distance_out, uint64_t *n_edges_out)
+{
+  return guarded(c, [&] {
+    return neighbors_impl(c, capacity, d_row_start_out, d_hit_out, d_distance_out, n_edges_out, true, true);
+  });
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "cmpr_neighbors", "cmpr_neighbors_device",
     "cmpr_existence_csr", "cmpr_existence_csr_device",
     "cmpr_cluster_table", "cmpr_cluster_table_device",
+    "cmpr_neighbors_distance", "cmpr_neighbors_distance_device",
 ]
 
 
@@ -167,6 +168,10 @@ def load_library() -> C.CDLL:
         lib.cmpr_cluster_table.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.POINTER(C.c_uint64)]
         lib.cmpr_cluster_table_device.argtypes = lib.cmpr_cluster_table.argtypes
+    if hasattr(lib, "cmpr_neighbors_distance"):    # (likewise: tools/neighbors_timing.py --against)
+        lib.cmpr_neighbors_distance.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_uint64)]
+        lib.cmpr_neighbors_distance_device.argtypes = lib.cmpr_neighbors_distance.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -444,6 +449,34 @@ class HipOverlap:
                                                     C.c_void_p(d_hits or None), C.byref(n)))
         return n.value
 
+    # ---- ... with the distance of every edge (include/compairr_hip.h: cmpr_neighbors_distance*) ----
+
+    def neighbors_distance(self):
+        """(row_start uint64[n1 + 1], hits uint32[E], distance uint8[E]): neighbors() and, beside every hit, the
+        reference's --distance of the pair -- the number of differing positions when both sequences have one
+        length, else 1.  One degree-only call, then one with the exact capacity."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_neighbors_distance(self._ctx, 0, None, None, None, C.byref(n)))
+        row_start = np.zeros(self._queries() + 1, dtype=np.uint64)
+        hits = np.zeros(n.value, dtype=np.uint32)
+        distance = np.zeros(n.value, dtype=np.uint8)
+        self._check(self._lib.cmpr_neighbors_distance(self._ctx, n.value, row_start.ctypes.data,
+                                                      hits.ctypes.data if n.value else None,
+                                                      distance.ctypes.data if n.value else None, C.byref(n)))
+        assert n.value == len(hits)
+        return row_start, hits, distance
+
+    def neighbors_distance_device(self, capacity: int = 0, d_row_start: int = 0, d_hits: int = 0,
+                                  d_distance: int = 0) -> int:
+        """The same into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted), d_hits (uint32[capacity])
+        and d_distance (uint8[capacity]; both 0 with capacity 0: degrees only).  Returns the edge count; when it
+        exceeds `capacity` nothing was written to d_hits or d_distance."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_neighbors_distance_device(self._ctx, capacity, C.c_void_p(d_row_start or None),
+                                                             C.c_void_p(d_hits or None),
+                                                             C.c_void_p(d_distance or None), C.byref(n)))
+        return n.value
+
     # ---- the -x table as CSR (include/compairr_hip.h: cmpr_existence_csr*) ----
 
     def existence_csr(self):
@@ -544,6 +577,17 @@ def neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: 
         h.set_reference(set2, set1.longest)
         h.set_queries(set1)
         return h.neighbors()
+
+
+def neighbors_distance(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
+    """Convenience: (row_start, hits, distance) of set1 against set2 under `opt` (HipOverlap.neighbors_distance)
+    on a context of its own.  `tunables` are set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        h.set_reference(set2, set1.longest)
+        h.set_queries(set1)
+        return h.neighbors_distance()
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

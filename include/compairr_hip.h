@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_existence_csr*, cmpr_cluster_table*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -321,6 +321,37 @@ int cmpr_neighbors(cmpr_context *ctx, uint64_t capacity,
                    uint64_t *row_start_out, uint32_t *hit_out, uint64_t *n_edges_out);
 int cmpr_neighbors_device(cmpr_context *ctx, uint64_t capacity,
                           uint64_t *d_row_start_out, uint32_t *d_hit_out, uint64_t *n_edges_out);
+
+/*
+ * The neighbour lists with the distance of every edge: the `distance` column of the reference's --pairs --distance
+ * (overlap.cc:491-502) beside each hit.  Everything said of cmpr_neighbors[_device]() holds word for word -- the
+ * same edge set, the same row_start, strictly increasing rows, *n_edges_out == row_start[n1] ==
+ * cmpr_stats.matches, the same state checks and CMPR_EUNSUPPORTED cases, an empty query set is CMPR_OK, results
+ * bit-identical from run to run, under every tunable and with set 2 in parts, every temporary freed on every
+ * return -- and in addition:
+ *   distance_out[capacity]  distance_out[k] belongs to the pair (row of k, hit_out[k]): the number of positions at
+ *                           which the two sequences differ when they have one length, and 1 otherwise.  0 ..
+ *                           options.differences, so 0, 1 or 2.  One d = 2 call therefore holds the graphs at
+ *                           d <= 0, <= 1 and <= 2, and the weights of an edge-weighted network.
+ * The capacity protocol covers both arrays: with more edges than `capacity` NOTHING is written to hit_out or
+ * distance_out; capacity == 0 with both NULL is the degree-only call (one step, no sort); capacity > 0 with either
+ * of them NULL is CMPR_EINVAL, and cmpr_last_error() names the missing argument.  Elements behind the last edge
+ * are not written.  The device variant takes all three arrays as device memory on the context's device.
+ *
+ * The distance costs no comparison of sequences: a pair is verified as a variant of one kind -- the sequence
+ * itself, one substitution, one deletion or insertion, two substitutions --, a variant never puts a residue where
+ * the query has it already, and the lane that places the hit writes the distance of that kind beside it.  On top of
+ * the footprint of cmpr_neighbors(): 1 byte per edge (the host variant holds it on the device for the duration of
+ * the call), and for rows of more than 8192 hits the payload of the longest of them in and out of the device-wide
+ * sort (1 byte per hit of that row) plus the scratch of a pair sort instead of a key sort.  The timing tunables
+ * "neighbors_*_us" describe this call as they describe cmpr_neighbors().
+ */
+int cmpr_neighbors_distance(cmpr_context *ctx, uint64_t capacity,
+                            uint64_t *row_start_out, uint32_t *hit_out, uint8_t *distance_out,
+                            uint64_t *n_edges_out);
+int cmpr_neighbors_distance_device(cmpr_context *ctx, uint64_t capacity,
+                                   uint64_t *d_row_start_out, uint32_t *d_hit_out, uint8_t *d_distance_out,
+                                   uint64_t *n_edges_out);
 
 /*
  * The -x table without its zeros: per query, the set-2 repertoires it has a match in and the cell's value, as CSR.

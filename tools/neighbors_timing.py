@@ -19,6 +19,14 @@ that of (a); the rest is a report.
         * the route to the same CSR that exists without it: cmpr_overlap_pairs to the host (count, then list),
           np.lexsort, np.bincount + np.cumsum -- clocked in its parts; the two results must be equal.
 
+  (c) per size of --sizes and for d = 1 and d = 2 (--distance-d), the same sets against themselves:
+        * cmpr_neighbors_distance_device with the three arrays in HBM and the exact capacity, and its parts, beside
+          cmpr_neighbors_device on the same context (the hits of the two must be equal, and the distances lie in
+          0 .. d with every value present);
+        * at d = 2 the route to the graphs at d <= 0, <= 1, <= 2 that exists without it: one cmpr_neighbors_device
+          call on each of three resident contexts of d = 0, 1, 2 (the calls alone; the contexts are set up before).
+      Skipped when the timed library lacks the entry point (the parent commit's).
+
 Without --against, (a) is skipped and (b) times the library the environment names (COMPAIRR_HIP_LIB, e.g. the parent
 commit's build, for the same report of the parent), or this tree's when it names none.
 
@@ -105,6 +113,65 @@ def measure(n, reps):
     print(json.dumps(out))
 
 
+def timed_calls(h, call, reps):
+    """host ms per call and the library's parts, `reps` calls after a warm-up one"""
+    ms, parts = [], {p: [] for p in PARTS}
+    for k in range(reps + 1):
+        t0 = time.perf_counter()
+        call()
+        ms.append((time.perf_counter() - t0) * 1e3)
+        for p in PARTS:
+            parts[p].append(h.get_tunable("neighbors_%s_us" % p) / 1e3)
+    return ms[1:], {p: v[1:] for p, v in parts.items()}
+
+
+def measure_distance(n, d, reps):
+    """(child) one JSON line for one set size and one d: the distance call beside cmpr_neighbors_device"""
+    import torch
+    from compairr_amd import HipOverlap, Options, synth
+    s = synth.make_set(n, 2, prefix="B", pool_size=n // 4)
+    out = {"n": s.n, "d": d}
+
+    def context(dd):
+        h = HipOverlap(Options(differences=dd, n_v_genes=synth.N_V, n_j_genes=synth.N_J, device=0))
+        h.set_reference(s, s.longest)
+        h.set_queries(s)
+        return h
+
+    with context(d) as h:
+        if not hasattr(h._lib, "cmpr_neighbors_distance_device"):
+            print(json.dumps(dict(out, missing=True)))
+            return
+        edges = h.neighbors_device(0, 0, 0)
+        d_rows = torch.zeros(s.n + 1, dtype=torch.int64, device="cuda")
+        d_hits = torch.zeros(max(edges, 1), dtype=torch.int32, device="cuda")
+        d_hits2 = torch.zeros(max(edges, 1), dtype=torch.int32, device="cuda")
+        d_dist = torch.full((max(edges, 1),), 255, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        ms, parts = timed_calls(h, lambda: h.neighbors_device(edges, d_rows.data_ptr(), d_hits.data_ptr()), reps)
+        out.update(edges=edges, neighbors_ms=ms, **{"neighbors_%s_ms" % p: v for p, v in parts.items()})
+        ms, parts = timed_calls(h, lambda: h.neighbors_distance_device(edges, d_rows.data_ptr(), d_hits2.data_ptr(),
+                                                                       d_dist.data_ptr()), reps)
+        out.update(distance_ms=ms, **{"distance_%s_ms" % p: v for p, v in parts.items()})
+        hist = torch.bincount(d_dist[:edges].to(torch.int64), minlength=3).cpu().tolist()
+        out.update(histogram=hist, equal=bool(torch.equal(d_hits[:edges], d_hits2[:edges]) and sum(hist[:d + 1]) == edges
+                                              and all(x > 0 for x in hist[:d + 1])))
+        del d_hits2, d_dist
+    if d == 2:
+        # the route without the call: a context per d, one cmpr_neighbors_device call on each
+        per_d = []
+        for dd in (0, 1, 2):
+            with context(dd) as h:
+                e = h.neighbors_device(0, 0, 0)
+                hits = torch.zeros(max(e, 1), dtype=torch.int32, device="cuda")
+                torch.cuda.synchronize()
+                ms, _ = timed_calls(h, lambda: h.neighbors_device(e, d_rows.data_ptr(), hits.data_ptr()), reps)
+                per_d.append(ms)
+                del hits
+        out.update(three_contexts_ms=[sum(x) for x in zip(*per_d)], per_context_ms=[median(x) for x in per_d])
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -115,9 +182,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "build", "neighbors_timing"))
     ap.add_argument("--against", metavar="LIB", help="the parent commit's library")
     ap.add_argument("--measure", type=int, default=0, metavar="N", help="(child) time one set size, print one JSON line")
+    ap.add_argument("--distance-d", default="1,2", help="(c): the d of the cmpr_neighbors_distance_device timings; empty: none")
+    ap.add_argument("--measure-distance", type=int, default=0, metavar="N", help="(child) (c) for one set size and --d")
+    ap.add_argument("--d", type=int, default=1, help="(child) the d of --measure-distance")
     args = ap.parse_args()
     if args.measure:
         return measure(args.measure, args.reps)
+    if args.measure_distance:
+        return measure_distance(args.measure_distance, args.d, args.reps)
 
     os.makedirs(args.out, exist_ok=True)
     lines = ["cmpr_neighbors: cost to the existing workload and the new call (tools/neighbors_timing.py)"]
@@ -195,6 +267,37 @@ def main():
             lines.append("n = %d: the two routes differ" % n)
             flush()
             return 1
+
+    # (c) the distance of every edge
+    for n in [int(x) for x in args.sizes.split(",") if x]:
+        for d in [int(x) for x in args.distance_d.split(",") if x]:
+            p = subprocess.run(["timeout", "-k", "10", "500"] + me + ["--measure-distance", str(n), "--d", str(d), "--reps",
+                                                                     str(args.reps)],
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=timed_env)
+            if p.returncode != 0:
+                return failed("distance timing child (n = %d, d = %d)" % (n, d), p)
+            r = json.loads(p.stdout.decode().strip().splitlines()[-1])
+            if r.get("missing"):
+                lines.append("(c) not measured: the timed library has no cmpr_neighbors_distance_device")
+                break
+            first = len(lines)
+            lines.append("(c) n = %d CDR3aa against themselves, d = %d: %d edges, [d0, d1, d2] = %s; hits equal to "
+                         "cmpr_neighbors_device's and every distance in 0 .. d: %s" % (r["n"], d, r["edges"], r["histogram"], r["equal"]))
+            for call, what in (("neighbors", "cmpr_neighbors_device"), ("distance", "cmpr_neighbors_distance_device")):
+                lines.append("    %s, arrays in HBM, host ms per call (%d calls after a warm-up): %s"
+                             % (what, len(r["%s_ms" % call]), spread(r["%s_ms" % call])))
+                for part, name in zip(PARTS, ("count step", "sum + census", "fill step", "rows ordered")):
+                    lines.append("      %-13s %s" % (name, spread(r["%s_%s_ms" % (call, part)])))
+            if "three_contexts_ms" in r:
+                lines.append("    without it: cmpr_neighbors_device on three resident contexts of d = 0, 1, 2, the three calls in all: %s"
+                             % spread(r["three_contexts_ms"]))
+                lines.append("      medians per context d = 0, 1, 2: %s" % " ".join("%.2f" % x for x in r["per_context_ms"]))
+            flush()
+            print("\n".join(lines[first:]), flush=True)
+            if not r["equal"]:
+                lines.append("n = %d, d = %d: the two calls differ" % (n, d))
+                flush()
+                return 1
     flush()
     print("\n".join(lines), flush=True)
     return status

@@ -65,6 +65,10 @@ $(OBJ_DIR)/existence.o: $(KERN_DIR)/existence.hip $(KERN_HDR)
 	@mkdir -p $(OBJ_DIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
+$(OBJ_DIR)/hamming.o: $(KERN_DIR)/hamming.hip $(KERN_HDR)
+	@mkdir -p $(OBJ_DIR)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
 $(OBJ_DIR)/probe_v0.o: $(KERN_DIR)/probe_tu.hip $(KERN_HDR)
 	@mkdir -p $(OBJ_DIR)
 	$(HIPCC) $(HIPFLAGS) -DTU_VARIANT=0 -c -o $@ $<
@@ -98,7 +102,7 @@ $(OBJ_DIR)/probe_v2wi_nw%.o: $(KERN_DIR)/probe_tu.hip $(KERN_HDR)
 	$(HIPCC) $(HIPFLAGS) -DTU_VARIANT=2 -DTU_NW=$* -DTU_INLINE=1 -DTU_WIDE -c -o $@ $<
 
 $(LIB): $(OBJ_DIR)/main.o $(OBJ_DIR)/query_layout.o $(OBJ_DIR)/ref_index.o $(OBJ_DIR)/dedup.o $(OBJ_DIR)/cluster.o \
-        $(OBJ_DIR)/neighbors.o $(OBJ_DIR)/existence.o $(TU_OBJS)
+        $(OBJ_DIR)/neighbors.o $(OBJ_DIR)/existence.o $(OBJ_DIR)/hamming.o $(TU_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 # diagnostic build with per-phase cycle counters in the probe kernel (tools/phase_timing.py)

@@ -9,7 +9,7 @@ no compute path of its own and no CPU fallback.
 
 from .sets import RepertoireSet  # noqa: F401
 from .hip import (HipOverlap, HipError, Options, Stats, cluster, cluster_table, deduplicate, existence_csr,  # noqa: F401
-                  library_path, neighbors, neighbors_distance)
+                  hamming_matrix, hamming_neighbors, library_path, neighbors, neighbors_distance)
 
 __all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "cluster_table", "deduplicate",
-           "existence_csr", "library_path", "neighbors", "neighbors_distance"]
+           "existence_csr", "hamming_matrix", "hamming_neighbors", "library_path", "neighbors", "neighbors_distance"]

@@ -363,6 +363,10 @@ const Tunable TUNABLES[] = {
   /* TEST ONLY: at 0 every occupied slot of a chain has the sequence's tag, and the "same tag, another sequence,
      next slot" path of dedup_insert_kernel (dedup.hip) runs on ordinary data (tests/test_dedup_gpu.py) */
   {"dedup_tag_bits", F(dedup_tag_bits), 0, 32, LOCK_NEVER, T_NO_PLAN, " must be 0..32"},
+  /* TEST ONLY: the staging, the segments and the form of cmpr_hamming_* (hamming.hip; tests/test_hamming_gpu.py) */
+  {"hamming_stage_refs", F(hamming_stage_refs), 0, 65536, LOCK_NEVER, T_NO_PLAN, " must be 0..65536"},
+  {"hamming_segments", F(hamming_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
+  {"hamming_generic", F(hamming_generic), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
   {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
   {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
   {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},
@@ -480,6 +484,9 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "existence_copy_us") *value = (int64_t)(c->ex_ms[4] * 1e3);
   else if (n == "cluster_links_us") *value = (int64_t)(c->cl_ms[0] * 1e3);
   else if (n == "cluster_table_us") *value = (int64_t)(c->cl_ms[1] * 1e3);
+  else if (n == "hamming_group_us") *value = (int64_t)(c->hm_ms[0] * 1e3);
+  else if (n == "hamming_compare_us") *value = (int64_t)(c->hm_ms[1] * 1e3);
+  else if (n == "hamming_copy_us") *value = (int64_t)(c->hm_ms[2] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
   else if (n == "heavy_buckets") {
     *value = 0;

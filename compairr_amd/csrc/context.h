@@ -205,6 +205,9 @@ struct cmpr_context {
   int64_t record_tiles = 1;       /* 1 = where the layout allows (layout.h rec_tiles), the hash in the record where
                                      the sequences leave room; 2 = never the hash (rows) */
   int64_t dedup_tag_bits = 32;    /* TEST ONLY: bits of the hash a table word of cmpr_deduplicate carries (dedup.hip) */
+  /* TEST ONLY, of cmpr_hamming_* (hamming.hip): references staged per LDS piece (0 = as many as fit), the
+     segment count (0 = automatic), 1 = every group through the long-sequence form */
+  int64_t hamming_stage_refs = 0, hamming_segments = 0, hamming_generic = 0;
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */
@@ -348,6 +351,7 @@ struct cmpr_context {
   double              nb_ms[4] = {};   /* host time of the last cmpr_neighbors: count | scan | fill | order */
   double              ex_ms[5] = {};   /* ... of the last cmpr_existence_csr: edges | group | count | reduce | copy-out */
   double              cl_ms[2] = {};   /* ... of the last cmpr_cluster_table: labels and sizes | the table */
+  double              hm_ms[3] = {};   /* ... of the last cmpr_hamming_*: upload, groups, packing | compare | copy-out */
 };
 
 

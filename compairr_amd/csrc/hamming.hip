@@ -1,0 +1,786 @@
+/*
+ * hamming.hip -- the reference's all-against-all path for any d (process_trad, overlap.cc:286-359; seq_diff,
+ * util.cc:172-184) as library calls that take the distance as an argument: cmpr_hamming_matrix / _device and
+ * cmpr_hamming_neighbors / _device.  A pair (i of set 1, j of set 2) matches when the two sequences have one length
+ * (two empty ones included), the same V and J gene numbers unless ignore_genes, and differ at no more than
+ * `differences` positions.  Nothing is hashed: every query is compared with every sequence of its group.
+ *
+ *   group    every sequence gets the 64-bit key (length, V, J) -- the length alone with ignore_genes --; hipcub's
+ *            stable radix sort of (key, sequence number) per set, so inside a group the sequences stay in increasing
+ *            number; the runs of equal keys are the groups (hipcub run-length encode).  The host reads the two group
+ *            tables -- as many entries as there are distinct keys, not sequences -- and matches them by key.
+ *   pack     the residues of each set in group order, 32-bit words, a fixed number of words per sequence of a group:
+ *            four amino acids (a byte each) or sixteen nucleotides (two bits each) per word.  The words are zeroed
+ *            and the residues or-ed in: the padding of a last word is zero on both sides.  Groups of at most
+ *            HAMMING_REG_WORDS words are padded to the next of the word counts the register form is compiled for.
+ *   compare  hm_compare_kernel.  A workgroup of four waves takes four 64-query tiles of one group and one segment of
+ *            the matching set-2 group; it stages the segment's packed sequences in LDS, HM_LDS_WORDS at a time, and
+ *            every lane walks the staged references with its query's words in registers (register form) or read
+ *            from global memory (generic form: groups of more than HAMMING_REG_WORDS words; a reference that does
+ *            not fit the LDS buffer is staged in runs of words).  All lanes read the same reference word: an LDS
+ *            broadcast.  Differing residues per word: xor, SWAR, popcount.
+ *   sinks    matrix: the score of a match is added to a per-lane sum, which goes to its cell when the lane's next
+ *            match lies in another set-2 repertoire and at the end -- into a copy of the matrix in LDS when it has
+ *            at most HM_MAT_CELLS cells (added to the global one once per workgroup), else with 64-bit global
+ *            atomics.  With `existence` the row is the lane's own.  Integer sums: the same in any order.
+ *            count / fill: a lane counts the hits of its (query, segment), the counts are summed in (query,
+ *            segment) order (hipcub), and the same walk writes every hit and its distance at the lane's running
+ *            offset.  All hits of a query lie in ONE set-2 group, walked in increasing sequence number: the rows
+ *            come out sorted, without atomics and without a row sort.
+ *
+ * The (query, segment) count array has n1 x S words, S <= HM_MAX_SEGMENTS; the automatic S is above 1 only while
+ * the query tiles alone do not fill the machine (S <= ceil(8 x CUs / workgroups)), which bounds it by
+ * 256 x (8 x CUs + workgroups) words.  Nothing here writes the resident sets, plans or statistics of the context.
+ */
+#include "context.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace cmpr;
+
+namespace {
+
+constexpr uint32_t HM_WG = 256;                /* four waves: four 64-query tiles of one group */
+constexpr uint32_t HAMMING_REG_WORDS = 16;     /* the bound between the two forms: a group of more words per sequence
+                                                  (64 amino acids, 256 nucleotides) takes the generic form */
+constexpr uint32_t HM_LDS_WORDS = 4096;        /* packed words of references staged at a time (16 KiB) */
+constexpr uint32_t HM_STAGE_MAX = 512;         /* ... and at most this many references */
+constexpr uint32_t HM_MAT_CELLS = 1024;        /* a matrix of up to this many cells is privatised in LDS (8 KiB) */
+constexpr uint32_t HM_MAX_SEGMENTS = 64;
+constexpr uint32_t AA_PER_WORD = 4, NT_PER_WORD = 16;
+
+/* a group of one set: the sequences at positions start .. start + count - 1 of the sorted order */
+struct HmGroup {
+  uint64_t pk_off;                 /* first packed word of the group */
+  uint32_t start, count;
+  uint32_t stride, len;            /* words per sequence; residues per sequence */
+};
+
+/* a group of set 1 and the group of set 2 with the same key */
+struct HmPair {
+  uint64_t pk1, pk2;               /* first packed word of either group */
+  uint32_t q0, nq, r0, nr;         /* positions in the two sorted orders */
+  uint32_t stride, blk0;           /* words per sequence; first workgroup (grid x) of the pair */
+};
+
+struct HmParams {
+  const HmPair   *pairs;
+  uint32_t        npairs, segments;
+  const uint32_t *pk1, *pk2;       /* packed words */
+  const uint32_t *ord1, *ord2;     /* sequence numbers in group order */
+  uint32_t        d, stage_refs;
+  uint32_t        blk_base;        /* workgroup number of this launch's first workgroup */
+  /* count / fill */
+  uint32_t       *cnt;             /* [n1 x segments]: hits of (query, segment) */
+  const unsigned long long *offs;  /* their exclusive sum; NULL: the count step */
+  uint32_t       *hit;
+  uint16_t       *dist;            /* may be NULL */
+  /* matrix */
+  const uint32_t *rep1, *rep2;
+  const uint64_t *cnt1, *cnt2;     /* NULL: ignore_counts */
+  uint32_t        R2, score, existence, mat_lds;
+  unsigned long long *matrix;
+  uint32_t        cells;
+};
+
+enum { SINK_CSR = 0, SINK_MATRIX = 1 };
+
+/* differing residues of two packed words.  Amino acids: a byte each, codes below 0x80, so neither the xor nor the
+   sum carries into the next byte and bit 7 says "this byte is not zero".  Nucleotides: two bits each. */
+template <bool NT>
+__device__ __forceinline__ uint32_t diff_word(uint32_t a, uint32_t b)
+{
+  const uint32_t x = a ^ b;
+  if (NT)
+    return (uint32_t)__popc((x | (x >> 1)) & 0x55555555u);
+  return (uint32_t)__popc((x + 0x7f7f7f7fu) & 0x80808080u);
+}
+
+__device__ __forceinline__ unsigned long long pair_score(uint32_t score, unsigned long long f, unsigned long long g)
+{
+  switch (score) {
+  case CMPR_SCORE_MIN: case CMPR_SCORE_JACCARD: return f < g ? f : g;
+  case CMPR_SCORE_MAX:                          return f > g ? f : g;
+  case CMPR_SCORE_MEAN:                         return f + g;             /* 2 x mean */
+  default:                                      return f * g;             /* product, MH */
+  }
+}
+
+/* what a lane keeps of its matches */
+struct LaneSink {
+  /* CSR */
+  uint32_t hits = 0;
+  unsigned long long pos = 0;
+  /* matrix */
+  unsigned long long acc = 0, row = 0, f = 1;
+  uint32_t cur_rep = 0;
+};
+
+/* NW: words per sequence held in registers (the group's stride), 0: the generic form */
+template <int NW, int SINK, bool NT>
+__global__ void __launch_bounds__(HM_WG)
+hm_compare_kernel(const HmParams P)
+{
+  __shared__ uint32_t st_words[HM_LDS_WORDS];
+  __shared__ uint32_t st_id[HM_STAGE_MAX];
+  __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? HM_STAGE_MAX : 1];
+  __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? HM_STAGE_MAX : 1];
+  __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? HM_MAT_CELLS : 1];
+
+  /* the pair of this workgroup: the last one whose first workgroup is not behind it */
+  const uint32_t blk = P.blk_base + blockIdx.x;
+  uint32_t lo = 0, hi = P.npairs - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (P.pairs[mid].blk0 <= blk)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const HmPair pr = P.pairs[lo];
+  const uint32_t stride = NW ? (uint32_t)NW : pr.stride;
+  const uint32_t qi = (blk - pr.blk0) * HM_WG + threadIdx.x;     /* query within the group */
+  const bool active = qi < pr.nq;
+  const uint32_t qpos = pr.q0 + (active ? qi : 0u);                     /* (an idle lane reads the group's first query) */
+  const uint32_t qorig = P.ord1[qpos];
+  /* the segment of the set-2 group */
+  const uint32_t seg = blockIdx.y;
+  const uint32_t e0 = (uint32_t)((uint64_t)pr.nr * seg / P.segments);
+  const uint32_t e1 = (uint32_t)((uint64_t)pr.nr * (seg + 1) / P.segments);
+
+  if (e0 >= e1)
+    return;                                                             /* (the whole workgroup) */
+  const bool mat_lds = SINK == SINK_MATRIX && P.mat_lds;
+  if (mat_lds) {                                                        /* (a barrier follows before the first flush) */
+    for (uint32_t k = threadIdx.x; k < P.cells; k += HM_WG)
+      st_mat[k] = 0;
+  }
+
+  const uint32_t *const qw = P.pk1 + pr.pk1 + (uint64_t)(qpos - pr.q0) * stride;
+  uint32_t q[NW ? NW : 1];
+  if (NW) {
+#pragma unroll
+    for (int k = 0; k < NW; k++)
+      q[k] = qw[k];
+  }
+
+  LaneSink S;
+  if (SINK == SINK_CSR) {
+    if (P.offs)
+      S.pos = P.offs[(uint64_t)qorig * P.segments + seg];
+  } else {
+    S.row = P.existence ? (unsigned long long)qorig : (unsigned long long)P.rep1[qorig];
+    S.f = P.cnt1 ? P.cnt1[qorig] : 1ull;
+  }
+  auto flush = [&]() {
+    if (SINK == SINK_MATRIX && S.acc) {
+      const uint64_t cell = S.row * P.R2 + S.cur_rep;
+      if (mat_lds)
+        atomicAdd(&st_mat[cell], S.acc);
+      else
+        atomicAdd(P.matrix + cell, S.acc);
+      S.acc = 0;
+    }
+  };
+  /* reference r of the staged piece matched at distance `dd` */
+  auto sink = [&](uint32_t r, uint32_t dd) {
+    if (SINK == SINK_CSR) {
+      if (P.offs) {
+        P.hit[S.pos] = st_id[r];
+        if (P.dist)
+          P.dist[S.pos] = (uint16_t)dd;
+        S.pos++;
+      } else {
+        S.hits++;
+      }
+    } else {
+      /* the lane's sum belongs to one set-2 repertoire: a match in another one sends it to its cell first (a
+         reference that does not match costs the matrix sink nothing) */
+      const uint32_t rp = st_rep[r];
+      if (rp != S.cur_rep) {
+        flush();
+        S.cur_rep = rp;
+      }
+      S.acc += P.cnt1 ? pair_score(P.score, S.f, st_cnt[r]) : 1ull;
+    }
+  };
+  /* sequence numbers, repertoires and counts of the references e .. e + n - 1 of the group */
+  auto stage_ids = [&](uint32_t e, uint32_t n) {
+    for (uint32_t r = threadIdx.x; r < n; r += HM_WG) {
+      const uint32_t id = P.ord2[pr.r0 + e + r];
+      st_id[r] = id;
+      if (SINK == SINK_MATRIX) {
+        st_rep[r] = P.rep2[id];
+        st_cnt[r] = P.cnt2 ? P.cnt2[id] : 1ull;
+      }
+    }
+  };
+
+  if (stride <= HM_LDS_WORDS) {
+    /* whole references, R at a time */
+    uint32_t R = HM_LDS_WORDS / stride;
+    if (R > HM_STAGE_MAX) R = HM_STAGE_MAX;
+    if (P.stage_refs && P.stage_refs < R) R = P.stage_refs;
+    for (uint32_t e = e0; e < e1; e += R) {
+      const uint32_t n = e1 - e < R ? e1 - e : R;
+      __syncthreads();                                                  /* the previous piece has been read */
+      const uint32_t *const src = P.pk2 + pr.pk2 + (uint64_t)e * stride;
+      for (uint32_t k = threadIdx.x; k < n * stride; k += HM_WG)
+        st_words[k] = src[k];
+      stage_ids(e, n);
+      __syncthreads();
+      for (uint32_t r = 0; r < n; r++) {
+        const uint32_t *const w = st_words + r * stride;
+        uint32_t dd = 0;
+        if (NW) {
+#pragma unroll
+          for (int k = 0; k < NW; k++)
+            dd += diff_word<NT>(q[k], w[k]);
+        } else {
+          for (uint32_t k = 0; k < stride; k++)
+            dd += diff_word<NT>(qw[k], w[k]);
+        }
+        if (dd <= P.d && active)
+          sink(r, dd);
+      }
+    }
+  } else {
+    /* generic form only: a reference longer than the buffer, staged in runs of words */
+    for (uint32_t e = e0; e < e1; e++) {
+      uint32_t dd = 0;
+      for (uint32_t k0 = 0; k0 < stride; k0 += HM_LDS_WORDS) {
+        const uint32_t m = stride - k0 < HM_LDS_WORDS ? stride - k0 : HM_LDS_WORDS;
+        __syncthreads();
+        const uint32_t *const src = P.pk2 + pr.pk2 + (uint64_t)e * stride + k0;
+        for (uint32_t k = threadIdx.x; k < m; k += HM_WG)
+          st_words[k] = src[k];
+        if (k0 == 0)
+          stage_ids(e, 1);
+        __syncthreads();
+        for (uint32_t k = 0; k < m; k++)
+          dd += diff_word<NT>(qw[k0 + k], st_words[k]);
+      }
+      if (dd <= P.d && active)
+        sink(0, dd);
+    }
+  }
+
+  if (SINK == SINK_CSR) {
+    if (!P.offs && active)
+      P.cnt[(uint64_t)qorig * P.segments + seg] = S.hits;
+  } else {
+    flush();
+    if (mat_lds) {
+      __syncthreads();
+      for (uint32_t k = threadIdx.x; k < P.cells; k += HM_WG)
+        if (st_mat[k])
+          atomicAdd(P.matrix + k, st_mat[k]);
+    }
+  }
+}
+
+typedef void (*HmKernel)(const HmParams);
+
+template <int SINK, bool NT>
+HmKernel hm_kernel_for(uint32_t nw)
+{
+  switch (nw) {
+  case 1:  return hm_compare_kernel<1, SINK, NT>;
+  case 2:  return hm_compare_kernel<2, SINK, NT>;
+  case 3:  return hm_compare_kernel<3, SINK, NT>;
+  case 4:  return hm_compare_kernel<4, SINK, NT>;
+  case 5:  return hm_compare_kernel<5, SINK, NT>;
+  case 6:  return hm_compare_kernel<6, SINK, NT>;
+  case 8:  return hm_compare_kernel<8, SINK, NT>;
+  case 12: return hm_compare_kernel<12, SINK, NT>;
+  case 16: return hm_compare_kernel<16, SINK, NT>;
+  default: return hm_compare_kernel<0, SINK, NT>;
+  }
+}
+
+/* words per sequence of a group of `len` residues: the next word count the register form is compiled for, or the
+   words themselves beyond HAMMING_REG_WORDS */
+uint32_t stride_of(uint32_t len, uint32_t per_word)
+{
+  const uint32_t w = std::max<uint32_t>(1, (len + per_word - 1) / per_word);
+  static const uint32_t forms[] = {1, 2, 3, 4, 5, 6, 8, 12, HAMMING_REG_WORDS};
+  for (uint32_t f : forms)
+    if (w <= f)
+      return f;
+  return w;
+}
+
+/* ---- grouping and packing ---- */
+
+struct KeyParams {
+  const uint64_t *off;
+  const uint32_t *v, *j;           /* NULL: ignore_genes */
+  uint64_t        n, n_v, n_j;
+  uint64_t       *key;
+  uint32_t       *num;
+};
+
+__global__ void __launch_bounds__(HM_WG)
+hm_key_kernel(const KeyParams K)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * HM_WG + threadIdx.x;
+  if (i >= K.n)
+    return;
+  uint64_t key = K.off[i + 1] - K.off[i];
+  if (K.v)
+    key = (key * K.n_v + K.v[i]) * K.n_j + K.j[i];
+  K.key[i] = key;
+  K.num[i] = (uint32_t)i;
+}
+
+struct PackParams {
+  const HmGroup  *groups;
+  uint32_t        ngroups, per_word, bits;
+  const uint8_t  *res;
+  const uint64_t *off;
+  const uint32_t *ord;
+  uint64_t        words;
+  uint32_t       *pk;
+};
+
+/* one thread per packed word: its group by the word offsets, its sequence and its place in it from there */
+__global__ void __launch_bounds__(HM_WG)
+hm_pack_kernel(const PackParams K)
+{
+  const uint64_t w = (uint64_t)blockIdx.x * HM_WG + threadIdx.x;
+  if (w >= K.words)
+    return;
+  uint32_t lo = 0, hi = K.ngroups - 1;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi + 1) >> 1;
+    if (K.groups[mid].pk_off <= w)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const HmGroup g = K.groups[lo];
+  const uint64_t rel = w - g.pk_off;
+  const uint32_t s = (uint32_t)(rel / g.stride), k = (uint32_t)(rel % g.stride);
+  const uint64_t b = K.off[K.ord[g.start + s]];
+  uint32_t word = 0;
+  const uint32_t p0 = k * K.per_word;
+  for (uint32_t t = 0; t < K.per_word && p0 + t < g.len; t++)
+    word |= (uint32_t)K.res[b + p0 + t] << (t * K.bits);
+  K.pk[w] = word;
+}
+
+/* row_start[i] = the offset of (query i, segment 0); row_start[n1] = the edge count */
+__global__ void __launch_bounds__(HM_WG)
+hm_rows_kernel(const unsigned long long *offs, uint64_t n1, uint32_t segments, uint64_t *row_start)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * HM_WG + threadIdx.x;
+  if (i <= n1)
+    row_start[i] = offs[i * segments];
+}
+
+/* a set on the device, validated, grouped and packed */
+struct HmSet {
+  Tmp<uint8_t>  res;
+  Tmp<uint64_t> off, cnt;
+  Tmp<uint32_t> v, j, rep, ord, pk;
+  uint64_t      n = 0;
+  uint32_t      longest = 0, R = 0;
+  std::vector<uint64_t> keys;      /* of the groups, increasing */
+  std::vector<HmGroup>  groups;
+};
+
+int hm_prepare(cmpr_context *c, const cmpr_set_view *s, bool on_device, HmSet &H)
+{
+  int rc;
+  uint64_t residues = 0;
+  if (s->n && on_device) {       /* (as cmpr_deduplicate_device: offsets[0] and offsets[n] are all the host sees) */
+    uint64_t ends[2] = {0, 0};
+    HIP_TRY(c, hipMemcpy(&ends[0], s->offsets, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&ends[1], s->offsets + s->n, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (ends[0] != 0)
+      return fail(c, CMPR_EINVAL, "offsets[0] must be 0");
+    if (ends[1] > 0xffffull * s->n)
+      return fail(c, CMPR_EINVAL, "offsets not monotone");
+    residues = ends[1];
+  }
+  std::vector<double> tot;
+  if ((rc = cmpr_upload_and_validate(c, s, H.res.b, H.off.b, H.v.b, H.j.b, H.rep.b, H.cnt.b, H.longest, tot, on_device,
+                                     residues)))
+    return rc;
+  H.n = s->n;
+  H.R = s->n_repertoires;
+  if (H.n == 0)
+    return CMPR_OK;
+  if (H.n > 0x7fffffffull)
+    return fail(c, CMPR_EUNSUPPORTED, "cmpr_hamming: more than 2^31-1 sequences in one set");
+
+  /* keys, the stable sort, the runs */
+  const uint64_t n = H.n;
+  const bool genes = !c->opt.ignore_genes;
+  const uint64_t n_v = std::max<uint32_t>(1, c->opt.n_v_genes), n_j = std::max<uint32_t>(1, c->opt.n_j_genes);
+  Tmp<uint64_t> key, key_sorted, run_key;
+  Tmp<uint32_t> num, run_len, nruns;
+  Tmp<char> scratch;
+  if ((rc = dev_alloc(c, key.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, key_sorted.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, num.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, H.ord.b, (size_t)n))) return rc;
+  KeyParams K{H.off.b.p, genes ? H.v.b.p : nullptr, genes ? H.j.b.p : nullptr, n, n_v, n_j, key.b.p, num.b.p};
+  hipLaunchKernelGGL(hm_key_kernel, dim3(blocks_for(n, HM_WG)), dim3(HM_WG), 0, c->stream, K);
+  HIP_TRY(c, hipGetLastError());
+  const uint64_t key_max = genes ? ((uint64_t)H.longest + 1) * n_v * n_j : (uint64_t)H.longest + 1;
+  int end_bit = 1;
+  while (end_bit < 64 && (key_max >> end_bit))
+    end_bit++;
+  size_t sort_bytes = 0, rle_bytes = 0;
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t *)key.b.p, key_sorted.b.p,
+                                                (const uint32_t *)num.b.p, H.ord.b.p, (size_t)n, 0, end_bit, c->stream));
+  if ((rc = dev_alloc(c, run_key.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, run_len.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, nruns.b, 1))) return rc;
+  HIP_TRY(c, hipcub::DeviceRunLengthEncode::Encode(nullptr, rle_bytes, (const uint64_t *)key_sorted.b.p, run_key.b.p,
+                                                   run_len.b.p, nruns.b.p, (int)n, c->stream));
+  if ((rc = dev_alloc(c, scratch.b, std::max(sort_bytes, rle_bytes)))) return rc;
+  HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, sort_bytes, (const uint64_t *)key.b.p, key_sorted.b.p,
+                                                (const uint32_t *)num.b.p, H.ord.b.p, (size_t)n, 0, end_bit, c->stream));
+  HIP_TRY(c, hipcub::DeviceRunLengthEncode::Encode(scratch.b.p, rle_bytes, (const uint64_t *)key_sorted.b.p, run_key.b.p,
+                                                   run_len.b.p, nruns.b.p, (int)n, c->stream));
+  uint32_t G = 0;
+  HIP_TRY(c, hipMemcpyAsync(&G, nruns.b.p, sizeof G, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (G == 0 || G > n)
+    return fail(c, CMPR_EDEVICE, "cmpr_hamming: the group count is out of range");
+  H.keys.resize(G);
+  std::vector<uint32_t> lens(G);
+  HIP_TRY(c, hipMemcpyAsync(H.keys.data(), run_key.b.p, (size_t)G * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(lens.data(), run_len.b.p, (size_t)G * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+
+  /* the group table; the packed words */
+  const uint32_t per_word = c->opt.alphabet_size == 4 ? NT_PER_WORD : AA_PER_WORD;
+  H.groups.resize(G);
+  uint64_t start = 0, words = 0;
+  for (uint32_t g = 0; g < G; g++) {
+    HmGroup &x = H.groups[g];
+    x.len = (uint32_t)(genes ? H.keys[g] / (n_v * n_j) : H.keys[g]);
+    x.stride = stride_of(x.len, per_word);
+    x.start = (uint32_t)start;
+    x.count = lens[g];
+    x.pk_off = words;
+    start += x.count;
+    words += (uint64_t)x.count * x.stride;
+  }
+  if (start != n || H.groups.back().len > H.longest)
+    return fail(c, CMPR_EDEVICE, "cmpr_hamming: the groups do not add up to the set");
+  if (words > (1ull << 38))
+    return fail(c, CMPR_EUNSUPPORTED, "cmpr_hamming: more than 2^38 packed words in one set");
+  Tmp<HmGroup> d_groups;
+  if ((rc = dev_upload(c, d_groups.b, H.groups.data(), H.groups.size()))) return rc;
+  if ((rc = dev_alloc(c, H.pk.b, (size_t)words))) return rc;
+  PackParams Q{d_groups.b.p, G, per_word, 32 / per_word, H.res.b.p, H.off.b.p, H.ord.b.p, words, H.pk.b.p};
+  hipLaunchKernelGGL(hm_pack_kernel, dim3(blocks_for(words, HM_WG)), dim3(HM_WG), 0, c->stream, Q);
+  HIP_TRY(c, hipGetLastError());
+  HIP_TRY(c, hipStreamSynchronize(c->stream));             /* (d_groups and the sort's temporaries leave scope) */
+  return CMPR_OK;
+}
+
+/* what the four entry points share: the refusals, both sets on the device, the pairs of groups */
+struct HmJob {
+  HmSet          own1, own2;
+  HmSet         *s1 = nullptr, *s2 = nullptr;
+  Tmp<HmPair>    pairs;
+  HmParams       P{};
+  uint32_t       blocks = 0;
+  std::vector<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> runs;   /* stride | first workgroup, workgroups */
+};
+
+int hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                int64_t differences, bool matrix, bool on_device)
+{
+  if (differences < 0)
+    return fail(c, CMPR_EINVAL, "Differences specified with -d or -differences cannot be negative.");
+  if (c->opt.indels)
+    return fail(c, CMPR_EINVAL, who + ": the all-against-all path has no indels");
+  if (matrix && is_f64_score(c->opt))
+    return fail(c, CMPR_EINVAL, who + ": ratio score needs cmpr_overlap_matrix_f64");
+  if (differences > 0 && (c->opt.score == CMPR_SCORE_MH || c->opt.score == CMPR_SCORE_JACCARD))
+    return fail(c, CMPR_EINVAL, "The Morisita-Horn / Jaccard index is not defined when d>0");
+  std::string why;
+  int rc;
+  if ((rc = validate_view(c->opt, set1, why, on_device)) || (rc = validate_view(c->opt, set2, why, on_device)))
+    return fail(c, rc, why);
+  if (c->work_shard_count > 1)
+    return fail(c, CMPR_EUNSUPPORTED, who + ": the call sees whole sets, every shard would give the whole answer "
+                                      "(work_shard_count > 1)");
+  if (!c->opt.ignore_genes &&
+      (uint64_t)std::max<uint32_t>(1, c->opt.n_v_genes) * std::max<uint32_t>(1, c->opt.n_j_genes) > (1ull << 46))
+    return fail(c, CMPR_EUNSUPPORTED, who + ": (length, V, J) does not fit a 64-bit key (n_v_genes x n_j_genes > 2^46)");
+  return CMPR_OK;
+}
+
+int hm_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
+             int64_t differences, bool on_device, HmJob &J)
+{
+  int rc;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = hm_prepare(c, set1, on_device, J.own1))) return rc;
+  J.s1 = &J.own1;
+  if (set2 == set1) {
+    J.s2 = J.s1;
+  } else {
+    if ((rc = hm_prepare(c, set2, on_device, J.own2))) return rc;
+    J.s2 = &J.own2;
+  }
+  HmSet &A = *J.s1, &B = *J.s2;
+  /* the groups of the two sets with one key; their workgroups, in runs of one form */
+  std::vector<HmPair> pairs;
+  uint64_t blocks = 0;
+  uint32_t nr_max = 0;
+  for (size_t a = 0, b = 0; a < A.keys.size() && b < B.keys.size();) {
+    if (A.keys[a] < B.keys[b]) {
+      a++;
+    } else if (B.keys[b] < A.keys[a]) {
+      b++;
+    } else {
+      const HmGroup &ga = A.groups[a], &gb = B.groups[b];
+      HmPair p{ga.pk_off, gb.pk_off, ga.start, ga.count, gb.start, gb.count, ga.stride, (uint32_t)blocks};
+      const uint32_t nb = blocks_for(ga.count, HM_WG);
+      const uint32_t form = c->hamming_generic || p.stride > HAMMING_REG_WORDS ? 0u : p.stride;
+      if (!J.runs.empty() && J.runs.back().first == form)
+        J.runs.back().second.second += nb;
+      else
+        J.runs.push_back({form, {(uint32_t)blocks, nb}});
+      blocks += nb;
+      nr_max = std::max(nr_max, gb.count);
+      pairs.push_back(p);
+      a++;
+      b++;
+    }
+  }
+  if (blocks > 0xffffffu)
+    return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^24 workgroups of queries");
+  J.blocks = (uint32_t)blocks;
+  if (!pairs.empty()) {
+    if ((rc = dev_upload(c, J.pairs.b, pairs.data(), pairs.size()))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));           /* (`pairs` leaves scope) */
+  }
+  /* segments: as many as fill the machine while the query tiles alone do not, none shorter than a wave of references */
+  uint32_t S = 1;
+  if (c->hamming_segments) {
+    S = (uint32_t)c->hamming_segments;
+  } else if (blocks) {
+    const uint64_t target = (uint64_t)c->cus * 8;
+    S = (uint32_t)std::min<uint64_t>(HM_MAX_SEGMENTS, (target + blocks - 1) / blocks);
+    S = std::max<uint32_t>(1, std::min<uint32_t>(S, (nr_max + 63) / 64));
+  }
+  const uint64_t longest = std::max(A.longest, B.longest);
+  HmParams &P = J.P;
+  P.pairs = J.pairs.b.p;
+  P.npairs = (uint32_t)pairs.size();
+  P.segments = S;
+  P.pk1 = A.pk.b.p; P.pk2 = B.pk.b.p;
+  P.ord1 = A.ord.b.p; P.ord2 = B.ord.b.p;
+  P.d = (uint32_t)std::min<uint64_t>((uint64_t)differences, longest);   /* above the longest sequence: as that length */
+  P.stage_refs = (uint32_t)c->hamming_stage_refs;
+  return CMPR_OK;
+}
+
+/* the compare kernel over every pair of groups: a launch per run of pairs of one form */
+template <int SINK>
+int hm_launch(cmpr_context *c, const HmJob &J)
+{
+  const bool nt = c->opt.alphabet_size == 4;
+  for (const auto &run : J.runs) {
+    const HmKernel fn = nt ? hm_kernel_for<SINK, true>(run.first) : hm_kernel_for<SINK, false>(run.first);
+    HmParams P = J.P;
+    P.blk_base = run.second.first;
+    hipLaunchKernelGGL(fn, dim3(run.second.second, P.segments), dim3(HM_WG), 0, c->stream, P);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return CMPR_OK;
+}
+
+int hamming_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t differences,
+                        void *matrix_out, bool on_device)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  const std::string who = "cmpr_hamming_matrix";
+  int rc;
+  if ((rc = hm_refusals(c, who, set1, set2, differences, true, on_device)))
+    return rc;
+  if (!matrix_out)
+    return fail(c, CMPR_EINVAL, who + ": matrix_out is NULL");
+  auto t0 = std::chrono::steady_clock::now();
+  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
+  HmJob J;
+  if ((rc = hm_setup(c, who, set1, set2, differences, on_device, J)))
+    return rc;
+  c->hm_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+
+  const uint64_t rows = c->opt.existence ? J.s1->n : J.s1->R, cells = rows * J.s2->R;
+  if (cells == 0)
+    return CMPR_OK;
+  Tmp<unsigned long long> own;
+  unsigned long long *matrix = (unsigned long long *)matrix_out;
+  if (!on_device) {
+    if ((rc = dev_alloc(c, own.b, (size_t)cells))) return rc;
+    matrix = own.b.p;
+  }
+  HIP_TRY(c, hipMemsetAsync(matrix, 0, cells * sizeof(unsigned long long), c->stream));
+  HmParams &P = J.P;
+  P.rep1 = J.s1->rep.b.p; P.rep2 = J.s2->rep.b.p;
+  P.cnt1 = c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p;
+  P.cnt2 = c->opt.ignore_counts ? nullptr : J.s2->cnt.b.p;
+  P.R2 = J.s2->R;
+  P.score = (uint32_t)c->opt.score;
+  P.existence = c->opt.existence ? 1u : 0u;
+  P.mat_lds = !c->opt.existence && cells <= HM_MAT_CELLS ? 1u : 0u;
+  P.matrix = matrix;
+  P.cells = (uint32_t)std::min<uint64_t>(cells, HM_MAT_CELLS);
+  if ((rc = hm_launch<SINK_MATRIX>(c, J)))
+    return rc;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  c->hm_ms[1] = ms_since(t0);
+  if (!on_device) {
+    t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipMemcpyAsync(matrix_out, matrix, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->hm_ms[2] = ms_since(t0);
+  }
+  return CMPR_OK;
+}
+
+int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t differences,
+                           uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out, uint16_t *dist_out,
+                           uint64_t *n_edges_out, bool on_device)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  const std::string who = "cmpr_hamming_neighbors";
+  if (!n_edges_out)
+    return fail(c, CMPR_EINVAL, who + ": n_edges_out is NULL");
+  *n_edges_out = 0;
+  if (capacity && !hit_out)
+    return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
+  int rc;
+  if ((rc = hm_refusals(c, who, set1, set2, differences, false, on_device)))
+    return rc;
+  auto t0 = std::chrono::steady_clock::now();
+  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
+  HmJob J;
+  if ((rc = hm_setup(c, who, set1, set2, differences, on_device, J)))
+    return rc;
+  c->hm_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+
+  /* count per (query, segment); the sum; the rows */
+  const uint64_t n1 = J.s1->n, S = J.P.segments, slots = n1 * S + 1;   /* (a zero behind the last: the sum's last is the total) */
+  if (slots > 0x7fffffffull)
+    return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^31-1 (query, segment) counts");
+  Tmp<uint32_t> cnt, d_hit;
+  Tmp<unsigned long long> offs;
+  Tmp<uint64_t> d_rows;
+  Tmp<uint16_t> d_dist;
+  Tmp<char> scan_tmp;
+  if ((rc = dev_alloc(c, cnt.b, (size_t)slots))) return rc;
+  if ((rc = dev_alloc(c, offs.b, (size_t)slots))) return rc;
+  HIP_TRY(c, hipMemsetAsync(cnt.b.p, 0, slots * sizeof(uint32_t), c->stream));
+  HmParams &P = J.P;
+  P.cnt = cnt.b.p;
+  if ((rc = hm_launch<SINK_CSR>(c, J)))
+    return rc;
+  hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> wide(cnt.b.p, U32To64());
+  size_t scan_bytes = 0;
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, wide, offs.b.p, (int)slots, c->stream));
+  if ((rc = dev_alloc(c, scan_tmp.b, scan_bytes))) return rc;
+  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(scan_tmp.b.p, scan_bytes, wide, offs.b.p, (int)slots, c->stream));
+  uint64_t *rows = on_device ? row_start_out : nullptr;
+  if (row_start_out && !on_device) {
+    if ((rc = dev_alloc(c, d_rows.b, (size_t)(n1 + 1)))) return rc;
+    rows = d_rows.b.p;
+  }
+  if (rows) {
+    hipLaunchKernelGGL(hm_rows_kernel, dim3(blocks_for(n1 + 1, HM_WG)), dim3(HM_WG), 0, c->stream, offs.b.p, n1,
+                       (uint32_t)S, rows);
+    HIP_TRY(c, hipGetLastError());
+  }
+  unsigned long long total = 0;
+  HIP_TRY(c, hipMemcpyAsync(&total, offs.b.p + (slots - 1), sizeof total, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  *n_edges_out = total;
+
+  /* the same walk again, every hit to its place -- when there is room for all of them */
+  const bool fill = hit_out && total && total <= capacity;
+  uint32_t *hit = on_device ? hit_out : nullptr;
+  uint16_t *dist = on_device ? dist_out : nullptr;
+  if (fill) {
+    if (!on_device) {
+      if ((rc = dev_alloc(c, d_hit.b, (size_t)total))) return rc;
+      hit = d_hit.b.p;
+      if (dist_out) {
+        if ((rc = dev_alloc(c, d_dist.b, (size_t)total))) return rc;
+        dist = d_dist.b.p;
+      }
+    }
+    P.offs = offs.b.p;
+    P.hit = hit;
+    P.dist = dist;
+    if ((rc = hm_launch<SINK_CSR>(c, J)))
+      return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  c->hm_ms[1] = ms_since(t0);
+  if (!on_device) {
+    t0 = std::chrono::steady_clock::now();
+    if (row_start_out)
+      HIP_TRY(c, hipMemcpyAsync(row_start_out, rows, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if (fill) {
+      HIP_TRY(c, hipMemcpyAsync(hit_out, hit, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      if (dist_out)
+        HIP_TRY(c, hipMemcpyAsync(dist_out, dist, (size_t)total * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->hm_ms[2] = ms_since(t0);
+  }
+  return CMPR_OK;
+}
+
+}  // namespace
+
+extern "C" int cmpr_hamming_matrix(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                                   int64_t differences, uint64_t *matrix_out)
+{
+  return guarded(c, [&] { return hamming_matrix_impl(c, set1, set2, differences, matrix_out, false); });
+}
+
+extern "C" int cmpr_hamming_matrix_device(cmpr_context *c, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                          int64_t differences, void *d_matrix)
+{
+  return guarded(c, [&] { return hamming_matrix_impl(c, d_set1, d_set2, differences, d_matrix, true); });
+}
+
+extern "C" int cmpr_hamming_neighbors(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                                      int64_t differences, uint64_t capacity, uint64_t *row_start_out,
+                                      uint32_t *hit_out, uint16_t *distance_out, uint64_t *n_edges_out)
+{
+  return guarded(c, [&] {
+    return hamming_neighbors_impl(c, set1, set2, differences, capacity, row_start_out, hit_out, distance_out,
+                                  n_edges_out, false);
+  });
+}
+
+extern "C" int cmpr_hamming_neighbors_device(cmpr_context *c, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                             int64_t differences, uint64_t capacity, uint64_t *d_row_start_out,
+                                             uint32_t *d_hit_out, uint16_t *d_distance_out, uint64_t *n_edges_out)
+{
+  return guarded(c, [&] {
+    return hamming_neighbors_impl(c, d_set1, d_set2, differences, capacity, d_row_start_out, d_hit_out,
+                                  d_distance_out, n_edges_out, true);
+  });
+}

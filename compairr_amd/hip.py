@@ -33,6 +33,8 @@ EXPORTS = [
     "cmpr_existence_csr", "cmpr_existence_csr_device",
     "cmpr_cluster_table", "cmpr_cluster_table_device",
     "cmpr_neighbors_distance", "cmpr_neighbors_distance_device",
+    "cmpr_hamming_matrix", "cmpr_hamming_matrix_device",
+    "cmpr_hamming_neighbors", "cmpr_hamming_neighbors_device",
 ]
 
 
@@ -172,6 +174,14 @@ def load_library() -> C.CDLL:
         lib.cmpr_neighbors_distance.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.POINTER(C.c_uint64)]
         lib.cmpr_neighbors_distance_device.argtypes = lib.cmpr_neighbors_distance.argtypes
+    if hasattr(lib, "cmpr_hamming_matrix"):        # (likewise: tools/hamming_timing.py --against)
+        lib.cmpr_hamming_matrix.argtypes = [C.c_void_p, C.POINTER(_SetView), C.POINTER(_SetView), C.c_int64,
+                                            C.c_void_p]
+        lib.cmpr_hamming_matrix_device.argtypes = lib.cmpr_hamming_matrix.argtypes
+        lib.cmpr_hamming_neighbors.argtypes = [C.c_void_p, C.POINTER(_SetView), C.POINTER(_SetView), C.c_int64,
+                                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(C.c_uint64)]
+        lib.cmpr_hamming_neighbors_device.argtypes = lib.cmpr_hamming_neighbors.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -507,6 +517,55 @@ class HipOverlap:
                                                         C.c_void_p(d_value or None), C.byref(n)))
         return n.value
 
+    # ---- the all-against-all path for any d (include/compairr_hip.h: cmpr_hamming_*) ----
+
+    def hamming_matrix(self, set1: RepertoireSet, set2: RepertoireSet, differences: int) -> np.ndarray:
+        """The R1 x R2 matrix (n1 x R2 with `existence`) of set1 against set2 over the pairs of equal length, equal
+        V and J (unless ignore_genes) and at most `differences` differing positions -- the integer sums of
+        overlap_matrix().  `set2 is set1`: one-file mode, the (i, i) pairs included.  The context's own
+        `differences` and resident sets play no part."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is set1 else _view(set2)
+        rows = set1.n if self.opt.existence else set1.n_repertoires
+        out = np.zeros((rows, set2.n_repertoires), dtype=np.uint64)
+        self._check(self._lib.cmpr_hamming_matrix(self._ctx, C.byref(v1), C.byref(v2), differences, out.ctypes.data))
+        return out
+
+    def hamming_matrix_device(self, view1: _SetView, view2: _SetView, differences: int, d_matrix: int) -> None:
+        """The same for views of device pointers (device_view; the same object twice: one-file mode) into the
+        device array d_matrix (uint64[R1 * R2], or [n1 * R2] with `existence`)."""
+        self._check(self._lib.cmpr_hamming_matrix_device(self._ctx, C.byref(view1), C.byref(view2), differences,
+                                                         C.c_void_p(d_matrix or None)))
+
+    def hamming_neighbors(self, set1: RepertoireSet, set2: RepertoireSet, differences: int, distances: bool = True):
+        """(row_start uint64[n1 + 1], hits uint32[E], distance uint16[E] or None): the same pairs as CSR -- the
+        hits of sequence i of set1, increasing, are hits[row_start[i]:row_start[i + 1]], the number of differing
+        positions beside each.  One count-only call, then one with the exact capacity."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is set1 else _view(set2)
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_hamming_neighbors(self._ctx, C.byref(v1), C.byref(v2), differences, 0, None, None,
+                                                     None, C.byref(n)))
+        row_start = np.zeros(set1.n + 1, dtype=np.uint64)
+        hits = np.zeros(n.value, dtype=np.uint32)
+        dist = np.zeros(n.value, dtype=np.uint16) if distances else None
+        self._check(self._lib.cmpr_hamming_neighbors(
+            self._ctx, C.byref(v1), C.byref(v2), differences, n.value, row_start.ctypes.data,
+            hits.ctypes.data if n.value else None, dist.ctypes.data if distances and n.value else None, C.byref(n)))
+        assert n.value == len(hits)
+        return row_start, hits, dist
+
+    def hamming_neighbors_device(self, view1: _SetView, view2: _SetView, differences: int, capacity: int = 0,
+                                 d_row_start: int = 0, d_hits: int = 0, d_distance: int = 0) -> int:
+        """The same for views of device pointers into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted),
+        d_hits (uint32[capacity]; 0 with capacity 0: count only) and d_distance (uint16[capacity]; 0: hits only).
+        Returns the edge count; when it exceeds `capacity` nothing was written to d_hits or d_distance."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_hamming_neighbors_device(
+            self._ctx, C.byref(view1), C.byref(view2), differences, capacity, C.c_void_p(d_row_start or None),
+            C.c_void_p(d_hits or None), C.c_void_p(d_distance or None), C.byref(n)))
+        return n.value
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -588,6 +647,28 @@ def neighbors_distance(set1: RepertoireSet, set2: RepertoireSet, opt: Options, t
         h.set_reference(set2, set1.longest)
         h.set_queries(set1)
         return h.neighbors_distance()
+
+
+def hamming_matrix(set1: RepertoireSet, set2: RepertoireSet, opt: Options, differences: int,
+                   tunables: Optional[dict] = None):
+    """Convenience: the matrix of set1 against set2 at any `differences` (HipOverlap.hamming_matrix) on a context
+    of its own; `opt.differences` plays no part.  `tunables` are set on the context first (the result never
+    depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        return h.hamming_matrix(set1, set2, differences)
+
+
+def hamming_neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, differences: int,
+                      tunables: Optional[dict] = None, distances: bool = True):
+    """Convenience: (row_start, hits, distance) of set1 against set2 at any `differences`
+    (HipOverlap.hamming_neighbors) on a context of its own; `opt.differences` plays no part.  `tunables` are set on
+    the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        return h.hamming_neighbors(set1, set2, differences, distances)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

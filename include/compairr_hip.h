@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -543,6 +543,74 @@ int cmpr_cluster_table_device(cmpr_context *ctx, const cmpr_set_view *d_set,
                               uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out);
 
 /*
+ * The reference's all-against-all path, for ANY d: above d = 2 (MAXDIFF_HASH, overlap.cc:368) the reference stops
+ * hashing variants and compares every query with every sequence of set 2 (process_trad, overlap.cc:286-359; seq_diff,
+ * util.cc:172-184).  cmpr_create() still refuses options.differences > 2; these calls take the distance as an
+ * ARGUMENT and the two sets as views, as cmpr_deduplicate() takes its set, and options.differences plays no part.
+ *
+ * The pair relation is that of process_trad (overlap.cc:286-359), nothing filtered: (i of set1, j of set2) is a pair
+ * when the two sequences have the same length (two empty sequences included), the same V and J gene numbers unless
+ * options.ignore_genes, and differ at no more than `differences` positions.  With set2 == set1 (the same pointer)
+ * the set is uploaded once and the (i, i) pairs are included, as in the reference's one-file mode.
+ *   differences   any value >= 0, also 0, 1 and 2; negative is CMPR_EINVAL ("Differences specified with -d or
+ *                 -differences cannot be negative.").  A value above the longest sequence behaves as that length.
+ *
+ * cmpr_hamming_matrix() (overlap.cc:286-359 with the sums of overlap.cc:218-231) writes R1 x R2 uint64 -- n1 x R2
+ * with options.existence -- of exactly the integer sums cmpr_overlap_matrix() documents: product, min, max, mean as
+ * count1 + count2, 1 per pair with ignore_counts, uint64 arithmetic that wraps.  The output is overwritten.
+ * cmpr_hamming_matrix_device() takes DEVICE views, as cmpr_set_queries_device() does, and d_matrix on the context's
+ * device.
+ *
+ * cmpr_hamming_neighbors() (overlap.cc:286-359 with the pair list of overlap.cc:232-245) gives the pairs as CSR with
+ * the distance of every edge, under the protocol of cmpr_neighbors_distance(), word for word:
+ *   row_start_out[n1 + 1]   always written in full and always exact, whatever `capacity` is; may be NULL.
+ *   hit_out[capacity]       row i occupies [row_start[i], row_start[i + 1]): sequence numbers of set2 in strictly
+ *                           increasing order.  With more edges than `capacity` NOTHING is written to hit_out or
+ *                           distance_out and the call still returns CMPR_OK with *n_edges_out > capacity.
+ *                           capacity == 0 with both arrays NULL is the count-only call; capacity > 0 with hit_out
+ *                           NULL is CMPR_EINVAL.  Elements behind the last edge are not written.
+ *   distance_out[capacity]  the number of differing positions of the pair, 0 .. differences; uint16_t: validation
+ *                           caps a sequence at 65535 residues, so a distance fits, and a byte does not once d > 255.
+ *                           May be NULL (hits only).
+ *   *n_edges_out            required (NULL: CMPR_EINVAL), a HOST pointer in both variants; == row_start[n1].
+ * cmpr_hamming_neighbors_device() takes DEVICE views and the three arrays as device memory: nothing per sequence or
+ * per edge crosses PCIe, only two offsets per set, the group tables (one entry per distinct (length, V, J)) and the
+ * edge count.
+ *
+ * All four: synchronous; callable any time after cmpr_create(); the sets are validated as every other set (same
+ * codes and texts, passed through unchanged); the resident sets, plans and statistics are not disturbed; every
+ * temporary is freed on every return; results are bit-identical from run to run and under every tunable (integer
+ * sums; a row is one walk over one group in increasing sequence number -- no atomics, no row sort).  n1 == 0 or
+ * n2 == 0 is CMPR_OK with a zero matrix, or row_start all zero.  Refused before any device work: options.indels
+ * (CMPR_EINVAL, "the all-against-all path has no indels"); CMPR_SCORE_RATIO without ignore_counts in _matrix
+ * (CMPR_EINVAL, use cmpr_overlap_matrix_f64(): there is no f64 form of this call); MH / Jaccard with differences > 0
+ * (CMPR_EINVAL); a NULL set (CMPR_EINVAL); the tunable work_shard_count above 1 (CMPR_EUNSUPPORTED: the call sees
+ * whole sets, N sharded contexts would each give the whole answer); n_v_genes x n_j_genes above 2^46
+ * (CMPR_EUNSUPPORTED: (length, V, J) must fit a 64-bit key).  At most 2^31-1 sequences per set.
+ *
+ * How (compairr_amd/csrc/hamming.hip): each set is sorted by (length, V, J) -- a stable radix sort, so a group keeps
+ * its sequences in increasing number --, its residues are packed in group order (four amino acids or sixteen
+ * nucleotides per 32-bit word), and a workgroup compares 256 queries of a group with a segment of the matching set-2
+ * group staged in LDS, every lane its own query.  Device memory for the duration of the call, per sequence of either
+ * set: the validated copy (~45 bytes), 24 bytes of keys and sequence numbers before and behind the sort, 12 of run
+ * keys and lengths and the sort's scratch (these freed before the comparison), 4 for the group order, and the
+ * packed residues (4 bytes per 4 amino acids or 16 nucleotides, rounded up to 1, 2, 3, 4, 5, 6, 8, 12 or 16 words
+ * up to 64 amino acids / 256 nucleotides).  _neighbors adds 12 bytes per (query, segment) -- the segment count is 1
+ * once set 1 alone fills the machine, and at most 64 --; the host variants add what the device variants are handed:
+ * 8 bytes per matrix cell, or 8 per query and 6 per edge (4 without distances).
+ */
+int cmpr_hamming_matrix(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                        int64_t differences, uint64_t *matrix_out);
+int cmpr_hamming_matrix_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                               int64_t differences, void *d_matrix);
+int cmpr_hamming_neighbors(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                           int64_t differences, uint64_t capacity, uint64_t *row_start_out,
+                           uint32_t *hit_out, uint16_t *distance_out, uint64_t *n_edges_out);
+int cmpr_hamming_neighbors_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                  int64_t differences, uint64_t capacity, uint64_t *d_row_start_out,
+                                  uint32_t *d_hit_out, uint16_t *d_distance_out, uint64_t *n_edges_out);
+
+/*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
  * runtime, the device's context, the code objects of the kernels the given options will run.
  * The reference has no counterpart -- its threads start in microseconds (overlap.cc:926-936);
@@ -664,6 +732,12 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
                              sequence number (0..32, default 32).  At 0 every occupied slot of a chain passes
                              the tag test and is compared in full: the path a tag collision takes, a 2^-32
                              event otherwise
+     "hamming_stage_refs"    TEST ONLY, cmpr_hamming_*(): references staged per LDS piece (0 = default: as many as
+                             fit 16 KiB, at most 512; a larger value is clamped to that)
+     "hamming_segments"      TEST ONLY: forces the number of segments a set-2 group is walked in (1..64; 0 = default:
+                             automatic, from the number of query workgroups)
+     "hamming_generic"       TEST ONLY: 1 sends every group through the long-sequence form (query words read from
+                             global memory), 0 (default) only groups of more than 16 words per sequence
    What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
    the state):
      before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",
@@ -690,7 +764,10 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    to the host), "existence_reduce_us" (the cells; 0 when they did not fit) and "existence_copy_us" (host variant);
    and of the last cmpr_cluster_table*(), host times, each part ending in a wait: "cluster_links_us" (the set as
    both sets, the link step, labels and sizes flat on the device) and "cluster_table_us" (everything after: the
-   numbering, the members, the counts and, in the host variant, their copies). */
+   numbering, the members, the counts and, in the host variant, their copies); and of the last cmpr_hamming_*(),
+   host times, each part ending in a wait: "hamming_group_us" (upload, validation, keys, sort, groups, packing),
+   "hamming_compare_us" (the compare kernel: once for a matrix, the count step, the sum and the fill step for
+   neighbours) and "hamming_copy_us" (host variant: the results copied out). */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

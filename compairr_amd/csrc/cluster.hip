@@ -68,7 +68,7 @@ cluster_init_kernel(uint32_t *parent, uint64_t n)
 }
 
 /* The forest is final (kernel boundary): plain loads, and nothing is written to it -- a lane's walk does not
-   depend on how far another lane has come.  A parent is smaller than its child (kernels.h link_pair), so the
+   depend on how far another lane has come.  A parent is smaller than its child (link_forest.h link_pair), so the
    walk ends at the tree's smallest number.  roots: the number of i with label[i] == i. */
 __global__ void __launch_bounds__(CLUSTER_WG)
 cluster_flatten_kernel(const uint32_t *parent, uint32_t *label, uint64_t n, unsigned long long *roots)
@@ -127,19 +127,73 @@ cluster_gather_kernel(const uint32_t *label, const uint32_t *cnt, uint32_t *size
     size[i] = cnt[label[i]];
 }
 
+}  // namespace
+
+int cmpr_cluster_forest(cmpr_context *c, uint64_t n, ClusterLinks &L)
+{
+  int rc;
+  if ((rc = dev_alloc(c, L.parent.b, (size_t)n))) return rc;
+  if ((rc = dev_alloc(c, L.roots.b, 1))) return rc;
+  hipLaunchKernelGGL(cluster_init_kernel, dim3(blocks_for(n, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
+                     L.parent.b.p, n);
+  HIP_TRY(c, hipGetLastError());
+  return CMPR_OK;
+}
+
+int cmpr_cluster_flatten(cmpr_context *c, uint64_t n, uint32_t *d_label, uint32_t *d_size, bool want_size,
+                         ClusterLinks &L)
+{
+  int rc;
+  uint32_t *label = d_label;
+  if (!label) {
+    if ((rc = dev_alloc(c, L.labels.b, (size_t)n))) return rc;
+    label = L.labels.b.p;
+  }
+  uint32_t *const parent = L.parent.b.p;
+  const dim3 grid(blocks_for(n, CLUSTER_WG)), wg(CLUSTER_WG);
+  HIP_TRY(c, hipMemsetAsync(L.roots.b.p, 0, sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(cluster_flatten_kernel, grid, wg, 0, c->stream, parent, label, n, L.roots.b.p);
+  HIP_TRY(c, hipGetLastError());
+  if (want_size) {
+    /* the counts go where the sizes will be (a device array of the caller) or where the forest was */
+    uint32_t *cnt = d_size ? d_size : parent;
+    HIP_TRY(c, hipMemsetAsync(cnt, 0, n * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(cluster_count_kernel, grid, wg, 0, c->stream, label, cnt, n);
+    HIP_TRY(c, hipGetLastError());
+    hipLaunchKernelGGL(cluster_gather_kernel, grid, wg, 0, c->stream, label, cnt, cnt, n);
+    HIP_TRY(c, hipGetLastError());
+    L.size = cnt;
+  }
+  L.label = label;
+  L.n = n;
+  return CMPR_OK;
+}
+
+int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, bool on_device, uint32_t *label_out, uint32_t *size_out,
+                         uint64_t *n_clusters_out)
+{
+  const uint64_t n = L.n;
+  if (n == 0)
+    return CMPR_OK;
+  if (!on_device && size_out)
+    HIP_TRY(c, hipMemcpyAsync(size_out, L.size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  if (!on_device && label_out)
+    HIP_TRY(c, hipMemcpyAsync(label_out, L.label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  unsigned long long clusters = 0;
+  HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_clusters_out)
+    *n_clusters_out = clusters;
+  return CMPR_OK;
+}
+
+namespace {
+
 /* What cmpr_cluster and cmpr_cluster_table share: the refusals, the set as both sets, the link step, the
    flat labels and (want_size) the sizes, all queued on the context's stream and NOT waited for.  d_label,
-   d_size: device arrays of the caller's to take them, or NULL -- the labels then go to an array of L's, the
-   sizes to where the forest was.  n == 0 leaves L.n == 0 and nothing queued. */
-struct Links {
-  Tmp<uint32_t> parent, labels;
-  Tmp<unsigned long long> roots;
-  uint32_t *label = nullptr, *size = nullptr;
-  uint64_t n = 0;
-};
-
+   d_size: as cmpr_cluster_flatten takes them.  n == 0 leaves L.n == 0 and nothing queued. */
 int cluster_links(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *d_label, uint32_t *d_size,
-                  bool want_size, uint64_t *n_clusters_out, Links &L)
+                  bool want_size, uint64_t *n_clusters_out, ClusterLinks &L)
 {
   if (!c)
     return CMPR_EINVAL;
@@ -162,61 +216,22 @@ int cluster_links(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint3
     return CMPR_OK;
   HIP_TRY(c, hipSetDevice(c->device));
 
-  if ((rc = dev_alloc(c, L.parent.b, (size_t)n))) return rc;
-  if ((rc = dev_alloc(c, L.roots.b, 1))) return rc;
-  uint32_t *label = d_label;
-  if (!label) {
-    if ((rc = dev_alloc(c, L.labels.b, (size_t)n))) return rc;
-    label = L.labels.b.p;
-  }
-  uint32_t *const parent = L.parent.b.p;
-  const dim3 grid((uint32_t)((n + CLUSTER_WG - 1) / CLUSTER_WG)), wg(CLUSTER_WG);
-
-  /* once, before the step: its repeats and its redo pass only add links that are already implied */
-  hipLaunchKernelGGL(cluster_init_kernel, grid, wg, 0, c->stream, parent, n);
-  HIP_TRY(c, hipGetLastError());
-  if ((rc = cmpr_link_step(c, parent)))
+  /* parent[i] = i once, before the step: its repeats and its redo pass only add links that are already implied */
+  if ((rc = cmpr_cluster_forest(c, n, L))) return rc;
+  if ((rc = cmpr_link_step(c, L.parent.b.p)))
     return rc;
-
-  HIP_TRY(c, hipMemsetAsync(L.roots.b.p, 0, sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(cluster_flatten_kernel, grid, wg, 0, c->stream, parent, label, n, L.roots.b.p);
-  HIP_TRY(c, hipGetLastError());
-  if (want_size) {
-    /* the counts go where the sizes will be (a device array of the caller) or where the forest was */
-    uint32_t *cnt = d_size ? d_size : parent;
-    HIP_TRY(c, hipMemsetAsync(cnt, 0, n * sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(cluster_count_kernel, grid, wg, 0, c->stream, label, cnt, n);
-    HIP_TRY(c, hipGetLastError());
-    hipLaunchKernelGGL(cluster_gather_kernel, grid, wg, 0, c->stream, label, cnt, cnt, n);
-    HIP_TRY(c, hipGetLastError());
-    L.size = cnt;
-  }
-  L.label = label;
-  L.n = n;
-  return CMPR_OK;
+  return cmpr_cluster_flatten(c, n, d_label, d_size, want_size, L);
 }
 
 int cluster_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *label_out,
                  uint32_t *size_out, uint64_t *n_clusters_out)
 {
-  Links L;
+  ClusterLinks L;
   int rc;
   if ((rc = cluster_links(c, s, on_device, on_device ? label_out : nullptr, on_device ? size_out : nullptr,
                           size_out != nullptr, n_clusters_out, L)))
     return rc;
-  const uint64_t n = L.n;
-  if (n == 0)
-    return CMPR_OK;
-  if (!on_device && size_out)
-    HIP_TRY(c, hipMemcpyAsync(size_out, L.size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (!on_device && label_out)
-    HIP_TRY(c, hipMemcpyAsync(label_out, L.label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  unsigned long long clusters = 0;
-  HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (n_clusters_out)
-    *n_clusters_out = clusters;
-  return CMPR_OK;
+  return cmpr_cluster_results(c, L, on_device, label_out, size_out, n_clusters_out);
 }
 
 /* ---- the table pass ---- */
@@ -303,16 +318,14 @@ int bit_length(uint64_t x)
   return x ? 64 - __builtin_clzll(x) : 0;
 }
 
-int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *cluster_of_out,
-               uint64_t *cluster_start_out, uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out)
+}  // namespace
+
+int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_cnt, bool on_device,
+                            uint32_t *cluster_of_out, uint64_t *cluster_start_out, uint32_t *member_out,
+                            uint64_t *count_out, uint64_t *n_clusters_out,
+                            std::chrono::steady_clock::time_point t0, double *flat_ms)
 {
-  auto t0 = std::chrono::steady_clock::now();
-  if (c)
-    c->cl_ms[0] = c->cl_ms[1] = 0;
-  Links L;
   int rc;
-  if ((rc = cluster_links(c, s, on_device, nullptr, nullptr, true, n_clusters_out, L)))
-    return rc;
   const uint64_t n = L.n;
   if (n == 0) {
     if (cluster_start_out && on_device) {
@@ -338,7 +351,7 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(&largest, largest_word.b.p, sizeof largest, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->cl_ms[0] = ms_since(t0);
+  *flat_ms = ms_since(t0);
   t0 = std::chrono::steady_clock::now();
   const uint64_t K = clusters;
   if (K == 0 || K > n || largest == 0 || largest > n)
@@ -352,7 +365,7 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   const bool want_of = cluster_of_out || want_members;
   if (!want_of && !cluster_start_out && !count_out)
     return CMPR_OK;
-  if (sum_counts && !c->cnt2.p)
+  if (sum_counts && !d_cnt)
     return fail(c, CMPR_ESTATE, "cmpr_cluster_table: the resident set has no counts");
 
   Tmp<uint32_t> root, key, root_sorted, key_sorted, of_tmp, member_tmp;
@@ -438,7 +451,7 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   if (sum_counts) {
     HIP_TRY(c, hipMemsetAsync(count, 0, (size_t)K * sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(table_count_kernel, dim3(blocks_for(n, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
-                       L.size, member, c->cnt2.p, count, n);
+                       L.size, member, d_cnt, count, n);
     HIP_TRY(c, hipGetLastError());
   } else if (count) {
     hipLaunchKernelGGL(table_sizes_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
@@ -460,6 +473,23 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->cl_ms[1] = ms_since(t0);
   return CMPR_OK;
+}
+
+namespace {
+
+int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *cluster_of_out,
+               uint64_t *cluster_start_out, uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  if (c)
+    c->cl_ms[0] = c->cl_ms[1] = 0;
+  ClusterLinks L;
+  int rc;
+  if ((rc = cluster_links(c, s, on_device, nullptr, nullptr, true, n_clusters_out, L)))
+    return rc;
+  /* the set is resident: its counts are the reference's (context.h cnt2) */
+  return cmpr_cluster_table_pass(c, L, c->cnt2.p, on_device, cluster_of_out, cluster_start_out, member_out, count_out,
+                                 n_clusters_out, t0, &c->cl_ms[0]);
 }
 
 }  // namespace

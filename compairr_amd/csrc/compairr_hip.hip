@@ -367,6 +367,7 @@ const Tunable TUNABLES[] = {
   {"hamming_stage_refs", F(hamming_stage_refs), 0, 65536, LOCK_NEVER, T_NO_PLAN, " must be 0..65536"},
   {"hamming_segments", F(hamming_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
   {"hamming_generic", F(hamming_generic), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  {"hamming_link_snapshot", F(hamming_link_snapshot), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
   {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
   {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
   {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},

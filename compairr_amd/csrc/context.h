@@ -208,6 +208,7 @@ struct cmpr_context {
   /* TEST ONLY, of cmpr_hamming_* (hamming.hip): references staged per LDS piece (0 = as many as fit), the
      segment count (0 = automatic), 1 = every group through the long-sequence form */
   int64_t hamming_stage_refs = 0, hamming_segments = 0, hamming_generic = 0;
+  int64_t hamming_link_snapshot = 1;  /* TEST ONLY, of cmpr_hamming_cluster*: 0 = every match goes to link_pair */
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */
@@ -533,6 +534,35 @@ int cmpr_upload_and_validate(cmpr_context *c, const cmpr_set_view *s, DevBuf<uin
    resident sets united in `parent` (one word per sequence, parent[i] == i or a forest that earlier steps
    left); the same run_step_and_wait loop as the other synchronous entry points */
 int cmpr_link_step(cmpr_context *c, uint32_t *parent);
+
+/* cluster.hip: what cmpr_cluster*, cmpr_cluster_table* (cluster.hip) and cmpr_hamming_cluster* (hamming.hip) share
+   around their link steps -- the forest, the flat labels and sizes, the results of the plain call, the table pass.
+   Everything is queued on the context's stream; only the last two wait. */
+struct ClusterLinks {
+  Tmp<uint32_t> parent, labels;
+  Tmp<unsigned long long> roots;
+  uint32_t *label = nullptr, *size = nullptr;
+  uint64_t n = 0;
+};
+/* the forest of n sequences and the root counter allocated, parent[i] = i queued (n > 0) */
+int cmpr_cluster_forest(cmpr_context *c, uint64_t n, ClusterLinks &L);
+/* behind the links: label[i] = the root of i, the roots counted and (want_size) size[i] = the members of i's
+   tree.  d_label, d_size: device arrays of the caller's to take them, or NULL -- the labels then go to an array
+   of L's, the sizes to where the forest was.  Sets L.label, L.size and L.n. */
+int cmpr_cluster_flatten(cmpr_context *c, uint64_t n, uint32_t *d_label, uint32_t *d_size, bool want_size,
+                         ClusterLinks &L);
+/* the end of cmpr_cluster / cmpr_hamming_cluster: labels and sizes to the host (host variant), the cluster
+   count; waits */
+int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, bool on_device, uint32_t *label_out, uint32_t *size_out,
+                         uint64_t *n_clusters_out);
+/* the table pass of cmpr_cluster_table / cmpr_hamming_cluster_table over flat labels and sizes (L.n == 0: only
+   cluster_start[0] = 0).  d_cnt: the duplicate_count of every sequence on the device (not looked at with
+   ignore_counts).  *flat_ms = the host time since t0 at the wait after which labels and sizes are flat;
+   cl_ms[1] = the time from there. */
+int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_cnt, bool on_device,
+                            uint32_t *cluster_of_out, uint64_t *cluster_start_out, uint32_t *member_out,
+                            uint64_t *count_out, uint64_t *n_clusters_out,
+                            std::chrono::steady_clock::time_point t0, double *flat_ms);
 
 /* compairr_hip.hip: the synchronous step in neighbour mode (cmpr_neighbors, neighbors.hip).  hit == NULL: the
    count step, every match adds one to degree[its query]; otherwise the fill step, every match takes a place of

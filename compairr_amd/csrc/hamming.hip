@@ -1,7 +1,9 @@
 /*
  * hamming.hip -- the reference's all-against-all path for any d (process_trad, overlap.cc:286-359; seq_diff,
  * util.cc:172-184) as library calls that take the distance as an argument: cmpr_hamming_matrix / _device and
- * cmpr_hamming_neighbors / _device.  A pair (i of set 1, j of set 2) matches when the two sequences have one length
+ * cmpr_hamming_neighbors / _device; and the reference's clusters on that path (process_trad, cluster.cc:165-211, swept by
+ * cluster.cc:276-410): cmpr_hamming_cluster / _device and cmpr_hamming_cluster_table / _device.  A pair (i of set 1, j of
+ * set 2) matches when the two sequences have one length
  * (two empty ones included), the same V and J gene numbers unless ignore_genes, and differ at no more than
  * `differences` positions.  Nothing is hashed: every query is compared with every sequence of its group.
  *
@@ -27,6 +29,14 @@
  *            segment) order (hipcub), and the same walk writes every hit and its distance at the lane's running
  *            offset.  All hits of a query lie in ONE set-2 group, walked in increasing sequence number: the rows
  *            come out sorted, without atomics and without a row sort.
+ *            link (the cluster calls: the set against itself, every group paired with itself): the forest of
+ *            link_forest.h over the ORIGINAL sequence numbers.  Position order inside a group is number order, so the
+ *            lane whose query sits at position qi links only references at positions above qi: every unordered pair
+ *            once, (i, i) never.  The workgroup of the queries [256b, 256b + 256) walks [256b + 1, nr), its segments
+ *            divide that range, and a wave skips what lies at or below its own first query.  Beside every staged
+ *            reference lies a snapshot of its root; a lane keeps its own root in a register, skips a match whose
+ *            snapshot equals it and looks its root up again after a link it made.  No count array, no pair list.
+ *            What follows the launch is cluster.hip's: flatten, sizes, and for the table calls the table pass.
  *
  * The (query, segment) count array has n1 x S words, S <= HM_MAX_SEGMENTS; the automatic S is above 1 only while
  * the query tiles alone do not fill the machine (S <= ceil(8 x CUs / workgroups)), which bounds it by
@@ -51,6 +61,7 @@ constexpr uint32_t HM_LDS_WORDS = 4096;        /* packed words of references sta
 constexpr uint32_t HM_STAGE_MAX = 512;         /* ... and at most this many references */
 constexpr uint32_t HM_MAT_CELLS = 1024;        /* a matrix of up to this many cells is privatised in LDS (8 KiB) */
 constexpr uint32_t HM_MAX_SEGMENTS = 64;
+constexpr uint32_t HM_LINK_SEGMENT = 16384;    /* link sink: references of the longest automatic segment (32 pieces) */
 constexpr uint32_t AA_PER_WORD = 4, NT_PER_WORD = 16;
 
 /* a group of one set: the sequences at positions start .. start + count - 1 of the sorted order */
@@ -85,9 +96,12 @@ struct HmParams {
   uint32_t        R2, score, existence, mat_lds;
   unsigned long long *matrix;
   uint32_t        cells;
+  /* link */
+  uint32_t       *parent;          /* the forest, over original sequence numbers (link_forest.h) */
+  uint32_t        snapshot;        /* 1: matches whose two root snapshots are equal are skipped */
 };
 
-enum { SINK_CSR = 0, SINK_MATRIX = 1 };
+enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2 };
 
 /* differing residues of two packed words.  Amino acids: a byte each, codes below 0x80, so neither the xor nor the
    sum carries into the next byte and bit 7 says "this byte is not zero".  Nucleotides: two bits each. */
@@ -118,6 +132,8 @@ struct LaneSink {
   /* matrix */
   unsigned long long acc = 0, row = 0, f = 1;
   uint32_t cur_rep = 0;
+  /* link: the root of the lane's query when it last looked */
+  uint32_t root = 0;
 };
 
 /* NW: words per sequence held in registers (the group's stride), 0: the generic form */
@@ -130,6 +146,7 @@ hm_compare_kernel(const HmParams P)
   __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? HM_STAGE_MAX : 1];
   __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? HM_STAGE_MAX : 1];
   __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? HM_MAT_CELLS : 1];
+  __shared__ uint32_t st_root[SINK == SINK_LINK ? HM_STAGE_MAX : 1];
 
   /* the pair of this workgroup: the last one whose first workgroup is not behind it */
   const uint32_t blk = P.blk_base + blockIdx.x;
@@ -147,10 +164,16 @@ hm_compare_kernel(const HmParams P)
   const bool active = qi < pr.nq;
   const uint32_t qpos = pr.q0 + (active ? qi : 0u);                     /* (an idle lane reads the group's first query) */
   const uint32_t qorig = P.ord1[qpos];
-  /* the segment of the set-2 group */
+  /* the segment of the set-2 group.  Link sink: set 2 IS set 1 and position order is number order (the stable
+     sort), so an unordered pair is walked once, by the lane of its smaller position: the workgroup whose first
+     query sits at position b walks the references behind b only, and its segments divide THAT range. */
   const uint32_t seg = blockIdx.y;
-  const uint32_t e0 = (uint32_t)((uint64_t)pr.nr * seg / P.segments);
-  const uint32_t e1 = (uint32_t)((uint64_t)pr.nr * (seg + 1) / P.segments);
+  const uint32_t w0 = SINK == SINK_LINK ? min((blk - pr.blk0) * HM_WG + 1u, pr.nr) : 0u;
+  const uint32_t e0 = w0 + (uint32_t)((uint64_t)(pr.nr - w0) * seg / P.segments);
+  const uint32_t e1 = w0 + (uint32_t)((uint64_t)(pr.nr - w0) * (seg + 1) / P.segments);
+  /* ... and a wave skips the staged references at or below its first query: no lane of it wants them */
+  const uint32_t wave_q0 = SINK == SINK_LINK
+      ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((blk - pr.blk0) * HM_WG + (threadIdx.x & ~(WAVE - 1u)))) : 0u;
 
   if (e0 >= e1)
     return;                                                             /* (the whole workgroup) */
@@ -172,6 +195,9 @@ hm_compare_kernel(const HmParams P)
   if (SINK == SINK_CSR) {
     if (P.offs)
       S.pos = P.offs[(uint64_t)qorig * P.segments + seg];
+  } else if (SINK == SINK_LINK) {
+    if (P.snapshot)
+      S.root = link_root(P.parent, qorig);
   } else {
     S.row = P.existence ? (unsigned long long)qorig : (unsigned long long)P.rep1[qorig];
     S.f = P.cnt1 ? P.cnt1[qorig] : 1ull;
@@ -197,6 +223,16 @@ hm_compare_kernel(const HmParams P)
       } else {
         S.hits++;
       }
+    } else if (SINK == SINK_LINK) {
+      /* (cluster.cc:165-211 lists the pair, :276-410 walks the lists: here the two trees become one.)  In a dense
+         group almost every match joins two sequences that share a root already: equal snapshots prove it --
+         trees only merge, whatever was once under a root stays in its component -- and cost no walk; unequal
+         ones, stale or not, fall through to link_pair, after which the lane looks its root up again. */
+      if (!P.snapshot || st_root[r] != S.root) {
+        link_pair(P.parent, qorig, st_id[r]);
+        if (P.snapshot)
+          S.root = link_root(P.parent, qorig);
+      }
     } else {
       /* the lane's sum belongs to one set-2 repertoire: a match in another one sends it to its cell first (a
          reference that does not match costs the matrix sink nothing) */
@@ -217,6 +253,8 @@ hm_compare_kernel(const HmParams P)
         st_rep[r] = P.rep2[id];
         st_cnt[r] = P.cnt2 ? P.cnt2[id] : 1ull;
       }
+      if (SINK == SINK_LINK && P.snapshot)
+        st_root[r] = link_root(P.parent, id);
     }
   };
 
@@ -233,7 +271,8 @@ hm_compare_kernel(const HmParams P)
         st_words[k] = src[k];
       stage_ids(e, n);
       __syncthreads();
-      for (uint32_t r = 0; r < n; r++) {
+      const uint32_t r0 = SINK == SINK_LINK && wave_q0 >= e ? min(wave_q0 - e + 1u, n) : 0u;
+      for (uint32_t r = r0; r < n; r++) {
         const uint32_t *const w = st_words + r * stride;
         uint32_t dd = 0;
         if (NW) {
@@ -244,7 +283,7 @@ hm_compare_kernel(const HmParams P)
           for (uint32_t k = 0; k < stride; k++)
             dd += diff_word<NT>(qw[k], w[k]);
         }
-        if (dd <= P.d && active)
+        if (dd <= P.d && active && (SINK != SINK_LINK || e + r > qi))
           sink(r, dd);
       }
     }
@@ -264,7 +303,7 @@ hm_compare_kernel(const HmParams P)
         for (uint32_t k = 0; k < m; k++)
           dd += diff_word<NT>(qw[k0 + k], st_words[k]);
       }
-      if (dd <= P.d && active)
+      if (dd <= P.d && active && (SINK != SINK_LINK || e > qi))
         sink(0, dd);
     }
   }
@@ -272,7 +311,7 @@ hm_compare_kernel(const HmParams P)
   if (SINK == SINK_CSR) {
     if (!P.offs && active)
       P.cnt[(uint64_t)qorig * P.segments + seg] = S.hits;
-  } else {
+  } else if (SINK == SINK_MATRIX) {
     flush();
     if (mat_lds) {
       __syncthreads();
@@ -498,16 +537,22 @@ struct HmJob {
   std::vector<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> runs;   /* stride | first workgroup, workgroups */
 };
 
+/* what a call makes of the pairs: the clusters take no score, so what the reference refuses of scores is not theirs */
+enum HmKind { HM_MATRIX, HM_NEIGHBORS, HM_CLUSTERS };
+
 int hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
-                int64_t differences, bool matrix, bool on_device)
+                int64_t differences, HmKind kind, bool on_device)
 {
   if (differences < 0)
     return fail(c, CMPR_EINVAL, "Differences specified with -d or -differences cannot be negative.");
   if (c->opt.indels)
     return fail(c, CMPR_EINVAL, who + ": the all-against-all path has no indels");
-  if (matrix && is_f64_score(c->opt))
+  if (kind == HM_CLUSTERS && c->opt.existence)
+    return fail(c, CMPR_EINVAL, "cmpr_cluster: clusters are not defined with options.existence");
+  if (kind == HM_MATRIX && is_f64_score(c->opt))
     return fail(c, CMPR_EINVAL, who + ": ratio score needs cmpr_overlap_matrix_f64");
-  if (differences > 0 && (c->opt.score == CMPR_SCORE_MH || c->opt.score == CMPR_SCORE_JACCARD))
+  if (kind != HM_CLUSTERS && differences > 0 &&
+      (c->opt.score == CMPR_SCORE_MH || c->opt.score == CMPR_SCORE_JACCARD))
     return fail(c, CMPR_EINVAL, "The Morisita-Horn / Jaccard index is not defined when d>0");
   std::string why;
   int rc;
@@ -523,7 +568,7 @@ int hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *se
 }
 
 int hm_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
-             int64_t differences, bool on_device, HmJob &J)
+             int64_t differences, bool on_device, HmJob &J, bool triangular = false)
 {
   int rc;
   HIP_TRY(c, hipSetDevice(c->device));
@@ -576,6 +621,11 @@ int hm_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
     const uint64_t target = (uint64_t)c->cus * 8;
     S = (uint32_t)std::min<uint64_t>(HM_MAX_SEGMENTS, (target + blocks - 1) / blocks);
     S = std::max<uint32_t>(1, std::min<uint32_t>(S, (nr_max + 63) / 64));
+    /* the link sink's workgroups walk what lies behind them: the first of a group all of it, the last nothing, and
+       the launch ends with the first ones of the largest group.  No segment longer than HM_LINK_SEGMENT references
+       keeps those as short as everybody else's */
+    if (triangular)
+      S = std::max(S, std::min<uint32_t>(HM_MAX_SEGMENTS, (nr_max + HM_LINK_SEGMENT - 1) / HM_LINK_SEGMENT));
   }
   const uint64_t longest = std::max(A.longest, B.longest);
   HmParams &P = J.P;
@@ -611,7 +661,7 @@ int hamming_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
     return CMPR_EINVAL;
   const std::string who = "cmpr_hamming_matrix";
   int rc;
-  if ((rc = hm_refusals(c, who, set1, set2, differences, true, on_device)))
+  if ((rc = hm_refusals(c, who, set1, set2, differences, HM_MATRIX, on_device)))
     return rc;
   if (!matrix_out)
     return fail(c, CMPR_EINVAL, who + ": matrix_out is NULL");
@@ -669,7 +719,7 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   if (capacity && !hit_out)
     return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
   int rc;
-  if ((rc = hm_refusals(c, who, set1, set2, differences, false, on_device)))
+  if ((rc = hm_refusals(c, who, set1, set2, differences, HM_NEIGHBORS, on_device)))
     return rc;
   auto t0 = std::chrono::steady_clock::now();
   c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
@@ -751,7 +801,119 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   return CMPR_OK;
 }
 
+/* cmpr_hamming_cluster* and cmpr_hamming_cluster_table*: the set against itself through the link sink, then the
+   flatten, size and table passes of cluster.hip.  The plain call fills label / size, the table call the other four. */
+struct HcOut {
+  uint32_t *label = nullptr, *size = nullptr;
+  uint32_t *cluster_of = nullptr, *member = nullptr;
+  uint64_t *cluster_start = nullptr, *count = nullptr;
+};
+
+int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differences, bool table, bool on_device,
+                         const HcOut &out, uint64_t *n_clusters_out)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  const std::string who = table ? "cmpr_hamming_cluster_table" : "cmpr_hamming_cluster";
+  if (n_clusters_out)
+    *n_clusters_out = 0;
+  int rc;
+  if ((rc = hm_refusals(c, who, set, set, differences, HM_CLUSTERS, on_device)))
+    return rc;
+  auto t0 = std::chrono::steady_clock::now();
+  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
+  if (table)
+    c->cl_ms[0] = c->cl_ms[1] = 0;
+  HmJob J;
+  if ((rc = hm_setup(c, who, set, set, differences, on_device, J, true)))
+    return rc;
+  c->hm_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+
+  /* the forest over the original sequence numbers; every unordered pair of every group linked; labels and sizes */
+  ClusterLinks L;
+  const uint64_t n = J.s1->n;
+  if (n) {
+    if ((rc = cmpr_cluster_forest(c, n, L))) return rc;
+    J.P.parent = L.parent.b.p;
+    J.P.snapshot = c->hamming_link_snapshot ? 1u : 0u;
+    if ((rc = hm_launch<SINK_LINK>(c, J)))
+      return rc;
+    const bool to_caller = on_device && !table;
+    if ((rc = cmpr_cluster_flatten(c, n, to_caller ? out.label : nullptr, to_caller ? out.size : nullptr,
+                                   table || out.size != nullptr, L)))
+      return rc;
+  }
+  if (table)
+    return cmpr_cluster_table_pass(c, L, c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p, on_device, out.cluster_of,
+                                   out.cluster_start, out.member, out.count, n_clusters_out, t0, &c->hm_ms[1]);
+  if (n && !on_device) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->hm_ms[1] = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = cmpr_cluster_results(c, L, false, out.label, out.size, n_clusters_out)))
+      return rc;
+    c->hm_ms[2] = ms_since(t0);
+    return CMPR_OK;
+  }
+  if ((rc = cmpr_cluster_results(c, L, on_device, out.label, out.size, n_clusters_out)))
+    return rc;
+  c->hm_ms[1] = ms_since(t0);
+  return CMPR_OK;
+}
+
 }  // namespace
+
+extern "C" int cmpr_hamming_cluster(cmpr_context *c, const cmpr_set_view *set, int64_t differences,
+                                    uint32_t *label_out, uint32_t *size_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    HcOut out;
+    out.label = label_out;
+    out.size = size_out;
+    return hamming_cluster_impl(c, set, differences, false, false, out, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_hamming_cluster_device(cmpr_context *c, const cmpr_set_view *d_set, int64_t differences,
+                                           uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    HcOut out;
+    out.label = d_label_out;
+    out.size = d_size_out;
+    return hamming_cluster_impl(c, d_set, differences, false, true, out, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_hamming_cluster_table(cmpr_context *c, const cmpr_set_view *set, int64_t differences,
+                                          uint32_t *cluster_of_out, uint64_t *cluster_start_out,
+                                          uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    HcOut out;
+    out.cluster_of = cluster_of_out;
+    out.cluster_start = cluster_start_out;
+    out.member = member_out;
+    out.count = count_out;
+    return hamming_cluster_impl(c, set, differences, true, false, out, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_hamming_cluster_table_device(cmpr_context *c, const cmpr_set_view *d_set, int64_t differences,
+                                                 uint32_t *d_cluster_of_out, uint64_t *d_cluster_start_out,
+                                                 uint32_t *d_member_out, uint64_t *d_count_out,
+                                                 uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    HcOut out;
+    out.cluster_of = d_cluster_of_out;
+    out.cluster_start = d_cluster_start_out;
+    out.member = d_member_out;
+    out.count = d_count_out;
+    return hamming_cluster_impl(c, d_set, differences, true, true, out, n_clusters_out);
+  });
+}
 
 extern "C" int cmpr_hamming_matrix(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2,
                                    int64_t differences, uint64_t *matrix_out)

@@ -424,7 +424,7 @@ struct ProbeParams {
   unsigned long long *pair_count;   /* NULL: matrix mode                        */
   uint64_t            pair_cap;
   /* link mode (cmpr_cluster): rides on pairs mode -- pair_count is then set but never touched --; matches
-     are neither listed nor counted, their two sequences are united in this forest (kernels.h link_pair) */
+     are neither listed nor counted, their two sequences are united in this forest (link_forest.h link_pair) */
   uint32_t           *link_parent;  /* NULL everywhere but in cmpr_cluster        */
   /* neighbour mode (cmpr_neighbors, neighbors.hip): rides on pairs mode as link mode does.  Count step:
      nb_hit is NULL and a match adds one to nb_degree[query].  Fill step: nb_degree[query] is the number of

@@ -35,6 +35,8 @@ EXPORTS = [
     "cmpr_neighbors_distance", "cmpr_neighbors_distance_device",
     "cmpr_hamming_matrix", "cmpr_hamming_matrix_device",
     "cmpr_hamming_neighbors", "cmpr_hamming_neighbors_device",
+    "cmpr_hamming_cluster", "cmpr_hamming_cluster_device",
+    "cmpr_hamming_cluster_table", "cmpr_hamming_cluster_table_device",
 ]
 
 
@@ -182,6 +184,13 @@ def load_library() -> C.CDLL:
                                                C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.POINTER(C.c_uint64)]
         lib.cmpr_hamming_neighbors_device.argtypes = lib.cmpr_hamming_neighbors.argtypes
+    if hasattr(lib, "cmpr_hamming_cluster"):       # (likewise: tools/hamming_cluster_timing.py --against)
+        lib.cmpr_hamming_cluster.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_uint64)]
+        lib.cmpr_hamming_cluster_device.argtypes = lib.cmpr_hamming_cluster.argtypes
+        lib.cmpr_hamming_cluster_table.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_int64, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.cmpr_hamming_cluster_table_device.argtypes = lib.cmpr_hamming_cluster_table.argtypes
     lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
     lib.cmpr_cols.argtypes = [C.c_void_p]
@@ -566,6 +575,56 @@ class HipOverlap:
             C.c_void_p(d_hits or None), C.c_void_p(d_distance or None), C.byref(n)))
         return n.value
 
+    # ---- single-linkage clusters at any d (include/compairr_hip.h: cmpr_hamming_cluster*) ----
+
+    def hamming_cluster(self, s: RepertoireSet, differences: int):
+        """(label uint32[n], size uint32[n], n_clusters) of `s` as cluster() gives them, under the pair relation of
+        hamming_neighbors(s, s, differences): any `differences` >= 0.  The context's own `differences` and
+        resident sets play no part, and `s` is not resident afterwards."""
+        v = _view(s)
+        label = np.zeros(s.n, dtype=np.uint32)
+        size = np.zeros(s.n, dtype=np.uint32)
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_hamming_cluster(self._ctx, C.byref(v), differences, label.ctypes.data,
+                                                   size.ctypes.data, C.byref(clusters)))
+        return label, size, clusters.value
+
+    def hamming_cluster_device(self, view: _SetView, differences: int, d_label: int = 0, d_size: int = 0) -> int:
+        """The same for a view of device pointers (device_view): labels and sizes are written to the device
+        arrays d_label and d_size (uint32[n] each; 0: not wanted); returns n_clusters."""
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_hamming_cluster_device(self._ctx, C.byref(view), differences,
+                                                          C.c_void_p(d_label or None), C.c_void_p(d_size or None),
+                                                          C.byref(clusters)))
+        return clusters.value
+
+    def hamming_cluster_table(self, s: RepertoireSet, differences: int):
+        """(cluster_of uint32[n], cluster_start uint64[K + 1], members uint32[n], count uint64[K]) of `s` as
+        cluster_table() gives them, under the pair relation of hamming_neighbors(s, s, differences)."""
+        v = _view(s)
+        cluster_of = np.zeros(s.n, dtype=np.uint32)
+        cluster_start = np.zeros(s.n + 1, dtype=np.uint64)
+        members = np.zeros(s.n, dtype=np.uint32)
+        count = np.zeros(s.n, dtype=np.uint64)
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_hamming_cluster_table(self._ctx, C.byref(v), differences, cluster_of.ctypes.data,
+                                                         cluster_start.ctypes.data, members.ctypes.data,
+                                                         count.ctypes.data, C.byref(clusters)))
+        k = clusters.value
+        return cluster_of, cluster_start[:k + 1].copy(), members, count[:k].copy()
+
+    def hamming_cluster_table_device(self, view: _SetView, differences: int, d_cluster_of: int = 0,
+                                     d_cluster_start: int = 0, d_member: int = 0, d_count: int = 0) -> int:
+        """The same for a view of device pointers (device_view), into device arrays: d_cluster_of and d_member
+        (uint32[n]), d_cluster_start (uint64[n + 1], K + 1 written) and d_count (uint64[n], K written); 0: not
+        wanted.  Returns K."""
+        clusters = C.c_uint64()
+        self._check(self._lib.cmpr_hamming_cluster_table_device(
+            self._ctx, C.byref(view), differences, C.c_void_p(d_cluster_of or None),
+            C.c_void_p(d_cluster_start or None), C.c_void_p(d_member or None), C.c_void_p(d_count or None),
+            C.byref(clusters)))
+        return clusters.value
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -669,6 +728,26 @@ def hamming_neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, di
         for name, value in (tunables or {}).items():
             h.set_tunable(name, value)
         return h.hamming_neighbors(set1, set2, differences, distances)
+
+
+def hamming_cluster(s: RepertoireSet, opt: Options, differences: int, tunables: Optional[dict] = None):
+    """Convenience: (label, size, n_clusters) of `s` at any `differences` (HipOverlap.hamming_cluster) on a context
+    of its own; `opt.differences` plays no part.  `tunables` are set on the context first (the result never depends
+    on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        return h.hamming_cluster(s, differences)
+
+
+def hamming_cluster_table(s: RepertoireSet, opt: Options, differences: int, tunables: Optional[dict] = None):
+    """Convenience: (cluster_of, cluster_start, members, count) of `s` at any `differences`
+    (HipOverlap.hamming_cluster_table) on a context of its own; `opt.differences` plays no part.  `tunables` are
+    set on the context first (the result never depends on them)."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        return h.hamming_cluster_table(s, differences)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

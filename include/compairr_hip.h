@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -611,6 +611,65 @@ int cmpr_hamming_neighbors_device(cmpr_context *ctx, const cmpr_set_view *d_set1
                                   uint32_t *d_hit_out, uint16_t *d_distance_out, uint64_t *n_edges_out);
 
 /*
+ * Single-linkage clusters for ANY d: above d = 2 (MAXDIFF_HASH) the reference's --cluster builds its network by the
+ * all-against-all sweep instead of hashed variants (process_trad, cluster.cc:165-211; the switch, cluster.cc:213-223)
+ * and sweeps it as before (cluster.cc:276-410).  cmpr_cluster*() get their links from the hashed step and stop at
+ * d = 2, where cmpr_create() stops; these calls take the distance as an ARGUMENT, as the rest of cmpr_hamming_*().
+ *
+ * Sequences i and j of `set` are linked when cmpr_hamming_neighbors(set, set, differences) lists (i, j): one length
+ * (two empty sequences included), the same V and J gene numbers unless options.ignore_genes, at most `differences`
+ * differing positions.  A cluster is a connected component of that graph.
+ *
+ * cmpr_hamming_cluster() (cluster.cc:165-211, :276-410) gives label_out[n], size_out[n] and *n_clusters_out, which
+ * mean, word for word, what they mean in cmpr_cluster(): the smallest sequence number of i's cluster, the number of
+ * its members, the number of i with label_out[i] == i.  cmpr_hamming_cluster_device() (cluster.cc:165-211) takes a
+ * DEVICE view and writes d_label_out / d_size_out, device memory of n uint32 each, where they lie.
+ *
+ * cmpr_hamming_cluster_table() (cluster.cc:165-211, :276-410, numbered as cluster.cc:53-63, :422) gives
+ * cluster_of_out[n], cluster_start_out (n + 1 provided, K + 1 written), member_out[n], count_out (n provided, K
+ * written) and *n_clusters_out = K, which mean, word for word, what they mean in cmpr_cluster_table(): the clusters
+ * numbered by (members descending, smallest member ascending) -- the reference's cluster_no - 1 --, the members of
+ * each as CSR in increasing order, the summed duplicate_count per cluster (the number of members with
+ * ignore_counts).  cmpr_hamming_cluster_table_device() (cluster.cc:165-211) takes a DEVICE view and writes the four
+ * arrays -- device memory on the context's device -- where they lie.
+ *
+ * All four: any output may be NULL; n_clusters_out is a HOST pointer in both variants; n == 0 is CMPR_OK with K = 0
+ * and nothing written but cluster_start[0] = 0.  As the rest of cmpr_hamming_*() and UNLIKE cmpr_cluster():
+ * `differences` is any value >= 0, also 0, 1 and 2 (a value above the longest sequence behaves as that length) and
+ * options.differences plays no part; callable any time after cmpr_create(); the resident sets, plans and statistics
+ * are not disturbed and `set` is NOT resident afterwards; synchronous; every temporary is freed on every return;
+ * results are bit-identical from run to run and under every tunable (a root of the forest is the smallest number of
+ * its tree whatever the schedule; stable sorts, integer sums).  Refused before any device work, with the codes and
+ * texts of cmpr_hamming_neighbors(): a negative `differences`, options.indels, a NULL set, the tunable
+ * work_shard_count above 1, n_v_genes x n_j_genes above 2^46; options.existence is CMPR_EINVAL ("clusters are not
+ * defined with options.existence", as cmpr_cluster()).  No score plays a part: MH / Jaccard with differences > 0 and
+ * the ratio score are NOT refused here.  The set is validated as every other set (same codes and texts, passed
+ * through unchanged).  At most 2^31-1 sequences.
+ *
+ * How (compairr_amd/csrc/hamming.hip, the link sink of the compare kernel): the set is grouped and packed once and
+ * every group is compared with itself; a lane walks only the references BEHIND its own query in the group -- each
+ * unordered pair once, the (i, i) pair never -- and a match unites the two sequences in a union-find forest over the
+ * original sequence numbers (link_forest.h) unless the snapshots of their roots, staged beside the references,
+ * already agree.  No pair list and no (query, segment) count array exist.  The flatten, size and table passes are
+ * those of cmpr_cluster*() (cluster.hip).  Device memory for the duration of the call: the set copy, group order and
+ * packed words of cmpr_hamming_*() above, 8 bytes per sequence of forest and labels (the forest's words take the sizes
+ * afterwards; either goes to the caller's device array where one is given), and for the table calls the terms of
+ * cmpr_cluster_table(): 4 bytes per sequence each for cluster_of and the members unless they go to the caller's
+ * device arrays, 8 and a few histograms for the radix sort's scratch, 16 per cluster, and in the host variant 8 each
+ * per cluster for cluster_start and the counts.
+ */
+int cmpr_hamming_cluster(cmpr_context *ctx, const cmpr_set_view *set, int64_t differences,
+                         uint32_t *label_out, uint32_t *size_out, uint64_t *n_clusters_out);
+int cmpr_hamming_cluster_device(cmpr_context *ctx, const cmpr_set_view *d_set, int64_t differences,
+                                uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out);
+int cmpr_hamming_cluster_table(cmpr_context *ctx, const cmpr_set_view *set, int64_t differences,
+                               uint32_t *cluster_of_out, uint64_t *cluster_start_out,
+                               uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out);
+int cmpr_hamming_cluster_table_device(cmpr_context *ctx, const cmpr_set_view *d_set, int64_t differences,
+                                      uint32_t *d_cluster_of_out, uint64_t *d_cluster_start_out,
+                                      uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out);
+
+/*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
  * runtime, the device's context, the code objects of the kernels the given options will run.
  * The reference has no counterpart -- its threads start in microseconds (overlap.cc:926-936);
@@ -738,6 +797,8 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
                              automatic, from the number of query workgroups)
      "hamming_generic"       TEST ONLY: 1 sends every group through the long-sequence form (query words read from
                              global memory), 0 (default) only groups of more than 16 words per sequence
+     "hamming_link_snapshot" TEST ONLY, cmpr_hamming_cluster*(): 1 (default) skips a match whose two staged root
+                             snapshots agree, 0 sends every match to the forest; the partition is the same
    What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
    the state):
      before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",
@@ -767,7 +828,9 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    numbering, the members, the counts and, in the host variant, their copies); and of the last cmpr_hamming_*(),
    host times, each part ending in a wait: "hamming_group_us" (upload, validation, keys, sort, groups, packing),
    "hamming_compare_us" (the compare kernel: once for a matrix, the count step, the sum and the fill step for
-   neighbours) and "hamming_copy_us" (host variant: the results copied out). */
+   neighbours; for cmpr_hamming_cluster*() the link kernel, the flatten and the sizes) and "hamming_copy_us" (host
+   variant: the results copied out).  cmpr_hamming_cluster_table*() set these three as well, zero
+   "cluster_links_us" and set "cluster_table_us" (the table pass, its copies included: "hamming_copy_us" stays 0). */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

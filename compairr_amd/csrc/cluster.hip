@@ -140,45 +140,37 @@ int cmpr_cluster_forest(cmpr_context *c, uint64_t n, ClusterLinks &L)
   return CMPR_OK;
 }
 
-int cmpr_cluster_flatten(cmpr_context *c, uint64_t n, uint32_t *d_label, uint32_t *d_size, bool want_size,
-                         ClusterLinks &L)
+int cmpr_cluster_flatten(cmpr_context *c, uint64_t n, bool want_size, ClusterLinks &L)
 {
   int rc;
-  uint32_t *label = d_label;
-  if (!label) {
-    if ((rc = dev_alloc(c, L.labels.b, (size_t)n))) return rc;
-    label = L.labels.b.p;
-  }
-  uint32_t *const parent = L.parent.b.p;
+  if ((rc = L.label.temp(c, (size_t)n))) return rc;
+  uint32_t *const parent = L.parent.b.p, *const label = L.label.p;
   const dim3 grid(blocks_for(n, CLUSTER_WG)), wg(CLUSTER_WG);
   HIP_TRY(c, hipMemsetAsync(L.roots.b.p, 0, sizeof(unsigned long long), c->stream));
   hipLaunchKernelGGL(cluster_flatten_kernel, grid, wg, 0, c->stream, parent, label, n, L.roots.b.p);
   HIP_TRY(c, hipGetLastError());
   if (want_size) {
     /* the counts go where the sizes will be (a device array of the caller) or where the forest was */
-    uint32_t *cnt = d_size ? d_size : parent;
+    L.size.lend(parent);
+    uint32_t *const cnt = L.size.p;
     HIP_TRY(c, hipMemsetAsync(cnt, 0, n * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(cluster_count_kernel, grid, wg, 0, c->stream, label, cnt, n);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(cluster_gather_kernel, grid, wg, 0, c->stream, label, cnt, cnt, n);
     HIP_TRY(c, hipGetLastError());
-    L.size = cnt;
   }
-  L.label = label;
   L.n = n;
   return CMPR_OK;
 }
 
-int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, bool on_device, uint32_t *label_out, uint32_t *size_out,
-                         uint64_t *n_clusters_out)
+int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, uint64_t *n_clusters_out)
 {
   const uint64_t n = L.n;
   if (n == 0)
     return CMPR_OK;
-  if (!on_device && size_out)
-    HIP_TRY(c, hipMemcpyAsync(size_out, L.size, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  if (!on_device && label_out)
-    HIP_TRY(c, hipMemcpyAsync(label_out, L.label, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  int rc;
+  if ((rc = L.size.copy_out(c, (size_t)n))) return rc;
+  if ((rc = L.label.copy_out(c, (size_t)n))) return rc;
   unsigned long long clusters = 0;
   HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -190,10 +182,10 @@ int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, bool on_device, uint3
 namespace {
 
 /* What cmpr_cluster and cmpr_cluster_table share: the refusals, the set as both sets, the link step, the
-   flat labels and (want_size) the sizes, all queued on the context's stream and NOT waited for.  d_label,
-   d_size: as cmpr_cluster_flatten takes them.  n == 0 leaves L.n == 0 and nothing queued. */
-int cluster_links(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *d_label, uint32_t *d_size,
-                  bool want_size, uint64_t *n_clusters_out, ClusterLinks &L)
+   flat labels and (want_size) the sizes, all queued on the context's stream and NOT waited for.  n == 0 leaves
+   L.n == 0 and nothing queued. */
+int cluster_links(cmpr_context *c, const cmpr_set_view *s, bool on_device, bool want_size, uint64_t *n_clusters_out,
+                  ClusterLinks &L)
 {
   if (!c)
     return CMPR_EINVAL;
@@ -220,18 +212,17 @@ int cluster_links(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint3
   if ((rc = cmpr_cluster_forest(c, n, L))) return rc;
   if ((rc = cmpr_link_step(c, L.parent.b.p)))
     return rc;
-  return cmpr_cluster_flatten(c, n, d_label, d_size, want_size, L);
+  return cmpr_cluster_flatten(c, n, want_size, L);
 }
 
 int cluster_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t *label_out,
                  uint32_t *size_out, uint64_t *n_clusters_out)
 {
-  ClusterLinks L;
+  ClusterLinks L(label_out, size_out, on_device);
   int rc;
-  if ((rc = cluster_links(c, s, on_device, on_device ? label_out : nullptr, on_device ? size_out : nullptr,
-                          size_out != nullptr, n_clusters_out, L)))
+  if ((rc = cluster_links(c, s, on_device, L.size.wanted(), n_clusters_out, L)))
     return rc;
-  return cmpr_cluster_results(c, L, on_device, label_out, size_out, n_clusters_out);
+  return cmpr_cluster_results(c, L, n_clusters_out);
 }
 
 /* ---- the table pass ---- */
@@ -320,32 +311,29 @@ int bit_length(uint64_t x)
 
 }  // namespace
 
-int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_cnt, bool on_device,
-                            uint32_t *cluster_of_out, uint64_t *cluster_start_out, uint32_t *member_out,
-                            uint64_t *count_out, uint64_t *n_clusters_out,
-                            std::chrono::steady_clock::time_point t0, double *flat_ms)
+int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_cnt, ClusterTableOut &T,
+                            uint64_t *n_clusters_out, std::chrono::steady_clock::time_point t0, double *flat_ms)
 {
   int rc;
   const uint64_t n = L.n;
   if (n == 0) {
-    if (cluster_start_out && on_device) {
+    if (T.cluster_start.wanted()) {
       HIP_TRY(c, hipSetDevice(c->device));
-      HIP_TRY(c, hipMemsetAsync(cluster_start_out, 0, sizeof(uint64_t), c->stream));
+      if ((rc = T.cluster_start.zero(c, 1))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (cluster_start_out) {
-      cluster_start_out[0] = 0;
     }
     return CMPR_OK;
   }
+  uint32_t *const label = L.label.p, *const size = L.size.p;
 
   /* ---- the two words the host needs: the number of roots, the largest size ---- */
   Tmp<uint32_t> largest_word;
   Tmp<char> scratch;
   size_t scratch_bytes = 0;
   if ((rc = dev_alloc(c, largest_word.b, 1))) return rc;
-  HIP_TRY(c, hipcub::DeviceReduce::Max(nullptr, scratch_bytes, (const uint32_t *)L.size, largest_word.b.p, n, c->stream));
+  HIP_TRY(c, hipcub::DeviceReduce::Max(nullptr, scratch_bytes, (const uint32_t *)size, largest_word.b.p, n, c->stream));
   if ((rc = dev_alloc(c, scratch.b, scratch_bytes))) return rc;
-  HIP_TRY(c, hipcub::DeviceReduce::Max(scratch.b.p, scratch_bytes, (const uint32_t *)L.size, largest_word.b.p, n, c->stream));
+  HIP_TRY(c, hipcub::DeviceReduce::Max(scratch.b.p, scratch_bytes, (const uint32_t *)size, largest_word.b.p, n, c->stream));
   unsigned long long clusters = 0;
   uint32_t largest = 0;
   HIP_TRY(c, hipMemcpyAsync(&clusters, L.roots.b.p, sizeof clusters, hipMemcpyDeviceToHost, c->stream));
@@ -360,41 +348,29 @@ int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_
     *n_clusters_out = K;
 
   /* what has to be made for what was asked for */
-  const bool sum_counts = count_out && !c->opt.ignore_counts;
-  const bool want_members = member_out || sum_counts;
-  const bool want_of = cluster_of_out || want_members;
-  if (!want_of && !cluster_start_out && !count_out)
+  const bool sum_counts = T.count.wanted() && !c->opt.ignore_counts;
+  const bool want_members = T.member.wanted() || sum_counts;
+  const bool want_of = T.cluster_of.wanted() || want_members;
+  if (!want_of && !T.cluster_start.wanted() && !T.count.wanted())
     return CMPR_OK;
   if (sum_counts && !d_cnt)
     return fail(c, CMPR_ESTATE, "cmpr_cluster_table: the resident set has no counts");
 
-  Tmp<uint32_t> root, key, root_sorted, key_sorted, of_tmp, member_tmp;
-  Tmp<uint64_t> start_tmp, count_tmp;
+  Tmp<uint32_t> root, key, root_sorted, key_sorted;
   Tmp<unsigned long long> selected;      /* DeviceSelect's count, never read: K is the flatten kernel's */
   if ((rc = dev_alloc(c, root.b, (size_t)K))) return rc;
   if ((rc = dev_alloc(c, key.b, (size_t)K))) return rc;
   if ((rc = dev_alloc(c, root_sorted.b, (size_t)K))) return rc;
   if ((rc = dev_alloc(c, key_sorted.b, (size_t)K))) return rc;
   if ((rc = dev_alloc(c, selected.b, 1))) return rc;
-  uint32_t *cluster_of = on_device ? cluster_of_out : nullptr, *member = on_device ? member_out : nullptr;
-  unsigned long long *cluster_start = on_device ? (unsigned long long *)cluster_start_out : nullptr;
-  unsigned long long *count = on_device ? (unsigned long long *)count_out : nullptr;
-  if (want_of && !cluster_of) {
-    if ((rc = dev_alloc(c, of_tmp.b, (size_t)n))) return rc;
-    cluster_of = of_tmp.b.p;
-  }
-  if (want_members && !member) {
-    if ((rc = dev_alloc(c, member_tmp.b, (size_t)n))) return rc;
-    member = member_tmp.b.p;
-  }
-  if (cluster_start_out && !cluster_start) {
-    if ((rc = dev_alloc(c, start_tmp.b, (size_t)(K + 1)))) return rc;
-    cluster_start = (unsigned long long *)start_tmp.b.p;
-  }
-  if (count_out && !count) {
-    if ((rc = dev_alloc(c, count_tmp.b, (size_t)K))) return rc;
-    count = (unsigned long long *)count_tmp.b.p;
-  }
+  /* (cluster_of and member are made for the arrays that need them, whether or not the caller asked) */
+  if (want_of && (rc = T.cluster_of.temp(c, (size_t)n))) return rc;
+  if (want_members && (rc = T.member.temp(c, (size_t)n))) return rc;
+  if (T.cluster_start.wanted() && (rc = T.cluster_start.temp(c, (size_t)(K + 1)))) return rc;
+  if (T.count.wanted() && (rc = T.count.temp(c, (size_t)K))) return rc;
+  uint32_t *const cluster_of = T.cluster_of.p, *const member = T.member.p;
+  unsigned long long *const cluster_start = (unsigned long long *)T.cluster_start.p;
+  unsigned long long *const count = (unsigned long long *)T.count.p;
 
   /* one scratch buffer for the four hipcub calls, which run one after the other */
   const int size_bits = std::max(1, bit_length(largest - 1)), number_bits = std::max(1, bit_length(K - 1));
@@ -403,7 +379,7 @@ int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_
       sorted_sizes(hipcub::CountingInputIterator<uint64_t>(0), SizeAt{key_sorted.b.p, K, largest});
   size_t select_bytes = 0, order_bytes = 0, scan_bytes = 0, member_bytes = 0;
   HIP_TRY(c, hipcub::DeviceSelect::If(nullptr, select_bytes, numbers, root.b.p, selected.b.p, (int64_t)n,
-                                      IsRoot{L.label}, c->stream));
+                                      IsRoot{label}, c->stream));
   HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, order_bytes, (const uint32_t *)key.b.p, key_sorted.b.p,
                                                 (const uint32_t *)root.b.p, root_sorted.b.p, (size_t)K, 0, size_bits,
                                                 c->stream));
@@ -411,17 +387,17 @@ int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, sorted_sizes, cluster_start, (size_t)(K + 1),
                                                 c->stream));
   if (want_members)
-    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, member_bytes, (const uint32_t *)cluster_of, L.size,
-                                                  (const uint32_t *)L.label, member, (size_t)n, 0, number_bits,
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, member_bytes, (const uint32_t *)cluster_of, size,
+                                                  (const uint32_t *)label, member, (size_t)n, 0, number_bits,
                                                   c->stream));
   scratch_bytes = std::max(std::max(select_bytes, order_bytes), std::max(scan_bytes, member_bytes));
   if ((rc = dev_alloc(c, scratch.b, scratch_bytes))) return rc;
 
   /* ---- roots and keys; the cluster order ---- */
   HIP_TRY(c, hipcub::DeviceSelect::If(scratch.b.p, select_bytes, numbers, root.b.p, selected.b.p, (int64_t)n,
-                                      IsRoot{L.label}, c->stream));
+                                      IsRoot{label}, c->stream));
   hipLaunchKernelGGL(table_key_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
-                     root.b.p, L.size, largest, key.b.p, K);
+                     root.b.p, size, largest, key.b.p, K);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, order_bytes, (const uint32_t *)key.b.p, key_sorted.b.p,
                                                 (const uint32_t *)root.b.p, root_sorted.b.p, (size_t)K, 0, size_bits,
@@ -432,26 +408,26 @@ int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(scratch.b.p, scan_bytes, sorted_sizes, cluster_start, (size_t)(K + 1),
                                                 c->stream));
   if (want_of) {
-    uint32_t *const number = L.size;             /* (the keys have read the sizes: their words are free) */
+    uint32_t *const number = size;               /* (the keys have read the sizes: their words are free) */
     hipLaunchKernelGGL(table_number_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
                        root_sorted.b.p, number, K);
     HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(table_of_kernel, dim3(blocks_for(n, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
-                       L.label, number, cluster_of, n);
+                       label, number, cluster_of, n);
     HIP_TRY(c, hipGetLastError());
   }
 
   /* ---- members: (cluster_of -> i), stable; the sorted keys (the cluster at every place) take the numbers' words ---- */
   if (want_members)
-    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, member_bytes, (const uint32_t *)cluster_of, L.size,
-                                                  (const uint32_t *)L.label, member, (size_t)n, 0, number_bits,
+    HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(scratch.b.p, member_bytes, (const uint32_t *)cluster_of, size,
+                                                  (const uint32_t *)label, member, (size_t)n, 0, number_bits,
                                                   c->stream));
 
   /* ---- counts ---- */
   if (sum_counts) {
     HIP_TRY(c, hipMemsetAsync(count, 0, (size_t)K * sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(table_count_kernel, dim3(blocks_for(n, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
-                       L.size, member, d_cnt, count, n);
+                       size, member, d_cnt, count, n);
     HIP_TRY(c, hipGetLastError());
   } else if (count) {
     hipLaunchKernelGGL(table_sizes_kernel, dim3(blocks_for(K, CLUSTER_WG)), dim3(CLUSTER_WG), 0, c->stream,
@@ -459,17 +435,10 @@ int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_
     HIP_TRY(c, hipGetLastError());
   }
 
-  if (!on_device) {
-    if (cluster_of_out)
-      HIP_TRY(c, hipMemcpyAsync(cluster_of_out, cluster_of, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (cluster_start_out)
-      HIP_TRY(c, hipMemcpyAsync(cluster_start_out, cluster_start, (size_t)(K + 1) * sizeof(uint64_t),
-                                hipMemcpyDeviceToHost, c->stream));
-    if (member_out)
-      HIP_TRY(c, hipMemcpyAsync(member_out, member, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (count_out)
-      HIP_TRY(c, hipMemcpyAsync(count_out, count, (size_t)K * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = T.cluster_of.copy_out(c, (size_t)n))) return rc;
+  if ((rc = T.cluster_start.copy_out(c, (size_t)(K + 1)))) return rc;
+  if ((rc = T.member.copy_out(c, (size_t)n))) return rc;
+  if ((rc = T.count.copy_out(c, (size_t)K))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->cl_ms[1] = ms_since(t0);
   return CMPR_OK;
@@ -483,13 +452,13 @@ int table_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, uint32_t
   const auto t0 = std::chrono::steady_clock::now();
   if (c)
     c->cl_ms[0] = c->cl_ms[1] = 0;
-  ClusterLinks L;
+  ClusterLinks L(nullptr, nullptr, on_device);
+  ClusterTableOut T(cluster_of_out, cluster_start_out, member_out, count_out, on_device);
   int rc;
-  if ((rc = cluster_links(c, s, on_device, nullptr, nullptr, true, n_clusters_out, L)))
+  if ((rc = cluster_links(c, s, on_device, true, n_clusters_out, L)))
     return rc;
   /* the set is resident: its counts are the reference's (context.h cnt2) */
-  return cmpr_cluster_table_pass(c, L, c->cnt2.p, on_device, cluster_of_out, cluster_start_out, member_out, count_out,
-                                 n_clusters_out, t0, &c->cl_ms[0]);
+  return cmpr_cluster_table_pass(c, L, c->cnt2.p, T, n_clusters_out, t0, &c->cl_ms[0]);
 }
 
 }  // namespace

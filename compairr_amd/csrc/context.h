@@ -12,6 +12,7 @@
 
 #include "select.h"
 
+#include <algorithm>
 #include <chrono>
 #include <functional>
 #include <map>
@@ -524,11 +525,92 @@ int cmpr_route_pack_impl(cmpr_context *c, void *d_send, uint64_t capacity_bytes)
 
 /* query_layout.hip: the caller's arrays into the given device buffers, validated
    there (what a host pass over the set would check); longest sequence and count
-   total per repertoire */
+   total per repertoire.  on_device: the view holds device pointers -- offsets[0] and
+   offsets[n] are fetched and checked before anything is allocated or copied, the rest
+   is a copy inside the device.  *residues (or NULL) = offsets[n], the residues in all. */
 int cmpr_upload_and_validate(cmpr_context *c, const cmpr_set_view *s, DevBuf<uint8_t> &res,
                              DevBuf<uint64_t> &off, DevBuf<uint32_t> &v, DevBuf<uint32_t> &j,
                              DevBuf<uint32_t> &rep, DevBuf<uint64_t> &cnt, uint32_t &longest,
-                             std::vector<double> &rep_total, bool on_device = false, uint64_t total_dev = 0);
+                             std::vector<double> &rep_total, bool on_device = false,
+                             uint64_t *residues = nullptr);
+
+/* A set staged for one call: the caller's arrays on the device, validated, in temporaries of the call
+   (cmpr_deduplicate*, cmpr_count_duplicates, cmpr_hamming_*; the resident reference keeps its own res2 .. cnt2) */
+struct StagedSet {
+  Tmp<uint8_t>  res;
+  Tmp<uint64_t> off, cnt;
+  Tmp<uint32_t> v, j, rep;
+  uint64_t      n = 0;
+  uint32_t      R = 0, longest = 0;
+  std::vector<double> totals;      /* count total per repertoire */
+};
+
+/* the view checked (validate_view), the context's device made current, the set uploaded and validated into S */
+inline int cmpr_stage_set(cmpr_context *c, const cmpr_set_view *s, bool on_device, StagedSet &S)
+{
+  std::string why;
+  int rc;
+  if ((rc = validate_view(c->opt, s, why, on_device)))
+    return fail(c, rc, why);
+  HIP_TRY(c, hipSetDevice(c->device));
+  if ((rc = cmpr_upload_and_validate(c, s, S.res.b, S.off.b, S.v.b, S.j.b, S.rep.b, S.cnt.b, S.longest, S.totals,
+                                     on_device)))
+    return rc;
+  S.n = s->n;
+  S.R = s->n_repertoires;
+  return CMPR_OK;
+}
+
+/* An output array of one call.  The host variant of an entry point takes host arrays, its _device twin device
+   arrays, and any of them may be NULL: this is the only place that tells the two apart.  `p` is what the kernels
+   write -- the caller's device array, or after temp() a temporary of the call; copy_out() brings a temporary's
+   contents to the caller's host array.  Everything is queued on the context's stream; nothing here waits. */
+template <typename T>
+struct Out {
+  T *p;
+  Out(T *caller, bool on_device)
+      : p(on_device ? caller : nullptr), host(on_device ? nullptr : caller), asked(caller != nullptr) {}
+  Out(const Out &) = delete;
+  Out &operator=(const Out &) = delete;
+  /* the caller asked for the array */
+  bool wanted() const { return asked; }
+  /* no device array of the caller's: a temporary of `count` elements for the kernels */
+  int temp(cmpr_context *c, size_t count)
+  {
+    if (p)
+      return CMPR_OK;
+    int rc = dev_alloc(c, tmp.b, count);
+    p = tmp.b.p;
+    return rc;
+  }
+  /* ... or `d`, device memory of the call's that outlives the copy-out */
+  void lend(T *d)
+  {
+    if (!p)
+      p = d;
+  }
+  /* `count` elements to the caller's host array, when there is one */
+  int copy_out(cmpr_context *c, size_t count)
+  {
+    if (host)
+      HIP_TRY(c, hipMemcpyAsync(host, p, count * sizeof(T), hipMemcpyDeviceToHost, c->stream));
+    return CMPR_OK;
+  }
+  /* `count` zeros in the caller's array: queued for a device array, written at once to a host array */
+  int zero(cmpr_context *c, size_t count)
+  {
+    if (host)
+      std::fill(host, host + count, T(0));
+    else if (asked)
+      HIP_TRY(c, hipMemsetAsync(p, 0, count * sizeof(T), c->stream));
+    return CMPR_OK;
+  }
+
+private:
+  T     *host;
+  bool   asked;
+  Tmp<T> tmp;
+};
 
 /* compairr_hip.hip: the synchronous step in link mode (cmpr_cluster, cluster.hip) -- every matching pair of the
    resident sets united in `parent` (one word per sequence, parent[i] == i or a forest that earlier steps
@@ -539,30 +621,37 @@ int cmpr_link_step(cmpr_context *c, uint32_t *parent);
    around their link steps -- the forest, the flat labels and sizes, the results of the plain call, the table pass.
    Everything is queued on the context's stream; only the last two wait. */
 struct ClusterLinks {
-  Tmp<uint32_t> parent, labels;
+  Tmp<uint32_t> parent;
   Tmp<unsigned long long> roots;
-  uint32_t *label = nullptr, *size = nullptr;
+  Out<uint32_t> label, size;       /* of cmpr_cluster*: the caller's arrays; of the table calls: nobody's (NULL, NULL) */
   uint64_t n = 0;
+  ClusterLinks(uint32_t *label_out, uint32_t *size_out, bool on_device)
+      : label(label_out, on_device), size(size_out, on_device) {}
+};
+/* the four arrays of cmpr_cluster_table* / cmpr_hamming_cluster_table* */
+struct ClusterTableOut {
+  Out<uint32_t> cluster_of, member;
+  Out<uint64_t> cluster_start, count;
+  ClusterTableOut(uint32_t *cluster_of_out, uint64_t *cluster_start_out, uint32_t *member_out, uint64_t *count_out,
+                  bool on_device)
+      : cluster_of(cluster_of_out, on_device), member(member_out, on_device), cluster_start(cluster_start_out, on_device),
+        count(count_out, on_device) {}
 };
 /* the forest of n sequences and the root counter allocated, parent[i] = i queued (n > 0) */
 int cmpr_cluster_forest(cmpr_context *c, uint64_t n, ClusterLinks &L);
-/* behind the links: label[i] = the root of i, the roots counted and (want_size) size[i] = the members of i's
-   tree.  d_label, d_size: device arrays of the caller's to take them, or NULL -- the labels then go to an array
-   of L's, the sizes to where the forest was.  Sets L.label, L.size and L.n. */
-int cmpr_cluster_flatten(cmpr_context *c, uint64_t n, uint32_t *d_label, uint32_t *d_size, bool want_size,
-                         ClusterLinks &L);
+/* behind the links: L.label.p[i] = the root of i, the roots counted and (want_size) L.size.p[i] = the members of i's
+   tree.  Labels that are no device array of the caller's go to a temporary, such sizes to where the forest was.
+   Sets L.n. */
+int cmpr_cluster_flatten(cmpr_context *c, uint64_t n, bool want_size, ClusterLinks &L);
 /* the end of cmpr_cluster / cmpr_hamming_cluster: labels and sizes to the host (host variant), the cluster
    count; waits */
-int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, bool on_device, uint32_t *label_out, uint32_t *size_out,
-                         uint64_t *n_clusters_out);
+int cmpr_cluster_results(cmpr_context *c, ClusterLinks &L, uint64_t *n_clusters_out);
 /* the table pass of cmpr_cluster_table / cmpr_hamming_cluster_table over flat labels and sizes (L.n == 0: only
    cluster_start[0] = 0).  d_cnt: the duplicate_count of every sequence on the device (not looked at with
    ignore_counts).  *flat_ms = the host time since t0 at the wait after which labels and sizes are flat;
    cl_ms[1] = the time from there. */
-int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_cnt, bool on_device,
-                            uint32_t *cluster_of_out, uint64_t *cluster_start_out, uint32_t *member_out,
-                            uint64_t *count_out, uint64_t *n_clusters_out,
-                            std::chrono::steady_clock::time_point t0, double *flat_ms);
+int cmpr_cluster_table_pass(cmpr_context *c, ClusterLinks &L, const uint64_t *d_cnt, ClusterTableOut &T,
+                            uint64_t *n_clusters_out, std::chrono::steady_clock::time_point t0, double *flat_ms);
 
 /* compairr_hip.hip: the synchronous step in neighbour mode (cmpr_neighbors, neighbors.hip).  hit == NULL: the
    count step, every match adds one to degree[its query]; otherwise the fill step, every match takes a place of
@@ -578,22 +667,19 @@ int cmpr_neighbor_step(cmpr_context *c, uint32_t *degree, const uint64_t *row_st
    `hit` stays empty.  Everything is released with the struct. */
 struct NeighborEdges {
   DevBuf<uint32_t> degree;             /* n1 + 1 words; all zero once the fill step has run */
-  DevBuf<uint64_t> row_start;          /* n1 + 1 (cmpr_neighbors: only when the caller's array is not on the device) */
-  DevBuf<uint32_t> hit;                /* `total` (cmpr_neighbors: likewise) */
+  Out<uint64_t>    row_start;          /* n1 + 1: cmpr_neighbors' array, or nobody's (a temporary) */
+  Out<uint32_t>    hit;                /* `total`: likewise */
   DevBuf<unsigned long long> census;   /* [0] rows of more than 64 hits, [1] of those the rows of more than 8192,
                                           [2] the longest of the latter; [3..4] two list counters, zero */
   DevBuf<char>     scan_tmp;
   size_t           scan_bytes = 0;
   bool             pretend_no_redo = false;
   uint64_t         total = 0, n_big = 0, n_long = 0, longest = 0;   /* rows of 65 .. 8192 | longer | the longest such */
-  NeighborEdges() = default;
-  NeighborEdges(const NeighborEdges &) = delete;
-  NeighborEdges &operator=(const NeighborEdges &) = delete;
+  explicit NeighborEdges(uint64_t *row_start_out = nullptr, uint32_t *hit_out = nullptr, bool on_device = false)
+      : row_start(row_start_out, on_device), hit(hit_out, on_device) {}
   ~NeighborEdges()
   {
     degree.release();
-    row_start.release();
-    hit.release();
     census.release();
     scan_tmp.release();
   }

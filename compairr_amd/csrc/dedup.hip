@@ -316,38 +316,21 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
 {
   if (!c)
     return CMPR_EINVAL;
-  std::string why;
-  int rc;
-  if ((rc = validate_view(c->opt, s, why, on_device)))
-    return fail(c, rc, why);
   if (capacity && (!first_out || !count_out))
     return fail(c, CMPR_EINVAL, "cmpr_deduplicate: output arrays are NULL with a capacity");
-  HIP_TRY(c, hipSetDevice(c->device));
   if (n_unique_out) *n_unique_out = 0;
   if (merged_out) *merged_out = 0;
 
-  Tmp<uint8_t> res;
-  Tmp<uint64_t> off, cnt, zob_own, d_count;
-  Tmp<uint32_t> v, j, rep, slot, blk, d_first;
-  Tmp<unsigned long long> table, sum, total;
-
-  /* residues in all: offsets[n], which a device view keeps on the device (ref_index.hip) */
-  uint64_t residues = 0;
-  if (s->n && on_device) {
-    uint64_t ends[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(&ends[0], s->offsets, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(&ends[1], s->offsets + s->n, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (ends[0] != 0)
-      return fail(c, CMPR_EINVAL, "offsets[0] must be 0");
-    if (ends[1] > 0xffffull * s->n)
-      return fail(c, CMPR_EINVAL, "offsets not monotone");
-    residues = ends[1];
-  }
   /* upload (a device view: a copy inside the device) + validation on the device (query_layout.hip) */
-  uint32_t longest = 0;
-  std::vector<double> tot;
-  if ((rc = cmpr_upload_and_validate(c, s, res.b, off.b, v.b, j.b, rep.b, cnt.b, longest, tot, on_device, residues)))
+  StagedSet set;
+  int rc;
+  if ((rc = cmpr_stage_set(c, s, on_device, set)))
     return rc;
+  Out<uint32_t> first(first_out, on_device);
+  Out<uint64_t> count(count_out, on_device);
+  Tmp<uint64_t> zob_own;
+  Tmp<uint32_t> slot, blk;
+  Tmp<unsigned long long> table, sum, total;
   const uint64_t n = s->n;
   if (n == 0)
     return CMPR_OK;
@@ -356,8 +339,8 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   P.S.A = (uint32_t)c->opt.alphabet_size;
   P.S.n_v = c->opt.ignore_genes ? 0 : c->opt.n_v_genes;
   P.S.use_genes = c->opt.ignore_genes ? 0u : 1u;
-  if ((rc = keys_for_set(c, longest, zob_own.b, P.S.zob, P.S.zpos))) return rc;
-  P.S.res = res.b.p; P.S.off = off.b.p; P.S.v = v.b.p; P.S.j = j.b.p; P.S.rep = rep.b.p;
+  if ((rc = keys_for_set(c, set.longest, zob_own.b, P.S.zob, P.S.zpos))) return rc;
+  P.S.res = set.res.b.p; P.S.off = set.off.b.p; P.S.v = set.v.b.p; P.S.j = set.j.b.p; P.S.rep = set.rep.b.p;
 
   /* one table under the 70 % rule of hashtable.cc:24; slot numbers are 32 bits, so beyond 0.7 x 2^32
      sequences it is fuller than that (never full: there are fewer classes than 2^32 - 64) */
@@ -376,7 +359,7 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   P.zob_words = (uint32_t)((size_t)P.S.A * P.S.zpos + P.S.n_v + (c->opt.ignore_genes ? 0 : c->opt.n_j_genes));
   P.zob_lds = (size_t)P.zob_words * sizeof(uint64_t) <= DEDUP_ZOB_LDS_BYTES ? 1u : 0u;
   P.tag_drop = 32u - (uint32_t)c->dedup_tag_bits;
-  P.cnt = c->opt.ignore_counts ? nullptr : cnt.b.p;
+  P.cnt = c->opt.ignore_counts ? nullptr : set.cnt.b.p;
   P.n = n;
   P.table = table.b.p; P.slot_mask = slots - 1;
   P.slot = slot.b.p; P.sum = sum.b.p; P.blk = blk.b.p; P.total = total.b.p;
@@ -397,21 +380,14 @@ int deduplicate_impl(cmpr_context *c, const cmpr_set_view *s, bool on_device, ui
   const uint64_t written = std::min<uint64_t>(capacity, classes);
   if (written) {
     P.capacity = written;
-    if (on_device) {
-      P.first_out = first_out;
-      P.count_out = count_out;
-    } else {
-      if ((rc = dev_alloc(c, d_first.b, (size_t)written))) return rc;
-      if ((rc = dev_alloc(c, d_count.b, (size_t)written))) return rc;
-      P.first_out = d_first.b.p;
-      P.count_out = d_count.b.p;
-    }
+    if ((rc = first.temp(c, (size_t)written))) return rc;
+    if ((rc = count.temp(c, (size_t)written))) return rc;
+    P.first_out = first.p;
+    P.count_out = count.p;
     hipLaunchKernelGGL(dedup_scatter_kernel, dim3((uint32_t)nblk), dim3(DEDUP_WG), 0, c->stream, P);
     HIP_TRY(c, hipGetLastError());
-    if (!on_device) {
-      HIP_TRY(c, hipMemcpyAsync(first_out, d_first.b.p, written * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      HIP_TRY(c, hipMemcpyAsync(count_out, d_count.b.p, written * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    }
+    if ((rc = first.copy_out(c, (size_t)written))) return rc;
+    if ((rc = count.copy_out(c, (size_t)written))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (n_unique_out) *n_unique_out = classes;
@@ -426,9 +402,8 @@ int count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, uint64_t *out
   HIP_TRY(c, hipSetDevice(c->device));
   *out = 0;
   int rc;
-  Tmp<uint8_t> res;
-  Tmp<uint64_t> off, cnt, zob_own;
-  Tmp<uint32_t> v, j, rep;
+  StagedSet set;
+  Tmp<uint64_t> zob_own;
   Tmp<unsigned long long> count;
   Tmp<DupTable> more;
   std::vector<Tmp<Slot>> slots;                /* a passed-in set: the table of each part */
@@ -452,16 +427,11 @@ int count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, uint64_t *out
     }
     first.push_back(c->n2);
   } else {
-    std::string why;
-    if ((rc = validate_view(c->opt, s, why)))
-      return fail(c, rc, why);
-    /* upload + validation on the device (query_layout.hip) */
-    uint32_t longest = 0;
-    std::vector<double> tot;
-    if ((rc = cmpr_upload_and_validate(c, s, res.b, off.b, v.b, j.b, rep.b, cnt.b, longest, tot)))
+    /* the view as host memory; upload + validation on the device (query_layout.hip) */
+    if ((rc = cmpr_stage_set(c, s, false, set)))
       return rc;
-    if ((rc = keys_for_set(c, longest, zob_own.b, B.S.zob, B.S.zpos))) return rc;
-    B.S.res = res.b.p; B.S.off = off.b.p; B.S.v = v.b.p; B.S.j = j.b.p; B.S.rep = rep.b.p;
+    if ((rc = keys_for_set(c, set.longest, zob_own.b, B.S.zob, B.S.zpos))) return rc;
+    B.S.res = set.res.b.p; B.S.off = set.off.b.p; B.S.v = set.v.b.p; B.S.j = set.j.b.p; B.S.rep = set.rep.b.p;
     /* a set larger than one table of at most 2^part_buckets_log2 slots: a table per contiguous part */
     const uint64_t per_part = (uint64_t)FILL_PERCENT * (1ull << c->part_buckets_log2) / 100;
     const uint64_t nparts = s->n > per_part ? (s->n + per_part - 1) / per_part : 1;
@@ -481,7 +451,7 @@ int count_duplicates_impl(cmpr_context *c, const cmpr_set_view *s, uint64_t *out
       HIP_TRY(c, hipMemsetAsync(table, 0xff, ps * sizeof(Slot), c->stream));
       BuildParams K{};
       K.zob = B.S.zob; K.A = B.S.A; K.zpos = B.S.zpos; K.n_v = B.S.n_v; K.use_genes = B.S.use_genes;
-      K.res = res.b.p; K.off = off.b.p + f; K.v = v.b.p ? v.b.p + f : nullptr; K.j = j.b.p ? j.b.p + f : nullptr;
+      K.res = B.S.res; K.off = B.S.off + f; K.v = B.S.v ? B.S.v + f : nullptr; K.j = B.S.j ? B.S.j + f : nullptr;
       K.n = n;
       K.table = table; K.slot_mask = ps - 1;       /* table only: no filter */
       if (n) {

@@ -289,6 +289,9 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   const uint64_t n1 = c->n1;
   for (double &t : c->ex_ms)
     t = 0;
+  Out<uint64_t> rows(row_start_out, on_device);
+  Out<uint32_t> reps(rep_out, on_device);
+  Out<uint64_t> vals(value_out, on_device);
 
   /* ---- edges ---- */
   auto t0 = std::chrono::steady_clock::now();
@@ -299,12 +302,9 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   const uint64_t total = e.total, n_big = e.n_big, n_long = e.n_long, longest = e.longest;
   if (total == 0) {
     /* no match at all: every row is empty */
-    if (row_start_out && on_device) {
-      HIP_TRY(c, hipMemsetAsync(row_start_out, 0, (size_t)(n1 + 1) * sizeof(uint64_t), c->stream));
+    if (rows.wanted()) {
+      if ((rc = rows.zero(c, (size_t)(n1 + 1)))) return rc;
       HIP_TRY(c, hipStreamSynchronize(c->stream));
-    } else if (row_start_out) {
-      for (uint64_t i = 0; i <= n1; i++)
-        row_start_out[i] = 0;
     }
     return CMPR_OK;
   }
@@ -315,16 +315,12 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
 
   /* ---- group ---- */
   t0 = std::chrono::steady_clock::now();
-  Tmp<uint64_t> rows;
   Tmp<uint32_t> big_rows, key_a, key_b, hit_b, runs;
   Tmp<unsigned long long> long_desc;
   Tmp<char> sort_tmp, reduce_tmp;
   size_t sort_bytes = 0;
-  uint64_t *cstart = on_device ? row_start_out : nullptr;
-  if (!cstart) {
-    if ((rc = dev_alloc(c, rows.b, (size_t)(n1 + 1)))) return rc;
-    cstart = rows.b.p;
-  }
+  if ((rc = rows.temp(c, (size_t)(n1 + 1)))) return rc;
+  uint64_t *const cstart = rows.p;
   int rep_bits = 1;
   while (rep_bits < 32 && (c->R2 - 1u) >> rep_bits)
     rep_bits++;
@@ -374,9 +370,7 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   std::vector<uint64_t> cell0(lr.size());              /* where the cells of the rows beyond LDS go */
   for (size_t k = 0; k < lr.size(); k++)
     HIP_TRY(c, hipMemcpyAsync(&cell0[k], cstart + lr[k].row, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-  if (!on_device && row_start_out)
-    HIP_TRY(c, hipMemcpyAsync(row_start_out, cstart, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                              c->stream));
+  if ((rc = rows.copy_out(c, (size_t)(n1 + 1)))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->ex_ms[2] = ms_since(t0);
   *n_cells_out = cells;
@@ -385,16 +379,11 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
 
   /* ---- reduce ---- */
   t0 = std::chrono::steady_clock::now();
-  Tmp<uint64_t> cnt1, vals;
-  Tmp<uint32_t> reps;
-  uint32_t *d_rep = on_device ? rep_out : nullptr;
-  unsigned long long *d_val = on_device ? (unsigned long long *)value_out : nullptr;
-  if (!on_device) {
-    if ((rc = dev_alloc(c, reps.b, (size_t)cells))) return rc;
-    if ((rc = dev_alloc(c, vals.b, (size_t)cells))) return rc;
-    d_rep = reps.b.p;
-    d_val = (unsigned long long *)vals.b.p;
-  }
+  Tmp<uint64_t> cnt1;
+  if ((rc = reps.temp(c, (size_t)cells))) return rc;
+  if ((rc = vals.temp(c, (size_t)cells))) return rc;
+  uint32_t *const d_rep = reps.p;
+  unsigned long long *const d_val = (unsigned long long *)vals.p;
   ExScore S{nullptr, nullptr, c->opt.score, c->opt.ignore_counts ? 1 : 0};
   if (!S.ignore_counts) {
     if (!c->cnt2.p)
@@ -443,8 +432,8 @@ int existence_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   /* ---- copy-out ---- */
   if (!on_device && cells) {
     t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipMemcpyAsync(rep_out, d_rep, (size_t)cells * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(value_out, d_val, (size_t)cells * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = reps.copy_out(c, (size_t)cells))) return rc;
+    if ((rc = vals.copy_out(c, (size_t)cells))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->ex_ms[4] = ms_since(t0);
   }

@@ -422,36 +422,16 @@ hm_rows_kernel(const unsigned long long *offs, uint64_t n1, uint32_t segments, u
 }
 
 /* a set on the device, validated, grouped and packed */
-struct HmSet {
-  Tmp<uint8_t>  res;
-  Tmp<uint64_t> off, cnt;
-  Tmp<uint32_t> v, j, rep, ord, pk;
-  uint64_t      n = 0;
-  uint32_t      longest = 0, R = 0;
+struct HmSet : StagedSet {
+  Tmp<uint32_t> ord, pk;
   std::vector<uint64_t> keys;      /* of the groups, increasing */
   std::vector<HmGroup>  groups;
 };
 
-int hm_prepare(cmpr_context *c, const cmpr_set_view *s, bool on_device, HmSet &H)
+/* the staged set H grouped and packed */
+int hm_prepare(cmpr_context *c, HmSet &H)
 {
   int rc;
-  uint64_t residues = 0;
-  if (s->n && on_device) {       /* (as cmpr_deduplicate_device: offsets[0] and offsets[n] are all the host sees) */
-    uint64_t ends[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(&ends[0], s->offsets, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(&ends[1], s->offsets + s->n, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (ends[0] != 0)
-      return fail(c, CMPR_EINVAL, "offsets[0] must be 0");
-    if (ends[1] > 0xffffull * s->n)
-      return fail(c, CMPR_EINVAL, "offsets not monotone");
-    residues = ends[1];
-  }
-  std::vector<double> tot;
-  if ((rc = cmpr_upload_and_validate(c, s, H.res.b, H.off.b, H.v.b, H.j.b, H.rep.b, H.cnt.b, H.longest, tot, on_device,
-                                     residues)))
-    return rc;
-  H.n = s->n;
-  H.R = s->n_repertoires;
   if (H.n == 0)
     return CMPR_OK;
   if (H.n > 0x7fffffffull)
@@ -571,13 +551,13 @@ int hm_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
              int64_t differences, bool on_device, HmJob &J, bool triangular = false)
 {
   int rc;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = hm_prepare(c, set1, on_device, J.own1))) return rc;
+  /* (hm_refusals has refused a bad view of either set before the first is staged: the look at it there changes nothing) */
+  if ((rc = cmpr_stage_set(c, set1, on_device, J.own1)) || (rc = hm_prepare(c, J.own1))) return rc;
   J.s1 = &J.own1;
   if (set2 == set1) {
     J.s2 = J.s1;
   } else {
-    if ((rc = hm_prepare(c, set2, on_device, J.own2))) return rc;
+    if ((rc = cmpr_stage_set(c, set2, on_device, J.own2)) || (rc = hm_prepare(c, J.own2))) return rc;
     J.s2 = &J.own2;
   }
   HmSet &A = *J.s1, &B = *J.s2;
@@ -676,13 +656,9 @@ int hamming_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
   const uint64_t rows = c->opt.existence ? J.s1->n : J.s1->R, cells = rows * J.s2->R;
   if (cells == 0)
     return CMPR_OK;
-  Tmp<unsigned long long> own;
-  unsigned long long *matrix = (unsigned long long *)matrix_out;
-  if (!on_device) {
-    if ((rc = dev_alloc(c, own.b, (size_t)cells))) return rc;
-    matrix = own.b.p;
-  }
-  HIP_TRY(c, hipMemsetAsync(matrix, 0, cells * sizeof(unsigned long long), c->stream));
+  Out<unsigned long long> matrix((unsigned long long *)matrix_out, on_device);
+  if ((rc = matrix.temp(c, (size_t)cells))) return rc;
+  HIP_TRY(c, hipMemsetAsync(matrix.p, 0, cells * sizeof(unsigned long long), c->stream));
   HmParams &P = J.P;
   P.rep1 = J.s1->rep.b.p; P.rep2 = J.s2->rep.b.p;
   P.cnt1 = c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p;
@@ -691,7 +667,7 @@ int hamming_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
   P.score = (uint32_t)c->opt.score;
   P.existence = c->opt.existence ? 1u : 0u;
   P.mat_lds = !c->opt.existence && cells <= HM_MAT_CELLS ? 1u : 0u;
-  P.matrix = matrix;
+  P.matrix = matrix.p;
   P.cells = (uint32_t)std::min<uint64_t>(cells, HM_MAT_CELLS);
   if ((rc = hm_launch<SINK_MATRIX>(c, J)))
     return rc;
@@ -699,7 +675,7 @@ int hamming_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
   c->hm_ms[1] = ms_since(t0);
   if (!on_device) {
     t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipMemcpyAsync(matrix_out, matrix, cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = matrix.copy_out(c, (size_t)cells))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->hm_ms[2] = ms_since(t0);
   }
@@ -733,10 +709,11 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   const uint64_t n1 = J.s1->n, S = J.P.segments, slots = n1 * S + 1;   /* (a zero behind the last: the sum's last is the total) */
   if (slots > 0x7fffffffull)
     return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^31-1 (query, segment) counts");
-  Tmp<uint32_t> cnt, d_hit;
+  Out<uint64_t> rows(row_start_out, on_device);
+  Out<uint32_t> hit(hit_out, on_device);
+  Out<uint16_t> dist(dist_out, on_device);
+  Tmp<uint32_t> cnt;
   Tmp<unsigned long long> offs;
-  Tmp<uint64_t> d_rows;
-  Tmp<uint16_t> d_dist;
   Tmp<char> scan_tmp;
   if ((rc = dev_alloc(c, cnt.b, (size_t)slots))) return rc;
   if ((rc = dev_alloc(c, offs.b, (size_t)slots))) return rc;
@@ -750,14 +727,10 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, wide, offs.b.p, (int)slots, c->stream));
   if ((rc = dev_alloc(c, scan_tmp.b, scan_bytes))) return rc;
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(scan_tmp.b.p, scan_bytes, wide, offs.b.p, (int)slots, c->stream));
-  uint64_t *rows = on_device ? row_start_out : nullptr;
-  if (row_start_out && !on_device) {
-    if ((rc = dev_alloc(c, d_rows.b, (size_t)(n1 + 1)))) return rc;
-    rows = d_rows.b.p;
-  }
-  if (rows) {
+  if (rows.wanted()) {
+    if ((rc = rows.temp(c, (size_t)(n1 + 1)))) return rc;
     hipLaunchKernelGGL(hm_rows_kernel, dim3(blocks_for(n1 + 1, HM_WG)), dim3(HM_WG), 0, c->stream, offs.b.p, n1,
-                       (uint32_t)S, rows);
+                       (uint32_t)S, rows.p);
     HIP_TRY(c, hipGetLastError());
   }
   unsigned long long total = 0;
@@ -766,21 +739,13 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   *n_edges_out = total;
 
   /* the same walk again, every hit to its place -- when there is room for all of them */
-  const bool fill = hit_out && total && total <= capacity;
-  uint32_t *hit = on_device ? hit_out : nullptr;
-  uint16_t *dist = on_device ? dist_out : nullptr;
+  const bool fill = hit.wanted() && total && total <= capacity;
   if (fill) {
-    if (!on_device) {
-      if ((rc = dev_alloc(c, d_hit.b, (size_t)total))) return rc;
-      hit = d_hit.b.p;
-      if (dist_out) {
-        if ((rc = dev_alloc(c, d_dist.b, (size_t)total))) return rc;
-        dist = d_dist.b.p;
-      }
-    }
+    if ((rc = hit.temp(c, (size_t)total))) return rc;
+    if (dist.wanted() && (rc = dist.temp(c, (size_t)total))) return rc;
     P.offs = offs.b.p;
-    P.hit = hit;
-    P.dist = dist;
+    P.hit = hit.p;
+    P.dist = dist.p;
     if ((rc = hm_launch<SINK_CSR>(c, J)))
       return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -788,12 +753,10 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   c->hm_ms[1] = ms_since(t0);
   if (!on_device) {
     t0 = std::chrono::steady_clock::now();
-    if (row_start_out)
-      HIP_TRY(c, hipMemcpyAsync(row_start_out, rows, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = rows.copy_out(c, (size_t)(n1 + 1)))) return rc;
     if (fill) {
-      HIP_TRY(c, hipMemcpyAsync(hit_out, hit, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-      if (dist_out)
-        HIP_TRY(c, hipMemcpyAsync(dist_out, dist, (size_t)total * sizeof(uint16_t), hipMemcpyDeviceToHost, c->stream));
+      if ((rc = hit.copy_out(c, (size_t)total))) return rc;
+      if ((rc = dist.copy_out(c, (size_t)total))) return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->hm_ms[2] = ms_since(t0);
@@ -802,18 +765,14 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
 }
 
 /* cmpr_hamming_cluster* and cmpr_hamming_cluster_table*: the set against itself through the link sink, then the
-   flatten, size and table passes of cluster.hip.  The plain call fills label / size, the table call the other four. */
-struct HcOut {
-  uint32_t *label = nullptr, *size = nullptr;
-  uint32_t *cluster_of = nullptr, *member = nullptr;
-  uint64_t *cluster_start = nullptr, *count = nullptr;
-};
-
-int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differences, bool table, bool on_device,
-                         const HcOut &out, uint64_t *n_clusters_out)
+   flatten, size and table passes of cluster.hip.  The plain call (T == NULL) fills L's label / size, the table call
+   T's four arrays from labels and sizes of nobody's. */
+int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differences, bool on_device,
+                         ClusterLinks &L, ClusterTableOut *T, uint64_t *n_clusters_out)
 {
   if (!c)
     return CMPR_EINVAL;
+  const bool table = T != nullptr;
   const std::string who = table ? "cmpr_hamming_cluster_table" : "cmpr_hamming_cluster";
   if (n_clusters_out)
     *n_clusters_out = 0;
@@ -831,7 +790,6 @@ int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t diff
   t0 = std::chrono::steady_clock::now();
 
   /* the forest over the original sequence numbers; every unordered pair of every group linked; labels and sizes */
-  ClusterLinks L;
   const uint64_t n = J.s1->n;
   if (n) {
     if ((rc = cmpr_cluster_forest(c, n, L))) return rc;
@@ -839,24 +797,22 @@ int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t diff
     J.P.snapshot = c->hamming_link_snapshot ? 1u : 0u;
     if ((rc = hm_launch<SINK_LINK>(c, J)))
       return rc;
-    const bool to_caller = on_device && !table;
-    if ((rc = cmpr_cluster_flatten(c, n, to_caller ? out.label : nullptr, to_caller ? out.size : nullptr,
-                                   table || out.size != nullptr, L)))
+    if ((rc = cmpr_cluster_flatten(c, n, table || L.size.wanted(), L)))
       return rc;
   }
   if (table)
-    return cmpr_cluster_table_pass(c, L, c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p, on_device, out.cluster_of,
-                                   out.cluster_start, out.member, out.count, n_clusters_out, t0, &c->hm_ms[1]);
+    return cmpr_cluster_table_pass(c, L, c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p, *T, n_clusters_out, t0,
+                                   &c->hm_ms[1]);
   if (n && !on_device) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->hm_ms[1] = ms_since(t0);
     t0 = std::chrono::steady_clock::now();
-    if ((rc = cmpr_cluster_results(c, L, false, out.label, out.size, n_clusters_out)))
+    if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
       return rc;
     c->hm_ms[2] = ms_since(t0);
     return CMPR_OK;
   }
-  if ((rc = cmpr_cluster_results(c, L, on_device, out.label, out.size, n_clusters_out)))
+  if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
     return rc;
   c->hm_ms[1] = ms_since(t0);
   return CMPR_OK;
@@ -868,10 +824,8 @@ extern "C" int cmpr_hamming_cluster(cmpr_context *c, const cmpr_set_view *set, i
                                     uint32_t *label_out, uint32_t *size_out, uint64_t *n_clusters_out)
 {
   return guarded(c, [&] {
-    HcOut out;
-    out.label = label_out;
-    out.size = size_out;
-    return hamming_cluster_impl(c, set, differences, false, false, out, n_clusters_out);
+    ClusterLinks L(label_out, size_out, false);
+    return hamming_cluster_impl(c, set, differences, false, L, nullptr, n_clusters_out);
   });
 }
 
@@ -879,10 +833,8 @@ extern "C" int cmpr_hamming_cluster_device(cmpr_context *c, const cmpr_set_view 
                                            uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out)
 {
   return guarded(c, [&] {
-    HcOut out;
-    out.label = d_label_out;
-    out.size = d_size_out;
-    return hamming_cluster_impl(c, d_set, differences, false, true, out, n_clusters_out);
+    ClusterLinks L(d_label_out, d_size_out, true);
+    return hamming_cluster_impl(c, d_set, differences, true, L, nullptr, n_clusters_out);
   });
 }
 
@@ -891,12 +843,9 @@ extern "C" int cmpr_hamming_cluster_table(cmpr_context *c, const cmpr_set_view *
                                           uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out)
 {
   return guarded(c, [&] {
-    HcOut out;
-    out.cluster_of = cluster_of_out;
-    out.cluster_start = cluster_start_out;
-    out.member = member_out;
-    out.count = count_out;
-    return hamming_cluster_impl(c, set, differences, true, false, out, n_clusters_out);
+    ClusterLinks L(nullptr, nullptr, false);
+    ClusterTableOut T(cluster_of_out, cluster_start_out, member_out, count_out, false);
+    return hamming_cluster_impl(c, set, differences, false, L, &T, n_clusters_out);
   });
 }
 
@@ -906,12 +855,9 @@ extern "C" int cmpr_hamming_cluster_table_device(cmpr_context *c, const cmpr_set
                                                  uint64_t *n_clusters_out)
 {
   return guarded(c, [&] {
-    HcOut out;
-    out.cluster_of = d_cluster_of_out;
-    out.cluster_start = d_cluster_start_out;
-    out.member = d_member_out;
-    out.count = d_count_out;
-    return hamming_cluster_impl(c, d_set, differences, true, true, out, n_clusters_out);
+    ClusterLinks L(nullptr, nullptr, true);
+    ClusterTableOut T(d_cluster_of_out, d_cluster_start_out, d_member_out, d_count_out, true);
+    return hamming_cluster_impl(c, d_set, differences, true, L, &T, n_clusters_out);
   });
 }
 

@@ -106,12 +106,14 @@ nb_cursor_kernel(const uint64_t *row_start, uint32_t *degree, uint64_t n)
     degree[i] = (uint32_t)(row_start[i + 1] - row_start[i]);
 }
 
-/* ---- count; scan, census ---- the degrees and the scan's scratch are allocated here; row_start[n1 + 1] is device
-   memory, host_rows (or NULL) receives a copy in the same wait that brings the edge count and the census */
-int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *host_rows)
+/* ---- count; scan, census ---- the degrees and the scan's scratch are allocated here; e.row_start is n1 + 1 words of
+   device memory, and a host array of the caller's receives them in the same wait that brings the edge count and the
+   census */
+int nb_count(cmpr_context *c, NeighborEdges &e)
 {
   int rc;
   const uint64_t n1 = c->n1;
+  uint64_t *const row_start = e.row_start.p;
   /* TEST ONLY (tunable "assume_never_overflows"): the pretence is used up by the first launch it meets; it is
      renewed for the fill step, so that the repeat of either step can be provoked (tests/test_neighbors_gpu.py) */
   e.pretend_no_redo = c->force_no_redo;
@@ -144,9 +146,7 @@ int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *h
   unsigned long long total = 0, seen[3] = {0, 0, 0};
   HIP_TRY(c, hipMemcpyAsync(&total, row_start + n1, sizeof total, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(seen, e.census.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
-  if (host_rows)
-    HIP_TRY(c, hipMemcpyAsync(host_rows, row_start, (size_t)(n1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                              c->stream));
+  if ((rc = e.row_start.copy_out(c, (size_t)(n1 + 1)))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->nb_ms[1] = ms_since(t0);
   e.total = total;
@@ -156,11 +156,13 @@ int nb_count(cmpr_context *c, NeighborEdges &e, uint64_t *row_start, uint64_t *h
   return CMPR_OK;
 }
 
-/* ---- fill ---- every hit into its row, in the order of arrival; dist (or NULL): its distance beside it */
-int nb_fill(cmpr_context *c, NeighborEdges &e, const uint64_t *row_start, uint32_t *hit, uint8_t *dist)
+/* ---- fill ---- every hit into its row of e.hit, in the order of arrival; dist (or NULL): its distance beside it */
+int nb_fill(cmpr_context *c, NeighborEdges &e, uint8_t *dist)
 {
   int rc;
   const uint64_t n1 = c->n1;
+  const uint64_t *const row_start = e.row_start.p;
+  uint32_t *const hit = e.hit.p;
   uint32_t *const degree = e.degree.p;
   if (e.pretend_no_redo) {
     c->force_no_redo = true;
@@ -200,13 +202,10 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     return fail(c, CMPR_EUNSUPPORTED, who + ": a routed query set holds part of each row (cmpr_set_queries_routed)");
   const uint64_t n1 = c->n1;
 
-  NeighborEdges e;
-  uint64_t *row_start = on_device ? row_start_out : nullptr;
-  if (!row_start) {
-    if ((rc = dev_alloc(c, e.row_start, (size_t)(n1 + 1)))) return rc;
-    row_start = e.row_start.p;
-  }
-  if ((rc = nb_count(c, e, row_start, on_device ? nullptr : row_start_out)))
+  NeighborEdges e(row_start_out, hit_out, on_device);
+  Out<uint8_t> dist_o(dist_out, on_device);
+  if ((rc = e.row_start.temp(c, (size_t)(n1 + 1)))) return rc;
+  if ((rc = nb_count(c, e)))
     return rc;
   const uint64_t total = e.total;
   *n_edges_out = total;
@@ -217,19 +216,14 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   const uint64_t n_long = e.n_long, n_big = e.n_big, longest = e.longest;
   Tmp<uint32_t> big_rows, scratch;
   Tmp<unsigned long long> long_desc;
-  Tmp<uint8_t> dist_tmp, dist_scratch;
+  Tmp<uint8_t> dist_scratch;
   Tmp<char> sort_tmp;
   size_t sort_bytes = 0;
-  uint32_t *hit = on_device ? hit_out : nullptr;
-  if (!hit) {
-    if ((rc = dev_alloc(c, e.hit, (size_t)total))) return rc;
-    hit = e.hit.p;
-  }
-  uint8_t *dist = on_device ? dist_out : nullptr;
-  if (with_dist && !dist) {
-    if ((rc = dev_alloc(c, dist_tmp.b, (size_t)total))) return rc;
-    dist = dist_tmp.b.p;
-  }
+  if ((rc = e.hit.temp(c, (size_t)total))) return rc;
+  if (with_dist && (rc = dist_o.temp(c, (size_t)total))) return rc;
+  const uint64_t *const row_start = e.row_start.p;
+  uint32_t *const hit = e.hit.p;
+  uint8_t *const dist = dist_o.p;
   if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
   if (n_long) {
     if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
@@ -245,7 +239,7 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
     }
     if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
   }
-  if ((rc = nb_fill(c, e, row_start, hit, dist)))
+  if ((rc = nb_fill(c, e, dist)))
     return rc;
 
   /* ---- order the rows ---- */
@@ -273,11 +267,8 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
                                 c->stream));
     }
   }
-  if (!on_device) {
-    HIP_TRY(c, hipMemcpyAsync(hit_out, hit, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (with_dist)
-      HIP_TRY(c, hipMemcpyAsync(dist_out, dist, (size_t)total, hipMemcpyDeviceToHost, c->stream));
-  }
+  if ((rc = e.hit.copy_out(c, (size_t)total))) return rc;
+  if ((rc = dist_o.copy_out(c, (size_t)total))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->nb_ms[3] = ms_since(t0);
   return CMPR_OK;
@@ -288,12 +279,12 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
 int cmpr_neighbor_edges(cmpr_context *c, NeighborEdges &e)
 {
   int rc;
-  if ((rc = dev_alloc(c, e.row_start, (size_t)(c->n1 + 1)))) return rc;
-  if ((rc = nb_count(c, e, e.row_start.p, nullptr))) return rc;
+  if ((rc = e.row_start.temp(c, (size_t)(c->n1 + 1)))) return rc;
+  if ((rc = nb_count(c, e))) return rc;
   if (e.total == 0)
     return CMPR_OK;
-  if ((rc = dev_alloc(c, e.hit, (size_t)e.total))) return rc;
-  return nb_fill(c, e, e.row_start.p, e.hit.p, nullptr);
+  if ((rc = e.hit.temp(c, (size_t)e.total))) return rc;
+  return nb_fill(c, e, nullptr);
 }
 
 extern "C" int cmpr_neighbors(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out,

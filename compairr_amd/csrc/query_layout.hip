@@ -2071,12 +2071,24 @@ const char *verr_message(uint32_t e)
 int cmpr_upload_and_validate(cmpr_context *c, const cmpr_set_view *s, DevBuf<uint8_t> &res,
                              DevBuf<uint64_t> &off, DevBuf<uint32_t> &v, DevBuf<uint32_t> &j,
                              DevBuf<uint32_t> &rep, DevBuf<uint64_t> &cnt, uint32_t &longest,
-                             std::vector<double> &rep_total, bool on_device, uint64_t total_dev)
+                             std::vector<double> &rep_total, bool on_device, uint64_t *residues)
 {
   int rc;
-  /* (on_device: the view's arrays are device memory -- a copy inside the device; its
-     offsets[n] was fetched by the caller) */
-  const uint64_t total = on_device ? total_dev : (s->n ? s->offsets[s->n] : 0);
+  /* (on_device: the view's arrays are device memory -- a copy inside the device; offsets[0] and
+     offsets[n] are all the host sees of them) */
+  uint64_t total = !on_device && s->n ? s->offsets[s->n] : 0;
+  if (on_device && s->n) {
+    uint64_t ends[2] = {0, 0};
+    HIP_TRY(c, hipMemcpy(&ends[0], s->offsets, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(&ends[1], s->offsets + s->n, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (ends[0] != 0)
+      return fail(c, CMPR_EINVAL, "offsets[0] must be 0");
+    if (ends[1] > 0xffffull * s->n)
+      return fail(c, CMPR_EINVAL, "offsets not monotone");
+    total = ends[1];
+  }
+  if (residues)
+    *residues = total;
   const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   static const uint64_t zero_off[1] = {0};
   auto put = [&](auto &buf, const auto *from, size_t count, bool host_src = false) -> int {

@@ -260,25 +260,12 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
     return fail(c, CMPR_EINVAL, "part_buckets_log2 below table_log2_delta");
   if (nparts > MAX_PARTS)
     return fail(c, CMPR_EUNSUPPORTED, "reference set needs more than 65536 parts (part_buckets_log2)");
-  /* residues in all: offsets[n], which a device view keeps on the device */
-  uint64_t residues2 = 0;
-  if (s->n && !on_device) {
-    residues2 = s->offsets[s->n];
-  } else if (s->n) {
-    uint64_t ends[2] = {0, 0};
-    HIP_TRY(c, hipMemcpy(&ends[0], s->offsets, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(c, hipMemcpy(&ends[1], s->offsets + s->n, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (ends[0] != 0)
-      return fail(c, CMPR_EINVAL, "offsets[0] must be 0");
-    if (ends[1] > 0xffffull * s->n)
-      return fail(c, CMPR_EINVAL, "offsets not monotone");
-    residues2 = ends[1];
-  }
 
-  /* ---- the set as the caller has it, validated on the device ---- */
+  /* ---- the set as the caller has it, validated on the device; residues in all: offsets[n] ---- */
   uint32_t longest = 0;
+  uint64_t residues2 = 0;
   if ((rc = cmpr_upload_and_validate(c, s, c->res2, c->off2, c->v2, c->j2, c->rep2, c->cnt2, longest,
-                                     c->tot2, on_device, residues2)))
+                                     c->tot2, on_device, &residues2)))
     return rc;
   c->longest2 = longest;
   c->n2 = s->n;

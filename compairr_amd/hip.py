@@ -6,6 +6,7 @@ calls fail loudly."""
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
@@ -111,6 +112,53 @@ def library_path() -> str:
 _lib = None
 
 
+def _argtypes() -> dict:
+    """argtypes per entry point; a host variant and its _device twin that take the same arguments are written once."""
+    ctx = ptr = C.c_void_p
+    opts, view, u64p = C.POINTER(_Options), C.POINTER(_SetView), C.POINTER(C.c_uint64)
+    table = {
+        "cmpr_create": [opts, C.POINTER(C.c_void_p)],
+        "cmpr_destroy": [ctx],
+        "cmpr_last_error": [ctx],
+        "cmpr_set_reference": [ctx, view, C.c_uint32],
+        "cmpr_set_reference_device": [ctx, view, C.c_uint32],
+        "cmpr_set_queries": [ctx, view],
+        "cmpr_set_queries_device": [ctx, view],
+        "cmpr_route_queries": [ctx, view, C.c_uint64, C.c_uint32, u64p, C.POINTER(C.c_uint32), ptr],
+        "cmpr_route_pack": [ctx, ptr, C.c_uint64],
+        "cmpr_set_queries_routed": [ctx, ptr, C.c_uint64, C.c_uint32, C.c_uint64, ptr],
+        "cmpr_overlap_matrix": [ctx, ptr],
+        "cmpr_overlap_matrix_f64": [ctx, ptr],
+        "cmpr_overlap_matrix_device": [ctx, ptr, ptr],
+        "cmpr_get_stats": [ctx, C.POINTER(_Stats)],
+        "cmpr_get_kernel_times": [ctx, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                  C.POINTER(C.c_uint32)],
+        "cmpr_overlap_pairs": [ctx, C.c_uint64, ptr, ptr, u64p],
+        "cmpr_count_duplicates": [ctx, view, u64p],
+        "cmpr_rows": [ctx],
+        "cmpr_cols": [ctx],
+        "cmpr_set_tunable": [ctx, C.c_char_p, C.c_int64],
+        "cmpr_get_tunable": [ctx, C.c_char_p, C.POINTER(C.c_int64)],
+        "cmpr_warm_up": [opts],
+        "cmpr_warm_up_sized": [opts, C.c_uint64, C.c_uint64, C.c_uint64],
+    }
+    twins = {
+        "cmpr_deduplicate": [ctx, view, C.c_uint64, ptr, ptr, u64p, u64p],
+        "cmpr_cluster": [ctx, view, ptr, ptr, u64p],
+        "cmpr_neighbors": [ctx, C.c_uint64, ptr, ptr, u64p],
+        "cmpr_existence_csr": [ctx, C.c_uint64, ptr, ptr, ptr, u64p],
+        "cmpr_cluster_table": [ctx, view, ptr, ptr, ptr, ptr, u64p],
+        "cmpr_neighbors_distance": [ctx, C.c_uint64, ptr, ptr, ptr, u64p],
+        "cmpr_hamming_matrix": [ctx, view, view, C.c_int64, ptr],
+        "cmpr_hamming_neighbors": [ctx, view, view, C.c_int64, C.c_uint64, ptr, ptr, ptr, u64p],
+        "cmpr_hamming_cluster": [ctx, view, C.c_int64, ptr, ptr, u64p],
+        "cmpr_hamming_cluster_table": [ctx, view, C.c_int64, ptr, ptr, ptr, ptr, u64p],
+    }
+    for name, args in twins.items():
+        table[name] = table[name + "_device"] = args
+    return table
+
+
 def load_library() -> C.CDLL:
     global _lib
     if _lib is not None:
@@ -129,76 +177,18 @@ def load_library() -> C.CDLL:
             "%s is missing: build it with `make lib` (hipcc --offload-arch=gfx950). "
             "There is no CPU fallback." % path)
     lib = C.CDLL(path)
+    # (additions do not bump the ABI version: a version-5 library built before an entry point lacks it, and only the
+    # callers of that entry point fail on it, with AttributeError -- tools/*_timing.py --against run the parent
+    # commit's build through this binding)
+    for name, args in _argtypes().items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = args
     lib.cmpr_abi_version.restype = C.c_int
-    lib.cmpr_create.argtypes = [C.POINTER(_Options), C.POINTER(C.c_void_p)]
-    lib.cmpr_destroy.argtypes = [C.c_void_p]
     lib.cmpr_destroy.restype = None
-    lib.cmpr_last_error.argtypes = [C.c_void_p]
     lib.cmpr_last_error.restype = C.c_char_p
-    lib.cmpr_set_reference.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_uint32]
-    lib.cmpr_set_queries.argtypes = [C.c_void_p, C.POINTER(_SetView)]
-    lib.cmpr_set_reference_device.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_uint32]
-    lib.cmpr_set_queries_device.argtypes = [C.c_void_p, C.POINTER(_SetView)]
-    lib.cmpr_route_queries.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_uint64, C.c_uint32,
-                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.c_void_p]
-    lib.cmpr_route_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-    lib.cmpr_set_queries_routed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64,
-                                            C.c_void_p]
-    lib.cmpr_overlap_matrix.argtypes = [C.c_void_p, C.c_void_p]
-    lib.cmpr_overlap_matrix_f64.argtypes = [C.c_void_p, C.c_void_p]
-    lib.cmpr_overlap_matrix_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.cmpr_get_stats.argtypes = [C.c_void_p, C.POINTER(_Stats)]
-    lib.cmpr_get_kernel_times.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double),
-                                          C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
-    lib.cmpr_overlap_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                       C.POINTER(C.c_uint64)]
-    lib.cmpr_count_duplicates.argtypes = [C.c_void_p, C.POINTER(_SetView), C.POINTER(C.c_uint64)]
-    lib.cmpr_deduplicate.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_uint64, C.c_void_p, C.c_void_p,
-                                     C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-    lib.cmpr_deduplicate_device.argtypes = lib.cmpr_deduplicate.argtypes
-    lib.cmpr_cluster.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-    lib.cmpr_cluster_device.argtypes = lib.cmpr_cluster.argtypes
-    # (additions do not bump the ABI version: a version-5 library built before this one lacks it, and only the
-    # callers of neighbors() fail on it, with AttributeError -- tools/neighbors_timing.py --against runs bench.py
-    # on the parent commit's build through this binding)
-    if hasattr(lib, "cmpr_neighbors"):
-        lib.cmpr_neighbors.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-        lib.cmpr_neighbors_device.argtypes = lib.cmpr_neighbors.argtypes
-    if hasattr(lib, "cmpr_existence_csr"):         # (likewise: tools/existence_timing.py --against)
-        lib.cmpr_existence_csr.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.POINTER(C.c_uint64)]
-        lib.cmpr_existence_csr_device.argtypes = lib.cmpr_existence_csr.argtypes
-    if hasattr(lib, "cmpr_cluster_table"):         # (likewise: tools/cluster_table_timing.py --against)
-        lib.cmpr_cluster_table.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.POINTER(C.c_uint64)]
-        lib.cmpr_cluster_table_device.argtypes = lib.cmpr_cluster_table.argtypes
-    if hasattr(lib, "cmpr_neighbors_distance"):    # (likewise: tools/neighbors_timing.py --against)
-        lib.cmpr_neighbors_distance.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.POINTER(C.c_uint64)]
-        lib.cmpr_neighbors_distance_device.argtypes = lib.cmpr_neighbors_distance.argtypes
-    if hasattr(lib, "cmpr_hamming_matrix"):        # (likewise: tools/hamming_timing.py --against)
-        lib.cmpr_hamming_matrix.argtypes = [C.c_void_p, C.POINTER(_SetView), C.POINTER(_SetView), C.c_int64,
-                                            C.c_void_p]
-        lib.cmpr_hamming_matrix_device.argtypes = lib.cmpr_hamming_matrix.argtypes
-        lib.cmpr_hamming_neighbors.argtypes = [C.c_void_p, C.POINTER(_SetView), C.POINTER(_SetView), C.c_int64,
-                                               C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(C.c_uint64)]
-        lib.cmpr_hamming_neighbors_device.argtypes = lib.cmpr_hamming_neighbors.argtypes
-    if hasattr(lib, "cmpr_hamming_cluster"):       # (likewise: tools/hamming_cluster_timing.py --against)
-        lib.cmpr_hamming_cluster.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_int64, C.c_void_p, C.c_void_p,
-                                             C.POINTER(C.c_uint64)]
-        lib.cmpr_hamming_cluster_device.argtypes = lib.cmpr_hamming_cluster.argtypes
-        lib.cmpr_hamming_cluster_table.argtypes = [C.c_void_p, C.POINTER(_SetView), C.c_int64, C.c_void_p, C.c_void_p,
-                                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-        lib.cmpr_hamming_cluster_table_device.argtypes = lib.cmpr_hamming_cluster_table.argtypes
-    lib.cmpr_rows.argtypes = [C.c_void_p]
     lib.cmpr_rows.restype = C.c_uint32
-    lib.cmpr_cols.argtypes = [C.c_void_p]
     lib.cmpr_cols.restype = C.c_uint32
-    lib.cmpr_set_tunable.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-    lib.cmpr_get_tunable.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64)]
-    lib.cmpr_warm_up.argtypes = [C.POINTER(_Options)]
-    lib.cmpr_warm_up_sized.argtypes = [C.POINTER(_Options), C.c_uint64, C.c_uint64, C.c_uint64]
     if lib.cmpr_abi_version() != 5:
         raise RuntimeError("libcompairr_hip.so ABI version mismatch")
     _lib = lib
@@ -348,15 +338,52 @@ class HipOverlap:
         self._check(self._lib.cmpr_overlap_matrix_device(
             self._ctx, C.c_void_p(d_matrix), C.c_void_p(stream or 0)))
 
+    def _count_then_fill(self, fn, head, n_rows, dtypes):
+        """The capacity protocol of fn(ctx, *head, capacity, [row_start,] *arrays, &n): one count-only call, then one
+        with the exact capacity.  n_rows: None for an entry point without row_start, else a callable that gives the
+        number of rows; dtypes: per array its dtype, None for one that is not wanted.  Returns [row_start,] *arrays."""
+        n = C.c_uint64()
+        lead = [] if n_rows is None else [None]
+        self._check(fn(self._ctx, *head, 0, *lead, *[None] * len(dtypes), C.byref(n)))
+        if n_rows is not None:
+            lead = [np.zeros(n_rows() + 1, dtype=np.uint64)]
+        arrays = [None if dt is None else np.zeros(n.value, dtype=dt) for dt in dtypes]
+        self._check(fn(self._ctx, *head, n.value, *[a.ctypes.data for a in lead],
+                       *[a.ctypes.data if a is not None and n.value else None for a in arrays], C.byref(n)))
+        assert n.value == len(arrays[0])
+        return lead + arrays
+
+    def _into_device(self, fn, view: _SetView, extra, *pointers) -> int:
+        """fn(ctx, view, *extra, *device pointers (0: not wanted), &count) -> count"""
+        out = C.c_uint64()
+        self._check(fn(self._ctx, C.byref(view), *extra, *[C.c_void_p(p or None) for p in pointers], C.byref(out)))
+        return out.value
+
+    def _labels(self, fn, s: RepertoireSet, *extra):
+        """cluster() / hamming_cluster(): fn(ctx, view, *extra, label, size, &n_clusters)"""
+        v = _view(s)
+        label = np.zeros(s.n, dtype=np.uint32)
+        size = np.zeros(s.n, dtype=np.uint32)
+        clusters = C.c_uint64()
+        self._check(fn(self._ctx, C.byref(v), *extra, label.ctypes.data, size.ctypes.data, C.byref(clusters)))
+        return label, size, clusters.value
+
+    def _table(self, fn, s: RepertoireSet, *extra):
+        """cluster_table() / hamming_cluster_table(): fn(ctx, view, *extra, the four arrays, &n_clusters)"""
+        v = _view(s)
+        cluster_of = np.zeros(s.n, dtype=np.uint32)
+        cluster_start = np.zeros(s.n + 1, dtype=np.uint64)
+        members = np.zeros(s.n, dtype=np.uint32)
+        count = np.zeros(s.n, dtype=np.uint64)
+        clusters = C.c_uint64()
+        self._check(fn(self._ctx, C.byref(v), *extra, cluster_of.ctypes.data, cluster_start.ctypes.data,
+                       members.ctypes.data, count.ctypes.data, C.byref(clusters)))
+        k = clusters.value
+        return cluster_of, cluster_start[:k + 1].copy(), members, count[:k].copy()
+
     def overlap_pairs(self) -> np.ndarray:
         """(query index, hit index) of every matching pair, sorted."""
-        n = C.c_uint64()
-        self._check(self._lib.cmpr_overlap_pairs(self._ctx, 0, None, None, C.byref(n)))
-        q = np.zeros(n.value, dtype=np.uint32)
-        h = np.zeros(n.value, dtype=np.uint32)
-        self._check(self._lib.cmpr_overlap_pairs(self._ctx, n.value, q.ctypes.data,
-                                                 h.ctypes.data, C.byref(n)))
-        assert n.value == len(q)
+        q, h = self._count_then_fill(self._lib.cmpr_overlap_pairs, (), None, (np.uint32, np.uint32))
         out = np.stack([q, h], axis=1)
         return out[np.lexsort((out[:, 1], out[:, 0]))]
 
@@ -398,21 +425,12 @@ class HipOverlap:
         """(label uint32[n], size uint32[n], n_clusters): per sequence of `s` the smallest sequence number of
         its cluster and the number of members of that cluster -- the reference's --cluster (cluster.cc) without
         its output order.  Afterwards `s` is resident as both sets."""
-        v = _view(s)
-        label = np.zeros(s.n, dtype=np.uint32)
-        size = np.zeros(s.n, dtype=np.uint32)
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_cluster(self._ctx, C.byref(v), label.ctypes.data, size.ctypes.data,
-                                           C.byref(clusters)))
-        return label, size, clusters.value
+        return self._labels(self._lib.cmpr_cluster, s)
 
     def cluster_device(self, view: _SetView, d_label: int = 0, d_size: int = 0) -> int:
         """The same for a view of device pointers (device_view): labels and sizes are written to the device
         arrays d_label and d_size (uint32[n] each; 0: not wanted); returns n_clusters."""
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_cluster_device(self._ctx, C.byref(view), C.c_void_p(d_label or None),
-                                                  C.c_void_p(d_size or None), C.byref(clusters)))
-        return clusters.value
+        return self._into_device(self._lib.cmpr_cluster_device, view, (), d_label, d_size)
 
     # ---- the clusters numbered and grouped (include/compairr_hip.h: cmpr_cluster_table*) ----
 
@@ -421,28 +439,15 @@ class HipOverlap:
         of `s` numbered by (size descending, smallest member ascending) -- the reference's cluster_no - 1 --, the
         members of cluster k, increasing, in members[cluster_start[k]:cluster_start[k + 1]], and its summed
         duplicate_count (with ignore_counts its size).  Afterwards `s` is resident as both sets."""
-        v = _view(s)
-        cluster_of = np.zeros(s.n, dtype=np.uint32)
-        cluster_start = np.zeros(s.n + 1, dtype=np.uint64)
-        members = np.zeros(s.n, dtype=np.uint32)
-        count = np.zeros(s.n, dtype=np.uint64)
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_cluster_table(self._ctx, C.byref(v), cluster_of.ctypes.data,
-                                                 cluster_start.ctypes.data, members.ctypes.data, count.ctypes.data,
-                                                 C.byref(clusters)))
-        k = clusters.value
-        return cluster_of, cluster_start[:k + 1].copy(), members, count[:k].copy()
+        return self._table(self._lib.cmpr_cluster_table, s)
 
     def cluster_table_device(self, view: _SetView, d_cluster_of: int = 0, d_cluster_start: int = 0,
                              d_member: int = 0, d_count: int = 0) -> int:
         """The same for a view of device pointers (device_view), into device arrays: d_cluster_of and d_member
         (uint32[n]), d_cluster_start (uint64[n + 1], K + 1 written) and d_count (uint64[n], K written); 0: not
         wanted.  Returns K."""
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_cluster_table_device(
-            self._ctx, C.byref(view), C.c_void_p(d_cluster_of or None), C.c_void_p(d_cluster_start or None),
-            C.c_void_p(d_member or None), C.c_void_p(d_count or None), C.byref(clusters)))
-        return clusters.value
+        return self._into_device(self._lib.cmpr_cluster_table_device, view, (), d_cluster_of, d_cluster_start,
+                                 d_member, d_count)
 
     # ---- the pairs as neighbour lists in CSR (include/compairr_hip.h: cmpr_neighbors*) ----
 
@@ -450,14 +455,7 @@ class HipOverlap:
         """(row_start uint64[n1 + 1], hits uint32[E]) of the resident sets: the hits of query i, in increasing
         order, are hits[row_start[i]:row_start[i + 1]] -- the pairs of overlap_pairs() without a sort on the
         host.  One degree-only call, then one with the exact capacity."""
-        n = C.c_uint64()
-        self._check(self._lib.cmpr_neighbors(self._ctx, 0, None, None, C.byref(n)))
-        row_start = np.zeros(self._queries() + 1, dtype=np.uint64)
-        hits = np.zeros(n.value, dtype=np.uint32)
-        self._check(self._lib.cmpr_neighbors(self._ctx, n.value, row_start.ctypes.data,
-                                             hits.ctypes.data if n.value else None, C.byref(n)))
-        assert n.value == len(hits)
-        return row_start, hits
+        return tuple(self._count_then_fill(self._lib.cmpr_neighbors, (), self._queries, (np.uint32,)))
 
     def neighbors_device(self, capacity: int = 0, d_row_start: int = 0, d_hits: int = 0) -> int:
         """The same into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted) and d_hits
@@ -474,16 +472,8 @@ class HipOverlap:
         """(row_start uint64[n1 + 1], hits uint32[E], distance uint8[E]): neighbors() and, beside every hit, the
         reference's --distance of the pair -- the number of differing positions when both sequences have one
         length, else 1.  One degree-only call, then one with the exact capacity."""
-        n = C.c_uint64()
-        self._check(self._lib.cmpr_neighbors_distance(self._ctx, 0, None, None, None, C.byref(n)))
-        row_start = np.zeros(self._queries() + 1, dtype=np.uint64)
-        hits = np.zeros(n.value, dtype=np.uint32)
-        distance = np.zeros(n.value, dtype=np.uint8)
-        self._check(self._lib.cmpr_neighbors_distance(self._ctx, n.value, row_start.ctypes.data,
-                                                      hits.ctypes.data if n.value else None,
-                                                      distance.ctypes.data if n.value else None, C.byref(n)))
-        assert n.value == len(hits)
-        return row_start, hits, distance
+        return tuple(self._count_then_fill(self._lib.cmpr_neighbors_distance, (), self._queries,
+                                           (np.uint32, np.uint8)))
 
     def neighbors_distance_device(self, capacity: int = 0, d_row_start: int = 0, d_hits: int = 0,
                                   d_distance: int = 0) -> int:
@@ -504,16 +494,8 @@ class HipOverlap:
         repertoire[row_start[i]:row_start[i + 1]], in increasing order, with their values beside them.  Works on
         a context without `existence`, which never holds the dense table.  One count-only call, then one with
         the exact capacity."""
-        n = C.c_uint64()
-        self._check(self._lib.cmpr_existence_csr(self._ctx, 0, None, None, None, C.byref(n)))
-        row_start = np.zeros(self._queries() + 1, dtype=np.uint64)
-        repertoire = np.zeros(n.value, dtype=np.uint32)
-        value = np.zeros(n.value, dtype=np.uint64)
-        self._check(self._lib.cmpr_existence_csr(self._ctx, n.value, row_start.ctypes.data,
-                                                 repertoire.ctypes.data if n.value else None,
-                                                 value.ctypes.data if n.value else None, C.byref(n)))
-        assert n.value == len(repertoire)
-        return row_start, repertoire, value
+        return tuple(self._count_then_fill(self._lib.cmpr_existence_csr, (), self._queries,
+                                           (np.uint32, np.uint64)))
 
     def existence_csr_device(self, capacity: int = 0, d_row_start: int = 0, d_repertoire: int = 0,
                              d_value: int = 0) -> int:
@@ -552,17 +534,8 @@ class HipOverlap:
         positions beside each.  One count-only call, then one with the exact capacity."""
         v1 = _view(set1)
         v2 = v1 if set2 is set1 else _view(set2)
-        n = C.c_uint64()
-        self._check(self._lib.cmpr_hamming_neighbors(self._ctx, C.byref(v1), C.byref(v2), differences, 0, None, None,
-                                                     None, C.byref(n)))
-        row_start = np.zeros(set1.n + 1, dtype=np.uint64)
-        hits = np.zeros(n.value, dtype=np.uint32)
-        dist = np.zeros(n.value, dtype=np.uint16) if distances else None
-        self._check(self._lib.cmpr_hamming_neighbors(
-            self._ctx, C.byref(v1), C.byref(v2), differences, n.value, row_start.ctypes.data,
-            hits.ctypes.data if n.value else None, dist.ctypes.data if distances and n.value else None, C.byref(n)))
-        assert n.value == len(hits)
-        return row_start, hits, dist
+        return tuple(self._count_then_fill(self._lib.cmpr_hamming_neighbors, (C.byref(v1), C.byref(v2), differences),
+                                           lambda: set1.n, (np.uint32, np.uint16 if distances else None)))
 
     def hamming_neighbors_device(self, view1: _SetView, view2: _SetView, differences: int, capacity: int = 0,
                                  d_row_start: int = 0, d_hits: int = 0, d_distance: int = 0) -> int:
@@ -581,49 +554,25 @@ class HipOverlap:
         """(label uint32[n], size uint32[n], n_clusters) of `s` as cluster() gives them, under the pair relation of
         hamming_neighbors(s, s, differences): any `differences` >= 0.  The context's own `differences` and
         resident sets play no part, and `s` is not resident afterwards."""
-        v = _view(s)
-        label = np.zeros(s.n, dtype=np.uint32)
-        size = np.zeros(s.n, dtype=np.uint32)
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_hamming_cluster(self._ctx, C.byref(v), differences, label.ctypes.data,
-                                                   size.ctypes.data, C.byref(clusters)))
-        return label, size, clusters.value
+        return self._labels(self._lib.cmpr_hamming_cluster, s, differences)
 
     def hamming_cluster_device(self, view: _SetView, differences: int, d_label: int = 0, d_size: int = 0) -> int:
         """The same for a view of device pointers (device_view): labels and sizes are written to the device
         arrays d_label and d_size (uint32[n] each; 0: not wanted); returns n_clusters."""
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_hamming_cluster_device(self._ctx, C.byref(view), differences,
-                                                          C.c_void_p(d_label or None), C.c_void_p(d_size or None),
-                                                          C.byref(clusters)))
-        return clusters.value
+        return self._into_device(self._lib.cmpr_hamming_cluster_device, view, (differences,), d_label, d_size)
 
     def hamming_cluster_table(self, s: RepertoireSet, differences: int):
         """(cluster_of uint32[n], cluster_start uint64[K + 1], members uint32[n], count uint64[K]) of `s` as
         cluster_table() gives them, under the pair relation of hamming_neighbors(s, s, differences)."""
-        v = _view(s)
-        cluster_of = np.zeros(s.n, dtype=np.uint32)
-        cluster_start = np.zeros(s.n + 1, dtype=np.uint64)
-        members = np.zeros(s.n, dtype=np.uint32)
-        count = np.zeros(s.n, dtype=np.uint64)
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_hamming_cluster_table(self._ctx, C.byref(v), differences, cluster_of.ctypes.data,
-                                                         cluster_start.ctypes.data, members.ctypes.data,
-                                                         count.ctypes.data, C.byref(clusters)))
-        k = clusters.value
-        return cluster_of, cluster_start[:k + 1].copy(), members, count[:k].copy()
+        return self._table(self._lib.cmpr_hamming_cluster_table, s, differences)
 
     def hamming_cluster_table_device(self, view: _SetView, differences: int, d_cluster_of: int = 0,
                                      d_cluster_start: int = 0, d_member: int = 0, d_count: int = 0) -> int:
         """The same for a view of device pointers (device_view), into device arrays: d_cluster_of and d_member
         (uint32[n]), d_cluster_start (uint64[n + 1], K + 1 written) and d_count (uint64[n], K written); 0: not
         wanted.  Returns K."""
-        clusters = C.c_uint64()
-        self._check(self._lib.cmpr_hamming_cluster_table_device(
-            self._ctx, C.byref(view), differences, C.c_void_p(d_cluster_of or None),
-            C.c_void_p(d_cluster_start or None), C.c_void_p(d_member or None), C.c_void_p(d_count or None),
-            C.byref(clusters)))
-        return clusters.value
+        return self._into_device(self._lib.cmpr_hamming_cluster_table_device, view, (differences,), d_cluster_of,
+                                 d_cluster_start, d_member, d_count)
 
     def _queries(self) -> int:
         return self.stats().queries
@@ -645,12 +594,24 @@ class HipOverlap:
                      st.kernel_launches, st.probe_ms, st.filter_reads)
 
 
+@contextlib.contextmanager
+def _context(opt: Options, tunables: Optional[dict] = None, set1: Optional[RepertoireSet] = None,
+             set2: Optional[RepertoireSet] = None):
+    """A context of its own for one convenience call: `tunables` set on it first, then (when given) set2 resident
+    as the reference and set1 as the queries."""
+    with HipOverlap(opt) as h:
+        for name, value in (tunables or {}).items():
+            h.set_tunable(name, value)
+        if set2 is not None:
+            h.set_reference(set2, set1.longest)
+            h.set_queries(set1)
+        yield h
+
+
 def overlap(set1: RepertoireSet, set2: RepertoireSet, opt: Options):
     """Convenience: the whole path once; returns (cells as float64 in the
     reference's units, Stats)."""
-    with HipOverlap(opt) as h:
-        h.set_reference(set2, set1.longest)
-        h.set_queries(set1)
+    with _context(opt, None, set1, set2) as h:
         m = h.overlap_matrix_f64()
         return m, h.stats()
 
@@ -659,9 +620,7 @@ def deduplicate(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None)
     """Convenience: (merged_set, merged) -- `s` with every class of equal entries reduced to its first
     member, which carries the class's summed count (the reference's --deduplicate, dedup.cc).  `tunables`
     are set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         first, count, merged = h.deduplicate(s)
     out = s.subset(first)
     out.count = count
@@ -671,40 +630,28 @@ def deduplicate(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None)
 def cluster(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
     """Convenience: (label, size, n_clusters) of `s` under `opt` (HipOverlap.cluster) on a context of its
     own.  `tunables` are set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         return h.cluster(s)
 
 
 def cluster_table(s: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
     """Convenience: (cluster_of, cluster_start, members, count) of `s` under `opt` (HipOverlap.cluster_table) on
     a context of its own.  `tunables` are set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         return h.cluster_table(s)
 
 
 def neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
     """Convenience: (row_start, hits) of set1 against set2 under `opt` (HipOverlap.neighbors) on a context of
     its own.  `tunables` are set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
-        h.set_reference(set2, set1.longest)
-        h.set_queries(set1)
+    with _context(opt, tunables, set1, set2) as h:
         return h.neighbors()
 
 
 def neighbors_distance(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
     """Convenience: (row_start, hits, distance) of set1 against set2 under `opt` (HipOverlap.neighbors_distance)
     on a context of its own.  `tunables` are set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
-        h.set_reference(set2, set1.longest)
-        h.set_queries(set1)
+    with _context(opt, tunables, set1, set2) as h:
         return h.neighbors_distance()
 
 
@@ -713,9 +660,7 @@ def hamming_matrix(set1: RepertoireSet, set2: RepertoireSet, opt: Options, diffe
     """Convenience: the matrix of set1 against set2 at any `differences` (HipOverlap.hamming_matrix) on a context
     of its own; `opt.differences` plays no part.  `tunables` are set on the context first (the result never
     depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         return h.hamming_matrix(set1, set2, differences)
 
 
@@ -724,9 +669,7 @@ def hamming_neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, di
     """Convenience: (row_start, hits, distance) of set1 against set2 at any `differences`
     (HipOverlap.hamming_neighbors) on a context of its own; `opt.differences` plays no part.  `tunables` are set on
     the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         return h.hamming_neighbors(set1, set2, differences, distances)
 
 
@@ -734,9 +677,7 @@ def hamming_cluster(s: RepertoireSet, opt: Options, differences: int, tunables: 
     """Convenience: (label, size, n_clusters) of `s` at any `differences` (HipOverlap.hamming_cluster) on a context
     of its own; `opt.differences` plays no part.  `tunables` are set on the context first (the result never depends
     on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         return h.hamming_cluster(s, differences)
 
 
@@ -744,18 +685,12 @@ def hamming_cluster_table(s: RepertoireSet, opt: Options, differences: int, tuna
     """Convenience: (cluster_of, cluster_start, members, count) of `s` at any `differences`
     (HipOverlap.hamming_cluster_table) on a context of its own; `opt.differences` plays no part.  `tunables` are
     set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
+    with _context(opt, tunables) as h:
         return h.hamming_cluster_table(s, differences)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):
     """Convenience: (row_start, repertoire, value) of set1 against set2 under `opt` (HipOverlap.existence_csr) on
     a context of its own.  `tunables` are set on the context first (the result never depends on them)."""
-    with HipOverlap(opt) as h:
-        for name, value in (tunables or {}).items():
-            h.set_tunable(name, value)
-        h.set_reference(set2, set1.longest)
-        h.set_queries(set1)
+    with _context(opt, tunables, set1, set2) as h:
         return h.existence_csr()

@@ -21,7 +21,7 @@ HOST_HDR = $(wildcard compairr_amd/host/*.h) include/compairr_hip.h
 KERN_DIR = compairr_amd/csrc
 KERN_HDR = $(KERN_DIR)/kernels.h $(KERN_DIR)/kernels_sliced.h $(KERN_DIR)/kernels_rows.h \
            $(KERN_DIR)/kernels_pairs2.h \
-           $(KERN_DIR)/layout.h $(KERN_DIR)/link_forest.h $(KERN_DIR)/select.h $(KERN_DIR)/context.h $(KERN_DIR)/csr_rows.h include/compairr_hip.h
+           $(KERN_DIR)/layout.h $(KERN_DIR)/lds_map.h $(KERN_DIR)/link_forest.h $(KERN_DIR)/select.h $(KERN_DIR)/context.h $(KERN_DIR)/csr_rows.h include/compairr_hip.h
 OBJ_DIR  = compairr_amd/lib/obj
 # the probe kernels are instantiated per (kernel variant, waves per workgroup) in
 # their own translation units, so that `make -j` compiles them side by side

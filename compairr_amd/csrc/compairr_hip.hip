@@ -786,35 +786,30 @@ int make_plan(cmpr_context *c)
   if (c->sliced && !c->rows && !c->waves_per_block_forced && c->nchunks > 0 &&
       (uint64_t)(c->ntiles - c->nsmall) < 6ull * c->nchunks)
     nw = 4;
+  const uint32_t lds_cells = P.lds_matrix ? (uint32_t)cells : 0u;      /* (lds_matrix: <= 2048 cells) */
   auto lds_for = [&](int waves) -> size_t {
-    const size_t zrow = c->rows ? (size_t)zs_of((int)A, c->opt.differences == 2 ? 2 : 1, pair_rows(c))
-                                : c->sliced ? (size_t)(zrow_stride((int)A) + zdelta_entries((int)A))
-                                            : (size_t)A;
-    size_t b = zrow * c->zpos * sizeof(uint64_t) +
-               (P.lds_matrix && !c->rows ? cells * sizeof(unsigned long long) : 0) +
-               (size_t)waves * sizeof(WaveQueue);
-    if (c->rows)
-      b += RING * (size_t)c->geom.rw_words * ROW_WORD_BYTES + MAX_CLASS_RES * A * sizeof(uint32_t) +
-           (c->opt.indels ? HEAVY_WORDS * sizeof(uint32_t) : 0) +
-           RING * (sizeof(RingSlot) + (size_t)c->chunk_cap * sizeof(TileRef)) +
-           (c->rec_tiles && !c->opt.ignore_genes ? ((size_t)c->opt.n_v_genes + c->opt.n_j_genes) * sizeof(uint64_t) : 0) +
-           (c->rec_tiles && c->opt.indels ? (size_t)c->geom.off_cr * sizeof(uint32_t) : 0);
-    else if (c->sliced)
-      b += ((size_t)1 << c->geom.words_log2) * sizeof(uint64_t) +
-           MAX_CLASS_RES * A * sizeof(uint32_t) + HEAVY_WORDS * sizeof(uint32_t) + 16 +
-           (size_t)c->chunk_cap * sizeof(TileRef);
-    return b;
+    if (c->rows)      /* (gene keys and class tables: what record tiles read) */
+      return rows_lds_map((uint32_t)A, zs_of((int)A, c->opt.differences == 2 ? 2 : 1, pair_rows(c)), c->zpos,
+                          (uint32_t)waves, c->geom.rw_words, c->opt.indels != 0, c->chunk_cap,
+                          c->rec_tiles && !c->opt.ignore_genes ? (uint32_t)(c->opt.n_v_genes + c->opt.n_j_genes) : 0u,
+                          c->rec_tiles && c->opt.indels ? c->geom.off_cr : 0u).bytes;
+    if (c->sliced)
+      return sliced_lds_map((uint32_t)A, c->zpos, (uint32_t)waves, c->geom.words_log2, lds_cells, c->chunk_cap).bytes;
+    return direct_lds_map((uint32_t)A, c->zpos, (uint32_t)waves, lds_cells).bytes;
+  };
+  /* variant 2 with deferred resolve: the second kernel of the step */
+  auto plan_resolve = [&]() {
+    S.rlds = resolve_lds_map(BLOCK_THREADS / WAVE, lds_cells).bytes;
+    /* 5 waves/SIMD fit its registers; a multiple of the segment count */
+    uint32_t rgrid = (uint32_t)c->cus * (uint32_t)c->resolve_blocks_per_cu;
+    S.rgrid = std::max<uint32_t>(1, rgrid / P.pos_segments) * P.pos_segments;
+    S.rfn = select_resolve(!c->opt.ignore_genes);
   };
   if (c->d2pairs) {
     /* kernels_pairs2.h: one workgroup of 16 waves per CU, two slice buffers */
     nw = 16;
-    const size_t npairs = ((size_t)c->zpos + 1) / 2;
-    const size_t lds2 = (size_t)c->geom.nbuf * c->geom.rw_words * ROW_WORD_BYTES +
-                        (16 * (size_t)c->zpos + P2_PZ * npairs) * sizeof(uint64_t) +
-                        (P.lds_matrix ? cells * sizeof(unsigned long long) : 0) + 16 * sizeof(WaveQueue) +
-                        MAX_CLASS_RES * A * sizeof(uint32_t) + 2 * sizeof(P2Slot) +
-                        2 * (size_t)c->chunk_cap * sizeof(TileRef);
-    if (lds2 > 160 * 1024)
+    const size_t lds2 = pairs2_lds_map(c->zpos, 16, c->geom.nbuf, c->geom.rw_words, lds_cells, c->chunk_cap).bytes;
+    if (lds2 > LDS_BYTES)
       return fail(c, CMPR_EUNSUPPORTED, "the pair-row kernel of d = 2 does not fit the 160 KiB LDS");
     ProbeFn fn = select_probe_pairs2(!c->opt.ignore_genes);
     if ((rc = raise_lds_limit(c, (const void *)fn, lds2))) return rc;
@@ -824,22 +819,17 @@ int make_plan(cmpr_context *c)
     S.grid = (uint32_t)grid;
     S.nw = 16;
     S.lds = lds2;
-    if (S.deferred) {
-      S.rlds = (BLOCK_THREADS / WAVE) * sizeof(CandQueue) +
-               (P.lds_matrix ? cells * sizeof(unsigned long long) : 0);
-      uint32_t rgrid = (uint32_t)c->cus * (uint32_t)c->resolve_blocks_per_cu;
-      S.rgrid = std::max<uint32_t>(1, rgrid / P.pos_segments) * P.pos_segments;
-      S.rfn = select_resolve(!c->opt.ignore_genes);
-    }
+    if (S.deferred)
+      plan_resolve();
     S.valid = true;
     return CMPR_OK;
   }
   size_t lds = lds_for(nw);
-  while (lds > 160 * 1024 && c->sliced && nw > 4) {
+  while (lds > LDS_BYTES && c->sliced && nw > 4) {
     nw /= 2;                             /* long sequences: fewer wave queues */
     lds = lds_for(nw);
   }
-  if (lds > 160 * 1024)
+  if (lds > LDS_BYTES)
     return fail(c, CMPR_EUNSUPPORTED,
                 "sequences too long: Zobrist table does not fit the 160 KiB LDS");
   P.chunk_cap = c->chunk_cap;
@@ -854,7 +844,7 @@ int make_plan(cmpr_context *c)
     return fail(c, CMPR_EUNSUPPORTED, "no kernel for this layout (class residues)");
   if ((rc = raise_lds_limit(c, (const void *)fn, lds))) return rc;
   /* resident workgroups per CU: LDS- and wave-limited, at most the tunable */
-  uint64_t per_cu = std::min<uint64_t>((160 * 1024) / lds, 32 / (uint64_t)nw);
+  uint64_t per_cu = std::min<uint64_t>(LDS_BYTES / lds, 32 / (uint64_t)nw);
   if (c->rows || direct) {
     /* variant 2 deals its chunks out statically over the workgroups of the grid:
        exactly as many as are resident at once (registers count too); so does the d = 0
@@ -873,14 +863,8 @@ int make_plan(cmpr_context *c)
   S.grid = (uint32_t)grid;
   S.nw = (uint32_t)nw;
   S.lds = lds;
-  if (S.deferred) {
-    S.rlds = (BLOCK_THREADS / WAVE) * sizeof(CandQueue) +
-             (P.lds_matrix ? cells * sizeof(unsigned long long) : 0);
-    /* 5 waves/SIMD fit its registers; a multiple of the segment count */
-    uint32_t rgrid = (uint32_t)c->cus * (uint32_t)c->resolve_blocks_per_cu;
-    S.rgrid = std::max<uint32_t>(1, rgrid / P.pos_segments) * P.pos_segments;
-    S.rfn = select_resolve(!c->opt.ignore_genes);
-  }
+  if (S.deferred)
+    plan_resolve();
   if (S.redo_kind) {
     /* the redo pass (issue_step) */
     S.fn2 = select_rows_kernel(c->opt, nw, true, wide);

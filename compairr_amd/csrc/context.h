@@ -318,7 +318,7 @@ struct cmpr_context {
   /* what the runtime said about a kernel with a given dynamic LDS size (asked once: a plan is made per query
      set): workgroups per CU, and whether its LDS limit has been raised */
   std::map<std::pair<const void *, size_t>, int> occupancy_seen;
-  std::set<std::pair<const void *, size_t>>      lds_raised;
+  std::map<const void *, size_t>                 lds_raised;     /* per function: the largest limit set */
   void                      *h_sizes = nullptr;           /* pinned: the layout's SizesBlock arrives here */
   size_t                     h_sizes_bytes = 0;
   hipEvent_t                 ev_layout[6] = {};
@@ -484,13 +484,15 @@ int dev_upload(cmpr_context *c, DevBuf<T> &b, const T *src, size_t n)
   return CMPR_OK;
 }
 
-/* hipFuncSetAttribute(MaxDynamicSharedMemorySize) / hipOccupancyMaxActiveBlocksPerMultiprocessor, remembered */
+/* hipFuncSetAttribute(MaxDynamicSharedMemorySize) / hipOccupancyMaxActiveBlocksPerMultiprocessor, remembered.
+   The attribute of a function only ever grows: set when a request exceeds the largest so far, never lowered */
 inline int raise_lds_limit(cmpr_context *c, const void *fn, size_t lds)
 {
-  if (lds <= 48 * 1024 || c->lds_raised.count({fn, lds}))
+  size_t &raised = c->lds_raised[fn];
+  if (lds <= 48 * 1024 || lds <= raised)
     return CMPR_OK;
   HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  c->lds_raised.insert({fn, lds});
+  raised = lds;
   return CMPR_OK;
 }
 

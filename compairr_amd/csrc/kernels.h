@@ -26,7 +26,7 @@
 #define COMPAIRR_AMD_KERNELS_H
 
 #include <hip/hip_runtime.h>
-#include "layout.h"
+#include "lds_map.h"
 #include "link_forest.h"
 
 namespace cmpr {
@@ -267,15 +267,7 @@ pack_records_kernel(const PackParams B)
 /* probe kernel                                                         */
 /* ------------------------------------------------------------------ */
 
-constexpr int QCAP = 2 * WAVE;      /* per-wave queue of Bloom positives   */
-
-struct WaveQueue {
-  uint64_t hash[QCAP];
-  uint32_t slot[QCAP];   /* query: tile * 64 + lane                          */
-  uint32_t ca[QCAP];     /* kind | p1 << 3 | r1 << 24                        */
-  uint32_t cb[QCAP];     /* p2 | r2 << 24                                    */
-  uint32_t m[QCAP];      /* variant 2 (kernels_rows.h q_push): the entry's mask of positive variants */
-};
+/* (the per-wave queue of Bloom positives, WaveQueue: lds_map.h) */
 
 __device__ __forceinline__ uint32_t pack_a(uint32_t kind, uint32_t p1, uint32_t r1)
 {
@@ -460,14 +452,7 @@ __device__ __forceinline__ void resolve_entry(const ProbeParams &P, const WaveQu
 
 /* ---- deferred mode: resolve_kernel -------------------------------------- */
 
-/* (query, variant, set-2 sequence) triples whose table key equals the variant
-   hash, waiting for verification -- one queue per wave, in LDS */
-struct CandQueue {
-  uint32_t slot[QCAP], ca[QCAP], cb[QCAP];
-  uint32_t tagb[QCAP];                 /* the key's bucket | its tag << 17 ... (see verify_candidate) */
-  uint32_t piece[QCAP];                /* the table slot to look at */
-  uint32_t bucket[QCAP];
-};
+/* (CandQueue, the candidates waiting for verification -- one queue per wave, in LDS: lds_map.h) */
 
 /* n low bytes set (n <= 0: none, n >= 4: all) */
 __device__ __forceinline__ uint32_t low_bytes(int n)
@@ -704,7 +689,7 @@ template <bool GENES>
 __global__ void __launch_bounds__(BLOCK_THREADS, 4)      /* <= 128 VGPRs: 4 waves per SIMD */
 resolve_kernel(const ProbeParams P)
 {
-  extern __shared__ __align__(16) unsigned char smem[];
+  extern __shared__ __align__(16) unsigned char smem[];       /* ResolveLds (lds_map.h) */
   CandQueue &cq = ((CandQueue *)smem)[threadIdx.x / WAVE];
   unsigned long long *mat_lds =
       (unsigned long long *)(smem + (BLOCK_THREADS / WAVE) * sizeof(CandQueue));
@@ -847,8 +832,7 @@ __device__ __forceinline__ void probe(Prober &W, uint64_t hv, bool live,
  * A: alphabet (20 aa / 4 nt); D: differences 0..2; INDELS: -i (D == 1);
  * GENES: V/J hashed and compared (no -g).
  *
- * LDS: [A * zpos Zobrist position keys][R1 * R2 matrix (optional)]
- *      [one WaveQueue per wave]
+ * LDS: DirectLds (lds_map.h); the casts below walk its regions in its order.
  *
  * The replacement-residue loops are deliberately NOT unrolled: each probe()
  * site carries an inlined queue drain, and memory-level parallelism comes
@@ -885,7 +869,6 @@ probe_kernel(const ProbeParams P)
 
   /* d = 0: every tile is the same work, dealt out statically (one counter for 4 x 10^5 tiles
      would serialise the launch); the wave's queue holds the walks that go on (CandQueue) */
-  static_assert(sizeof(CandQueue) <= sizeof(WaveQueue), "the d = 0 kernel keeps a CandQueue where the others keep a WaveQueue");
   CandQueue &cq = *(CandQueue *)&queues[wave];
   int cqn = 0;
   if (D == 0) {

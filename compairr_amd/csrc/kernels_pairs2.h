@@ -52,7 +52,7 @@ namespace cmpr {
  */
 constexpr uint32_t K2_CROSS = 5, K2_SAME = 6;
 constexpr uint32_t P2_NONE = 4;                  /* "no residue": the second position of a pair behind the end */
-constexpr uint32_t P2_PZ = 20;                   /* pair-blank keys per pair: (qa, qb) -> qa | qb << 2; 16 + qa: no second position */
+/* (P2_PZ, the pair-blank keys per pair: lds_map.h) */
 __device__ __forceinline__ uint32_t p2_pz_index(uint32_t qa, uint32_t qb)
 {
   return qb >= 4u ? 16u + qa : qa | (qb << 2);
@@ -210,15 +210,7 @@ __device__ __forceinline__ uint32_t p2_pair_of(const ResPack &pk, uint32_t j)
   return (w >> ((j & 7u) * 4u)) & 15u;
 }
 
-/*
- * LDS: [1 or 2 slice buffers, rw_words x 32 B each][ze: 16 x zpos][pz: P2_PZ x ceil(zpos / 2)]
- *      [NW WaveQueues][CR tables][2 x {chunk descriptor, unit counter}][2 x chunk_cap tile refs]
- */
-struct P2Slot {
-  uint32_t slice, first, ntiles, pass;
-  uint32_t next_unit, units, pad[2];
-};
-
+/* LDS: Pairs2Lds (lds_map.h, with P2Slot); the casts in the kernel walk its regions in its order. */
 template <bool GENES, int NW>
 __global__ void __launch_bounds__(NW * WAVE, 4)
 probe_pairs2_kernel(const ProbeParams P)

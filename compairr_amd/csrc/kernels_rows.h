@@ -340,14 +340,7 @@ template <int A> struct RowCfg {
   static constexpr uint32_t RBITS = A == 20 ? 5u : 2u;
 };
 
-/* keys per position of the kernel's LDS copy of the Zobrist table: d = 2 stores a row twice
-   (rotated reads); pair rows add a ZERO key for code A -- the residue code the layout pads
-   a query with behind its end (query_layout.hip fill_tiles_kernel), so that a pair that
-   hangs over the end hashes, and reads, without a test */
-__host__ __device__ constexpr uint32_t zs_of(int A, int D, bool pairs)
-{
-  return D == 2 ? 2u * (uint32_t)A : (pairs ? (uint32_t)A + 1u : (uint32_t)A);
-}
+/* (keys per position of the kernel's LDS copy of the Zobrist table, zs_of: lds_map.h) */
 
 /* ------------------------------------------------------------------ */
 /* the per-wave queue of this kernel holds ENTRIES, not variants        */
@@ -571,11 +564,9 @@ __device__ __forceinline__ void q_push(SProber &W, uint32_t zl_addr, bool pos, u
  * are copied at once, and no wave idles at the end of a chunk while another still
  * works on it.
  *
- * LDS: [RING slices, rw_words x 32 B each][ZS x zpos Zobrist keys]
- *      [NW WaveQueues][CR tables][heavy bitmap (-i)]
- *      [RING ring slots][RING x chunk_cap tile refs]
+ * LDS: RowsLds (lds_map.h, with RING and RingSlot, one buffer of the ring); the casts in the
+ * kernel walk its regions in its order.
  */
-constexpr uint32_t RING = 4;
 constexpr uint32_t RING_END = 0xffffffffu;
 /* blocks of 64 items a wave takes with one claim: an item is one row, and claiming,
    descriptor and address arithmetic of a unit cost ~3 rows' worth of instructions */
@@ -595,21 +586,6 @@ constexpr uint32_t ITEM_BLOCKS = 4;
 #endif
 enum { PT_CLAIM = 0, PT_TILE_DATA = 1, PT_ROWS = 2, PT_EMIT = 3, PT_OTHER = 4, PT_LOADER_WAIT = 5,
        PT_LOADER_DMA = 6, PT_TAIL = 7 };
-
-/* one buffer of the ring */
-struct RingSlot {
-  /* tag << 32 | ntiles << 16 | tiles handed out: claimed with ONE 64-bit LDS add,
-     so that a claim names the tenant it belongs to; tag 0 = nothing yet, tags
-     grow by one per tenant, RING_END = no more chunks */
-  unsigned long long claim;
-  uint32_t done;             /* tiles of the tenant finished */
-  uint32_t slice, pass;
-  uint32_t first;            /* class-row chunk: its first item (blocks of 64 items, no tile refs) */
-  uint32_t pad[2];           /* ([0] of slot 0: the workgroup's staging counter; [0] of slot 1: buffers whose
-                                chain of tenants has ended; [1]: item chunk: its blocks) */
-  uint32_t next_chunk;       /* the chunk of the tenant after this one (P.deal: reserved when this one was staged) */
-  uint32_t page;             /* the page of its slice the tenant holds | e of the slice << 4 (layout.h SliceGeom; 0: no pages) */
-};
 
 
 /* (16 waves = 1024 lanes is the largest workgroup there is: five waves per SIMD would take two

@@ -458,11 +458,7 @@ struct ResStream {
   }
 };
 
-/*
- * LDS: [2^w-word Bloom slice][A * zpos Zobrist keys][R1 * R2 matrix (optional)]
- *      [NW WaveQueues][CR tables][heavy bitmap]
- *      [chunk broadcast][tile descriptors of the chunk]
- */
+/* LDS: SlicedLds (lds_map.h); the casts below walk its regions in its order. */
 template <int A, int D, bool INDELS, bool GENES, int NW>
 __global__ void __launch_bounds__(NW * WAVE, 4)
 probe_sliced_kernel(const ProbeParams P)

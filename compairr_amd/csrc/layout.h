@@ -7,6 +7,11 @@
 
 #include <stdint.h>
 
+#ifndef __HIPCC__                 /* plain C++ (lds_map.h, tests/test_lds_map_cpu.py) */
+#define __host__
+#define __device__
+#endif
+
 namespace cmpr {
 
 constexpr int      WAVE              = 64;

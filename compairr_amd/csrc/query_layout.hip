@@ -2407,10 +2407,11 @@ int cmpr_layout_queries(cmpr_context *c, const LayoutSource &src)
     /* the workgroup size that leaves the most waves per CU resident (both kernels: the same grid) */
     uint32_t best_waves = 0;
     int bk = 0, bs = 0;
+    const uint32_t LAYOUT_LDS_RESERVE = 512;       /* kept free for what the kernels declare statically */
     for (int w = 0; w < 3; w++) {
       const size_t own = (size_t)wg_sizes[w] * (4 * own_np + 1) * sizeof(uint32_t);
       const size_t kl = keys_shared + own, sl = scatter_shared + own;
-      if (kl > 160 * 1024 - 512 || sl > 160 * 1024 - 512)
+      if (kl > LDS_BYTES - LAYOUT_LDS_RESERVE || sl > LDS_BYTES - LAYOUT_LDS_RESERVE)
         continue;
       if ((rc = raise_lds_limit(c, (const void *)keys_fns[w], kl))) return rc;
       if ((rc = raise_lds_limit(c, (const void *)scatter_fns[w], sl))) return rc;
@@ -2430,7 +2431,7 @@ int cmpr_layout_queries(cmpr_context *c, const LayoutSource &src)
       }
     }
     if (best_waves == 0)
-      return fail(c, CMPR_EUNSUPPORTED, "the layout kernels' tables do not fit the 160 KiB LDS");
+      return fail(c, CMPR_EUNSUPPORTED, "the layout kernels' tables do not fit the " + std::to_string(LDS_BYTES / 1024) + " KiB LDS");
     if (getenv("COMPAIRR_HIP_DEBUG"))
       fprintf(stderr, "compairr_hip: layout kernels: workgroups of %u; keys %zu B of LDS, %d per CU; scatter %zu B, %d; "
                       "grid %u; %llu item counters in %u groups (%s)\n", LAYOUT_WG, keys_lds, bk, scatter_lds, bs,

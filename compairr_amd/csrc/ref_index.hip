@@ -325,20 +325,18 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
   uint64_t row_max_words = c->slice_words_log2 < 0
       ? MAX_ROW_SLICE_WORDS : std::min<uint64_t>(1ull << c->slice_words_log2, MAX_ROW_SLICE_WORDS);
   if (c->sliced) {
-    const size_t zrow = c->rows ? 2 * (size_t)A : (size_t)(zrow_stride((int)A) + zdelta_entries((int)A));
-    /* everything but the slice(s), with the fewest waves a workgroup may have */
-    /* (variant 2 keeps no copy of the matrix in LDS) */
-    const size_t fixed = zrow * c->zpos * sizeof(uint64_t) +
-                         4 * sizeof(WaveQueue) + (c->rows ? 0 : 2048 * sizeof(unsigned long long)) +
-                         MAX_CLASS_RES * A * sizeof(uint32_t) + HEAVY_WORDS * sizeof(uint32_t) + 16 +
-                         64 * sizeof(TileRef) + (c->rows ? RING * (sizeof(RingSlot) + 64 * sizeof(TileRef)) : 0);
+    /* what the kernels would take: the estimates of lds_map.h (its maps at worst-case arguments) */
+    auto rows_need = [&](uint32_t waves, uint64_t slice_words) -> size_t {
+      return rows_lds_estimate((uint32_t)A, c->zpos, waves, (uint32_t)slice_words);
+    };
+    auto pairs2_need = [&](uint64_t nbuf, uint64_t slice_words) -> size_t {
+      return pairs2_lds_estimate(c->zpos, (uint32_t)nbuf, (uint32_t)slice_words);
+    };
     size_t need_d2 = 0;
     if (c->rows && c->d2pairs) {
       /* kernels_pairs2.h: two slice buffers beside its tables, a matrix copy and 16 wave queues */
-      const size_t fixed2 = (16 * (size_t)c->zpos + 20 * ((size_t)c->zpos + 1) / 2) * sizeof(uint64_t) +
-                            2048 * sizeof(unsigned long long) + 16 * sizeof(WaveQueue) +
-                            MAX_CLASS_RES * A * sizeof(uint32_t) + 2 * (64 + 64 * sizeof(TileRef)) + 1024;
-      const size_t room = fixed2 < 160 * 1024 ? 160 * 1024 - fixed2 : 0;
+      const size_t fixed2 = pairs2_need(0, 0);           /* everything but the slices */
+      const size_t room = fixed2 < LDS_BYTES ? LDS_BYTES - fixed2 : 0;
       const uint64_t nbuf = c->d2_buffers == 1 ? 1 : 2;
       c->geom.nbuf = (uint32_t)nbuf;
       uint64_t w = room / (nbuf * ROW_WORD_BYTES);
@@ -348,21 +346,22 @@ int cmpr_build_reference(cmpr_context *c, const cmpr_set_view *s, uint32_t longe
         c->d2pairs = false;                              /* (Zobrist tables too large: single rows, or variant 1) */
       } else {
         row_max_words = c->slice_words_log2 < 0 ? w : std::min<uint64_t>(1ull << c->slice_words_log2, w);
-        need_d2 = fixed2 + nbuf * (size_t)row_max_words * ROW_WORD_BYTES;
+        need_d2 = pairs2_need(nbuf, row_max_words);
       }
     }
     if (c->rows && c->slice_words_log2 < 0 && !c->d2pairs) {
       /* the default slice leaves room for the queues of 16 waves; long sequences: a
          smaller slice next to the bigger Zobrist table */
-      const size_t fixed16 = fixed + 12 * sizeof(WaveQueue);
-      const size_t room = fixed16 < 160 * 1024 ? 160 * 1024 - fixed16 : 0;
+      const size_t fixed16 = rows_need(16, 0);
+      const size_t room = fixed16 < LDS_BYTES ? LDS_BYTES - fixed16 : 0;
       row_max_words = std::min<uint64_t>(row_max_words, room / (RING * ROW_WORD_BYTES));
       row_max_words -= row_max_words % 32;               /* whole KiB: LDS-DMA pieces */
     }
+    /* ... with the fewest waves a workgroup may have */
     const size_t need = c->rows && c->d2pairs ? need_d2
-                        : fixed + (c->rows ? RING * (size_t)row_max_words * ROW_WORD_BYTES
-                                           : ((size_t)8 << swl));
-    if (need > 160 * 1024 || (c->rows && row_max_words < 1)) {
+                        : c->rows ? rows_need(4, row_max_words)
+                                  : sliced_lds_estimate((uint32_t)A, c->zpos, (uint32_t)swl);
+    if (need > LDS_BYTES || (c->rows && row_max_words < 1)) {
       c->sliced = false;
       c->rows = false;
     }

@@ -9,9 +9,9 @@ no compute path of its own and no CPU fallback.
 
 from .sets import RepertoireSet  # noqa: F401
 from .hip import (HipOverlap, HipError, Options, Stats, cluster, cluster_table, deduplicate, existence_csr,  # noqa: F401
-                  hamming_cluster, hamming_cluster_table, hamming_matrix, hamming_neighbors, library_path, neighbors,
-                  neighbors_distance)
+                  hamming_cluster, hamming_cluster_table, hamming_matrix, hamming_nearest, hamming_neighbors,
+                  library_path, neighbors, neighbors_distance)
 
 __all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "cluster_table", "deduplicate",
-           "existence_csr", "hamming_cluster", "hamming_cluster_table", "hamming_matrix", "hamming_neighbors",
-           "library_path", "neighbors", "neighbors_distance"]
+           "existence_csr", "hamming_cluster", "hamming_cluster_table", "hamming_matrix", "hamming_nearest",
+           "hamming_neighbors", "library_path", "neighbors", "neighbors_distance"]

@@ -2,8 +2,9 @@
  * hamming.hip -- the reference's all-against-all path for any d (process_trad, overlap.cc:286-359; seq_diff,
  * util.cc:172-184) as library calls that take the distance as an argument: cmpr_hamming_matrix / _device and
  * cmpr_hamming_neighbors / _device; and the reference's clusters on that path (process_trad, cluster.cc:165-211, swept by
- * cluster.cc:276-410): cmpr_hamming_cluster / _device and cmpr_hamming_cluster_table / _device.  A pair (i of set 1, j of
- * set 2) matches when the two sequences have one length
+ * cluster.cc:276-410): cmpr_hamming_cluster / _device and cmpr_hamming_cluster_table / _device; and the nearest neighbour
+ * of every sequence under that group relation, whatever its distance: cmpr_hamming_nearest / _device.  A pair (i of set 1,
+ * j of set 2) matches when the two sequences have one length
  * (two empty ones included), the same V and J gene numbers unless ignore_genes, and differ at no more than
  * `differences` positions.  Nothing is hashed: every query is compared with every sequence of its group.
  *
@@ -37,6 +38,15 @@
  *            reference lies a snapshot of its root; a lane keeps its own root in a register, skips a match whose
  *            snapshot equals it and looks its root up again after a link it made.  No count array, no pair list.
  *            What follows the launch is cluster.hip's: flatten, sizes, and for the table calls the table pass.
+ *            nearest (cmpr_hamming_nearest): no threshold -- a lane keeps the smallest distance so far, the POSITION in
+ *            the group of the first reference at it and the number of references at it: two compares and selects per
+ *            reference, nothing indexed by the distance.  A reference that is no candidate (below the floor, the
+ *            query itself in one-set mode, the query's own repertoire with the flag) takes part at an infinite
+ *            distance.  Position order is number order, so the first reference at the minimum is the one of the
+ *            smallest number, looked up in the group order once, at the end.  One segment: the lane writes its three
+ *            results.  Several: every (query, segment) writes a slot -- the 64-bit key (distance << 32 | number) and
+ *            the ties -- and hm_nearest_fold_kernel takes the smallest key of a query and sums the ties of the slots
+ *            at its distance.  Outputs and slots are set to "none" on the stream first: what no lane visits stays so.
  *
  * The (query, segment) count array has n1 x S words, S <= HM_MAX_SEGMENTS; the automatic S is above 1 only while
  * the query tiles alone do not fill the machine (S <= ceil(8 x CUs / workgroups)), which bounds it by
@@ -99,9 +109,20 @@ struct HmParams {
   /* link */
   uint32_t       *parent;          /* the forest, over original sequence numbers (link_forest.h) */
   uint32_t        snapshot;        /* 1: matches whose two root snapshots are equal are skipped */
+  /* nearest (rep1, rep2 as the matrix has them, read with other_rep only) */
+  uint32_t        floor;           /* a candidate differs at this many positions or more */
+  uint32_t        one_set;         /* 1: set 2 IS set 1, a query is no candidate of its own */
+  uint32_t        other_rep;       /* 1: a candidate comes from another repertoire than the query */
+  uint32_t       *nn_nearest;      /* one segment: the three results, each may be NULL */
+  uint16_t       *nn_dist;
+  uint32_t       *nn_ties;
+  unsigned long long *nn_key;      /* several: [n1 x segments] (distance << 32 | number), all ones: none */
+  uint32_t       *nn_slot_ties;    /* ... and the references of the segment at that distance */
 };
 
-enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2 };
+enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2, SINK_NEAREST = 3 };
+
+constexpr uint32_t HM_NONE = 0xffffffffu;      /* nearest sink: the infinite distance, and "no sequence" */
 
 /* differing residues of two packed words.  Amino acids: a byte each, codes below 0x80, so neither the xor nor the
    sum carries into the next byte and bit 7 says "this byte is not zero".  Nucleotides: two bits each. */
@@ -134,6 +155,8 @@ struct LaneSink {
   uint32_t cur_rep = 0;
   /* link: the root of the lane's query when it last looked */
   uint32_t root = 0;
+  /* nearest: the smallest distance so far, the position in the group of the first reference at it, how many at it */
+  uint32_t best = HM_NONE, bpos = 0, ties = 0;
 };
 
 /* NW: words per sequence held in registers (the group's stride), 0: the generic form */
@@ -143,7 +166,7 @@ hm_compare_kernel(const HmParams P)
 {
   __shared__ uint32_t st_words[HM_LDS_WORDS];
   __shared__ uint32_t st_id[HM_STAGE_MAX];
-  __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? HM_STAGE_MAX : 1];
+  __shared__ uint32_t st_rep[SINK == SINK_MATRIX || SINK == SINK_NEAREST ? HM_STAGE_MAX : 1];
   __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? HM_STAGE_MAX : 1];
   __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? HM_MAT_CELLS : 1];
   __shared__ uint32_t st_root[SINK == SINK_LINK ? HM_STAGE_MAX : 1];
@@ -198,7 +221,7 @@ hm_compare_kernel(const HmParams P)
   } else if (SINK == SINK_LINK) {
     if (P.snapshot)
       S.root = link_root(P.parent, qorig);
-  } else {
+  } else if (SINK == SINK_MATRIX) {
     S.row = P.existence ? (unsigned long long)qorig : (unsigned long long)P.rep1[qorig];
     S.f = P.cnt1 ? P.cnt1[qorig] : 1ull;
   }
@@ -244,8 +267,32 @@ hm_compare_kernel(const HmParams P)
       S.acc += P.cnt1 ? pair_score(P.score, S.f, st_cnt[r]) : 1ull;
     }
   };
+  /* nearest sink: the position in the group that is the lane's own query (one-set mode: the group is paired with
+     itself, as in the link sink) and the repertoire a candidate must not come from; HM_NONE is no position and no
+     repertoire */
+  const uint32_t nn_self = SINK == SINK_NEAREST && P.one_set ? qi : HM_NONE;
+  const uint32_t nn_rep = SINK == SINK_NEAREST && P.other_rep ? P.rep1[qorig] : HM_NONE;
+  /* the reference at position `pos` of the group, staged as r, differs at `dd` positions.  What is no candidate is
+     infinitely far; then (smaller: the first at it) and (equal: one more at it), as selects */
+  auto nearest = [&](uint32_t pos, uint32_t r, uint32_t dd) {
+    uint32_t rp = 0;                                                    /* (without the flag: not HM_NONE) */
+    if (P.other_rep)                                                    /* (the same for every lane) */
+      rp = st_rep[r];
+    const bool ok = (dd >= P.floor) & (pos != nn_self) & (rp != nn_rep);
+    const uint32_t de = ok ? dd : HM_NONE;
+    const bool lt = de < S.best;
+    S.ties = lt ? 1u : S.ties + (de == S.best ? 1u : 0u);              /* (the ties of "none" are dropped at the end) */
+    S.bpos = lt ? pos : S.bpos;
+    S.best = lt ? de : S.best;
+  };
   /* sequence numbers, repertoires and counts of the references e .. e + n - 1 of the group */
   auto stage_ids = [&](uint32_t e, uint32_t n) {
+    if (SINK == SINK_NEAREST) {                                         /* (the number is looked up once, at the end) */
+      if (P.other_rep)
+        for (uint32_t r = threadIdx.x; r < n; r += HM_WG)
+          st_rep[r] = P.rep2[P.ord2[pr.r0 + e + r]];
+      return;
+    }
     for (uint32_t r = threadIdx.x; r < n; r += HM_WG) {
       const uint32_t id = P.ord2[pr.r0 + e + r];
       st_id[r] = id;
@@ -283,7 +330,9 @@ hm_compare_kernel(const HmParams P)
           for (uint32_t k = 0; k < stride; k++)
             dd += diff_word<NT>(qw[k], w[k]);
         }
-        if (dd <= P.d && active && (SINK != SINK_LINK || e + r > qi))
+        if (SINK == SINK_NEAREST)
+          nearest(e + r, r, dd);
+        else if (dd <= P.d && active && (SINK != SINK_LINK || e + r > qi))
           sink(r, dd);
       }
     }
@@ -303,7 +352,9 @@ hm_compare_kernel(const HmParams P)
         for (uint32_t k = 0; k < m; k++)
           dd += diff_word<NT>(qw[k0 + k], st_words[k]);
       }
-      if (dd <= P.d && active && (SINK != SINK_LINK || e > qi))
+      if (SINK == SINK_NEAREST)
+        nearest(e, 0, dd);
+      else if (dd <= P.d && active && (SINK != SINK_LINK || e > qi))
         sink(0, dd);
     }
   }
@@ -319,8 +370,55 @@ hm_compare_kernel(const HmParams P)
         if (st_mat[k])
           atomicAdd(P.matrix + k, st_mat[k]);
     }
+  } else if (SINK == SINK_NEAREST) {
+    if (active) {
+      const bool none = S.best == HM_NONE;
+      const uint32_t id = none ? HM_NONE : P.ord2[pr.r0 + S.bpos];
+      const uint32_t ties = none ? 0u : S.ties;
+      if (P.segments == 1) {
+        if (P.nn_nearest)
+          P.nn_nearest[qorig] = id;
+        if (P.nn_dist)
+          P.nn_dist[qorig] = none ? (uint16_t)0xffffu : (uint16_t)S.best;
+        if (P.nn_ties)
+          P.nn_ties[qorig] = ties;
+      } else {
+        const uint64_t slot = (uint64_t)qorig * P.segments + seg;
+        P.nn_key[slot] = (unsigned long long)S.best << 32 | id;
+        P.nn_slot_ties[slot] = ties;
+      }
+    }
   }
 }
+
+/* the slots of a query folded: the smallest key, and the ties of the slots at its distance summed */
+__global__ void __launch_bounds__(HM_WG)
+hm_nearest_fold_kernel(const unsigned long long *key, const uint32_t *slot_ties, uint64_t n1, uint32_t segments,
+                       uint32_t *nearest, uint16_t *dist, uint32_t *ties)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * HM_WG + threadIdx.x;
+  if (i >= n1)
+    return;
+  unsigned long long best = ~0ull;
+  for (uint32_t s = 0; s < segments; s++)
+    best = min(best, key[i * segments + s]);
+  const uint32_t d = (uint32_t)(best >> 32);
+  uint32_t t = 0;
+  for (uint32_t s = 0; s < segments; s++)
+    t += (uint32_t)(key[i * segments + s] >> 32) == d ? slot_ties[i * segments + s] : 0u;
+  const bool none = d == HM_NONE;
+  if (nearest)
+    nearest[i] = none ? HM_NONE : (uint32_t)best;
+  if (dist)
+    dist[i] = none ? (uint16_t)0xffffu : (uint16_t)d;
+  if (ties)
+    ties[i] = none ? 0u : t;
+}
+
+/* 1 for a query that has a candidate (hipcub::TransformInputIterator over the finished ties) */
+struct HasTies {
+  __host__ __device__ unsigned long long operator()(uint32_t t) const { return t ? 1ull : 0ull; }
+};
 
 typedef void (*HmKernel)(const HmParams);
 
@@ -517,21 +615,23 @@ struct HmJob {
   std::vector<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> runs;   /* stride | first workgroup, workgroups */
 };
 
-/* what a call makes of the pairs: the clusters take no score, so what the reference refuses of scores is not theirs */
-enum HmKind { HM_MATRIX, HM_NEIGHBORS, HM_CLUSTERS };
+/* what a call makes of the pairs: the clusters and the nearest neighbours take no score, so what the reference refuses
+   of scores is not theirs.  HM_NEAREST: `differences` is the call's min_distance */
+enum HmKind { HM_MATRIX, HM_NEIGHBORS, HM_CLUSTERS, HM_NEAREST };
 
 int hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
                 int64_t differences, HmKind kind, bool on_device)
 {
   if (differences < 0)
-    return fail(c, CMPR_EINVAL, "Differences specified with -d or -differences cannot be negative.");
+    return fail(c, CMPR_EINVAL, kind == HM_NEAREST ? who + ": min_distance cannot be negative"
+                                                   : "Differences specified with -d or -differences cannot be negative.");
   if (c->opt.indels)
     return fail(c, CMPR_EINVAL, who + ": the all-against-all path has no indels");
   if (kind == HM_CLUSTERS && c->opt.existence)
     return fail(c, CMPR_EINVAL, "cmpr_cluster: clusters are not defined with options.existence");
   if (kind == HM_MATRIX && is_f64_score(c->opt))
     return fail(c, CMPR_EINVAL, who + ": ratio score needs cmpr_overlap_matrix_f64");
-  if (kind != HM_CLUSTERS && differences > 0 &&
+  if (kind != HM_CLUSTERS && kind != HM_NEAREST && differences > 0 &&
       (c->opt.score == CMPR_SCORE_MH || c->opt.score == CMPR_SCORE_JACCARD))
     return fail(c, CMPR_EINVAL, "The Morisita-Horn / Jaccard index is not defined when d>0");
   std::string why;
@@ -764,6 +864,98 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   return CMPR_OK;
 }
 
+/* cmpr_hamming_nearest*: one walk through the nearest sink, with several segments the fold of the slots behind it, and
+   the number of queries that found somebody counted over the finished ties */
+int hamming_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t min_distance,
+                         uint32_t flags, uint32_t *nearest_out, uint16_t *dist_out, uint32_t *ties_out,
+                         uint64_t *n_found_out, bool on_device)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  const std::string who = "cmpr_hamming_nearest";
+  if (n_found_out)
+    *n_found_out = 0;
+  int rc;
+  if ((rc = hm_refusals(c, who, set1, set2, min_distance, HM_NEAREST, on_device)))
+    return rc;
+  if (flags & ~(uint32_t)CMPR_NEAREST_OTHER_REPERTOIRE)
+    return fail(c, CMPR_EINVAL, who + ": unknown bits in flags");
+  const bool other_rep = (flags & CMPR_NEAREST_OTHER_REPERTOIRE) != 0;
+  if (other_rep && set2 != set1)
+    return fail(c, CMPR_EINVAL, who + ": CMPR_NEAREST_OTHER_REPERTOIRE needs set2 == set1 (two sets have two numberings "
+                                      "of their repertoires)");
+  auto t0 = std::chrono::steady_clock::now();
+  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
+  HmJob J;
+  if ((rc = hm_setup(c, who, set1, set2, 0, on_device, J)))
+    return rc;
+  c->hm_ms[0] = ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+
+  const uint64_t n1 = J.s1->n, S = J.P.segments;
+  if (n1 == 0)
+    return CMPR_OK;
+  Out<uint32_t> nearest(nearest_out, on_device);
+  Out<uint16_t> dist(dist_out, on_device);
+  Out<uint32_t> ties(ties_out, on_device);
+  if (nearest.wanted() && (rc = nearest.temp(c, (size_t)n1))) return rc;
+  if (dist.wanted() && (rc = dist.temp(c, (size_t)n1))) return rc;
+  if ((ties.wanted() || n_found_out) && (rc = ties.temp(c, (size_t)n1))) return rc;
+  HmParams &P = J.P;
+  P.rep1 = J.s1->rep.b.p; P.rep2 = J.s2->rep.b.p;
+  P.floor = (uint32_t)std::min<int64_t>(min_distance, 0x10000);        /* (no distance is above 65535) */
+  P.one_set = J.s2 == J.s1 ? 1u : 0u;
+  P.other_rep = other_rep ? 1u : 0u;
+  Tmp<unsigned long long> key, found;
+  Tmp<uint32_t> slot_ties;
+  Tmp<char> sum_tmp;
+  if (S == 1) {
+    /* "none" everywhere first: a query whose group set 2 lacks is no lane's */
+    if (nearest.p) HIP_TRY(c, hipMemsetAsync(nearest.p, 0xff, n1 * sizeof(uint32_t), c->stream));
+    if (dist.p) HIP_TRY(c, hipMemsetAsync(dist.p, 0xff, n1 * sizeof(uint16_t), c->stream));
+    if (ties.p) HIP_TRY(c, hipMemsetAsync(ties.p, 0, n1 * sizeof(uint32_t), c->stream));
+    P.nn_nearest = nearest.p; P.nn_dist = dist.p; P.nn_ties = ties.p;
+  } else {
+    /* ... nor is a (query, segment) whose range is empty: the fold writes every query from its slots */
+    if ((rc = dev_alloc(c, key.b, (size_t)(n1 * S)))) return rc;
+    if ((rc = dev_alloc(c, slot_ties.b, (size_t)(n1 * S)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(key.b.p, 0xff, n1 * S * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(slot_ties.b.p, 0, n1 * S * sizeof(uint32_t), c->stream));
+    P.nn_key = key.b.p; P.nn_slot_ties = slot_ties.b.p;
+  }
+  if ((rc = hm_launch<SINK_NEAREST>(c, J)))
+    return rc;
+  if (S > 1) {
+    hipLaunchKernelGGL(hm_nearest_fold_kernel, dim3(blocks_for(n1, HM_WG)), dim3(HM_WG), 0, c->stream,
+                       (const unsigned long long *)key.b.p, (const uint32_t *)slot_ties.b.p, n1, (uint32_t)S,
+                       nearest.p, dist.p, ties.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  unsigned long long n_found = 0;
+  if (n_found_out) {
+    hipcub::TransformInputIterator<unsigned long long, HasTies, const uint32_t *> has(ties.p, HasTies());
+    size_t sum_bytes = 0;
+    if ((rc = dev_alloc(c, found.b, 1))) return rc;
+    HIP_TRY(c, hipcub::DeviceReduce::Sum(nullptr, sum_bytes, has, found.b.p, (int)n1, c->stream));
+    if ((rc = dev_alloc(c, sum_tmp.b, sum_bytes))) return rc;
+    HIP_TRY(c, hipcub::DeviceReduce::Sum(sum_tmp.b.p, sum_bytes, has, found.b.p, (int)n1, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&n_found, found.b.p, sizeof n_found, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_found_out)
+    *n_found_out = n_found;
+  c->hm_ms[1] = ms_since(t0);
+  if (!on_device) {
+    t0 = std::chrono::steady_clock::now();
+    if (nearest.wanted() && (rc = nearest.copy_out(c, (size_t)n1))) return rc;
+    if (dist.wanted() && (rc = dist.copy_out(c, (size_t)n1))) return rc;
+    if (ties.wanted() && (rc = ties.copy_out(c, (size_t)n1))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->hm_ms[2] = ms_since(t0);
+  }
+  return CMPR_OK;
+}
+
 /* cmpr_hamming_cluster* and cmpr_hamming_cluster_table*: the set against itself through the link sink, then the
    flatten, size and table passes of cluster.hip.  The plain call (T == NULL) fills L's label / size, the table call
    T's four arrays from labels and sizes of nobody's. */
@@ -890,5 +1082,25 @@ extern "C" int cmpr_hamming_neighbors_device(cmpr_context *c, const cmpr_set_vie
   return guarded(c, [&] {
     return hamming_neighbors_impl(c, d_set1, d_set2, differences, capacity, d_row_start_out, d_hit_out,
                                   d_distance_out, n_edges_out, true);
+  });
+}
+
+extern "C" int cmpr_hamming_nearest(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                                    int64_t min_distance, uint32_t flags, uint32_t *nearest_out,
+                                    uint16_t *distance_out, uint32_t *ties_out, uint64_t *n_found_out)
+{
+  return guarded(c, [&] {
+    return hamming_nearest_impl(c, set1, set2, min_distance, flags, nearest_out, distance_out, ties_out, n_found_out,
+                                false);
+  });
+}
+
+extern "C" int cmpr_hamming_nearest_device(cmpr_context *c, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                           int64_t min_distance, uint32_t flags, uint32_t *d_nearest_out,
+                                           uint16_t *d_distance_out, uint32_t *d_ties_out, uint64_t *n_found_out)
+{
+  return guarded(c, [&] {
+    return hamming_nearest_impl(c, d_set1, d_set2, min_distance, flags, d_nearest_out, d_distance_out, d_ties_out,
+                                n_found_out, true);
   });
 }

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -668,6 +668,66 @@ int cmpr_hamming_cluster_table(cmpr_context *ctx, const cmpr_set_view *set, int6
 int cmpr_hamming_cluster_table_device(cmpr_context *ctx, const cmpr_set_view *d_set, int64_t differences,
                                       uint32_t *d_cluster_of_out, uint64_t *d_cluster_start_out,
                                       uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out);
+
+/*
+ * The nearest neighbour of every sequence, at ANY distance: the question the calls above cannot answer, because each of
+ * them takes a threshold -- and in repertoire analysis the threshold comes from the data: the histogram of the
+ * distances to the nearest neighbour is bimodal and the valley between its modes is the clonal threshold ("distance
+ * to nearest").  The group relation is that of process_trad (overlap.cc:286-359), the distance that of seq_diff
+ * (util.cc:172-184), as the rest of cmpr_hamming_*(); no `differences` limits it.
+ *
+ * The candidates of sequence i of set1 are the sequences j of set2 that
+ *   - have the same length as i (two empty sequences included) and the same V and J gene numbers unless
+ *     options.ignore_genes (overlap.cc:286-359);
+ *   - differ from i at `min_distance` or more positions: 0 admits everything, 1 leaves out the sequences with i's own
+ *     residues (the usual setting); negative is CMPR_EINVAL ("min_distance cannot be negative"); a value above the
+ *     longest sequence finds nobody;
+ *   - with set2 == set1 (the same pointer; the set is uploaded once) are not i itself: UNLIKE the calls above, the
+ *     (i, i) pair is NEVER a candidate.  Other sequences with i's residues are, at distance 0;
+ *   - with CMPR_NEAREST_OTHER_REPERTOIRE in `flags` come from another repertoire than i.  The flag is defined only
+ *     with set2 == set1 -- two sets have two numberings of their repertoires --: with two sets it is CMPR_EINVAL, and
+ *     so is any other bit of `flags`.
+ *
+ * cmpr_hamming_nearest() (overlap.cc:286-359) writes n1 elements of each output; any of them may be NULL:
+ *   distance_out[i]   the smallest distance D over the candidates of i.
+ *   nearest_out[i]    the smallest sequence number of set2 among the candidates at distance D.
+ *   ties_out[i]       the number of candidates at distance D.
+ * A sequence without a candidate gets nearest = 0xFFFFFFFF, distance = 0xFFFF and ties = 0.  nearest_out and ties_out
+ * are the authoritative test for "no candidate": validation admits sequences of 65535 residues, so 0xFFFF is also a
+ * possible distance.  Elements behind n1 are not written.
+ *   *n_found_out      a HOST pointer in both variants, may be NULL: the number of i that have a candidate.
+ * cmpr_hamming_nearest_device() (overlap.cc:286-359) takes DEVICE views and the three arrays as device memory on the
+ * context's device: nothing per sequence crosses PCIe.
+ *
+ * Both, as the rest of cmpr_hamming_*(): synchronous; callable any time after cmpr_create(); options.differences plays
+ * no part; the resident sets, plans and statistics are not disturbed; the sets are validated as every other set (same
+ * codes and texts, passed through unchanged); every temporary is freed on every return; results are bit-identical
+ * from run to run and under every tunable ((smallest distance, then smallest number) is a minimum, a tie count is an
+ * integer sum).  n1 == 0 or n2 == 0 is CMPR_OK with every i "none".  Refused before any device work, with the codes
+ * and texts of cmpr_hamming_neighbors(): options.indels, a NULL set, the tunable work_shard_count above 1,
+ * n_v_genes x n_j_genes above 2^46.  No score plays a part: MH, Jaccard, the ratio score and options.existence are
+ * NOT refused.  At most 2^31-1 sequences per set.
+ *
+ * How (compairr_amd/csrc/hamming.hip, the nearest sink of the compare kernel): one walk of the compare kernel, which
+ * computes the full distance of every pair of a group anyway.  A lane keeps three registers -- the smallest distance,
+ * the position in the group of the first reference at it, the number of references at it --, updated by two compares
+ * and selects per reference; a reference that is no candidate takes part at an infinite distance.  Position order in
+ * a group is number order (the stable sort), so the sequence number is looked up once, at the end.  With several
+ * segments every (query, segment) writes a slot and a small kernel folds them: the minimum of (distance << 32 |
+ * number), the ties of the slots at that distance summed.  Device memory for the duration of the call: the set copies,
+ * group order and packed words of cmpr_hamming_*() above, 12 bytes per (query, segment) when there are several
+ * segments, and in the host variant the 10 bytes per query of the outputs.
+ */
+enum { CMPR_NEAREST_OTHER_REPERTOIRE = 1 };
+
+int cmpr_hamming_nearest(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                         int64_t min_distance, uint32_t flags,
+                         uint32_t *nearest_out, uint16_t *distance_out, uint32_t *ties_out,
+                         uint64_t *n_found_out);
+int cmpr_hamming_nearest_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                int64_t min_distance, uint32_t flags,
+                                uint32_t *d_nearest_out, uint16_t *d_distance_out, uint32_t *d_ties_out,
+                                uint64_t *n_found_out);
 
 /*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP

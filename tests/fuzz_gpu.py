@@ -16,6 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
+import _ladder  # noqa: E402
 import _oracle  # noqa: E402
 from _routed import routed_contexts  # noqa: E402
 from compairr_amd import HipOverlap, Options, synth  # noqa: E402
@@ -27,7 +28,15 @@ def random_case(rng):
     tiny = rng.random() < 0.5
     n1 = int(rng.integers(1, 30000))
     n2 = int(rng.integers(1, 30000))
-    if tiny:
+    # now and then the two sets of tests/_ladder.py: a longest sequence at one of the lengths where the layout and
+    # the probe kernels change form (the synthetic sets end at 24 amino acids / 72 nucleotides)
+    ladder = rng.random() < 0.15
+    L = 0
+    if ladder:
+        L = int(rng.choice(_ladder.NT_LADDER if nt else _ladder.AA_LADDER))
+        a, b = _ladder.ladder_sets(L, nt, int(rng.integers(1 << 30)))
+        genes = dict(n_v_genes=_ladder.N_V, n_j_genes=_ladder.N_J)
+    elif tiny:
         letters = int(rng.integers(2, 5))
         max_len = int(rng.integers(3, 12))
         nrep = int(rng.integers(1, 5))
@@ -45,10 +54,12 @@ def random_case(rng):
                            nucleotides=nt, n_repertoires=int(rng.integers(1, 40)))
         genes = dict(n_v_genes=synth.N_V, n_j_genes=synth.N_J)
     d = int(rng.integers(0, 3))
+    if ladder and not nt and L > _ladder.AA_D2_MAX and d == 2:
+        d = 1                                             # oracle time
     indels = bool(d == 1 and rng.integers(0, 2))
-    if d == 2 and not tiny and not nt:
+    if d == 2 and not tiny and not nt and not ladder:
         a = a.subset(slice(0, min(a.n, 4000)))          # oracle time
-    if d == 2 and nt and not tiny:
+    if d == 2 and nt and not tiny and not ladder:
         a = a.subset(slice(0, min(a.n, 1500)))
     o = Options(differences=d, indels=indels, nucleotides=nt,
                 ignore_genes=bool(rng.integers(0, 2)), ignore_counts=bool(rng.integers(0, 2)),

@@ -22,13 +22,17 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
 
+import _ladder  # noqa: E402
 from compairr_amd import synth  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref", "compairr")
 REF_TEST = "/root/reference/test"
 INPUTS = os.path.join(HERE, "inputs")
 EXPECTED = os.path.join(HERE, "expected")
+
+LADDER_FILES = ((False, 33), (False, 37), (False, 29), (True, 129))      # (nucleotides, longest sequence)
 
 HDR = "repertoire_id\tsequence_id\tduplicate_count\tv_call\tj_call\tjunction\tjunction_aa\n"
 
@@ -116,6 +120,12 @@ def random_files():
                                            pool_size=200), False)
     out["rand_x_nt.tsv"] = (synth.make_set(200, 52, pool_seed=777, prefix="Q", n_repertoires=1,
                                            pool_size=80, nucleotides=True), True)
+    # sets whose longest sequence sits at a length where the layout and the probe kernels change form
+    # (tests/_ladder.py; tests/test_length_edges_gpu.py derives the lengths)
+    for nt, L in LADDER_FILES:
+        a, b = _ladder.ladder_sets(L, nt, L)
+        stem = "ladder_%s%d" % ("nt" if nt else "aa", L)
+        out[stem + "_a.tsv"], out[stem + "_b.tsv"] = (a, nt), (b, nt)
     return out
 
 
@@ -290,6 +300,12 @@ def cases():
     add("err_x_one_file", "-d 1", ["setc.tsv"], "exit 1", cmd="-x")
     add("err_x_mh", "-s MH", ["setc.tsv", "setb.tsv"], "exit 1", cmd="-x")
     add("err_x_no_sequence_id", "-d 1", ["noid.tsv", "crlf.tsv"], "exit 1", cmd="-x")
+    # (h) the product binary at the length edges: per-slot arrays and the tail of a reference record (33), a
+    #     query beyond its record (37), records hashed by the kernel (29), a nucleotide record's end (129)
+    add("ladder_aa33_d1i", "-d 1 -i", ["ladder_aa33_a.tsv", "ladder_aa33_b.tsv"])
+    add("ladder_aa37_d2", "-d 2", ["ladder_aa37_a.tsv", "ladder_aa37_b.tsv"])
+    add("p_ladder_aa29_d1", "-d 1", ["ladder_aa29_a.tsv", "ladder_aa29_b.tsv"], pairs=True)
+    add("ladder_nt129_d1", "-d 1 -n", ["ladder_nt129_a.tsv", "ladder_nt129_b.tsv"])
     return c
 
 
@@ -297,9 +313,12 @@ def main():
     if not os.path.exists(REF):
         sys.exit("build the reference first: make -C oracle ref")
     shutil.rmtree(INPUTS, ignore_errors=True)
-    shutil.rmtree(EXPECTED, ignore_errors=True)
     os.makedirs(INPUTS)
-    os.makedirs(EXPECTED)
+    os.makedirs(EXPECTED, exist_ok=True)
+    mine = {c["name"] for c in cases()}          # (expected/ also holds outputs recorded by other recipes: they stay)
+    for f in os.listdir(EXPECTED):
+        if f.replace(".pairs.tsv", "").replace(".tsv", "") in mine:
+            os.remove(os.path.join(EXPECTED, f))
     for f in ("seta.tsv", "setb.tsv", "setc.tsv"):
         shutil.copy(os.path.join(REF_TEST, f), os.path.join(INPUTS, f))
     for name, text in EDGE_FILES.items():

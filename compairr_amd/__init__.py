@@ -8,10 +8,11 @@ no compute path of its own and no CPU fallback.
 """
 
 from .sets import RepertoireSet  # noqa: F401
-from .hip import (HipOverlap, HipError, Options, Stats, cluster, cluster_table, deduplicate, existence_csr,  # noqa: F401
+from .hip import (HipOverlap, HipError, Options, Stats, cluster, cluster_table, deduplicate, edit_matrix,  # noqa: F401
+                  edit_neighbors, existence_csr,
                   hamming_cluster, hamming_cluster_table, hamming_matrix, hamming_nearest, hamming_neighbors,
                   library_path, neighbors, neighbors_distance)
 
 __all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "cluster_table", "deduplicate",
-           "existence_csr", "hamming_cluster", "hamming_cluster_table", "hamming_matrix", "hamming_nearest",
-           "hamming_neighbors", "library_path", "neighbors", "neighbors_distance"]
+           "edit_matrix", "edit_neighbors", "existence_csr", "hamming_cluster", "hamming_cluster_table", "hamming_matrix",
+           "hamming_nearest", "hamming_neighbors", "library_path", "neighbors", "neighbors_distance"]

@@ -318,6 +318,7 @@ struct Tunable {
 
 bool power_of_two(const cmpr_context *, int64_t v) { return (v & (v - 1)) == 0; }
 bool not_zero(const cmpr_context *, int64_t v) { return v != 0; }
+bool edit_words_ok(const cmpr_context *, int64_t v) { return v == 0 || v == 2 || v == 4; }
 bool class_res_fits(const cmpr_context *c, int64_t v) { return v <= (int64_t)max_class_res((uint32_t)c->opt.alphabet_size); }
 void force_waves(cmpr_context *c, int64_t) { c->waves_per_block_forced = true; }
 /* TEST ONLY: the next launch runs without redo pass as if the margin had been shown (tests/test_gpu_parity.py) */
@@ -368,6 +369,10 @@ const Tunable TUNABLES[] = {
   {"hamming_segments", F(hamming_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
   {"hamming_generic", F(hamming_generic), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
   {"hamming_link_snapshot", F(hamming_link_snapshot), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  /* TEST ONLY: the staging, the segments and the column words of cmpr_edit_* (edit.hip; tests/test_edit_gpu.py) */
+  {"edit_stage_refs", F(edit_stage_refs), 0, 65536, LOCK_NEVER, T_NO_PLAN, " must be 0..65536"},
+  {"edit_segments", F(edit_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
+  {"edit_words", F(edit_words), 0, 4, LOCK_NEVER, T_NO_PLAN, " must be 0 (from the length), 2 or 4", edit_words_ok},
   {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
   {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
   {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},
@@ -488,6 +493,10 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "hamming_group_us") *value = (int64_t)(c->hm_ms[0] * 1e3);
   else if (n == "hamming_compare_us") *value = (int64_t)(c->hm_ms[1] * 1e3);
   else if (n == "hamming_copy_us") *value = (int64_t)(c->hm_ms[2] * 1e3);
+  else if (n == "edit_group_us") *value = (int64_t)(c->ed_ms[0] * 1e3);
+  else if (n == "edit_compare_us") *value = (int64_t)(c->ed_ms[1] * 1e3);
+  else if (n == "edit_order_us") *value = (int64_t)(c->ed_ms[2] * 1e3);
+  else if (n == "edit_copy_us") *value = (int64_t)(c->ed_ms[3] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
   else if (n == "heavy_buckets") {
     *value = 0;

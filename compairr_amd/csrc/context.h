@@ -210,6 +210,9 @@ struct cmpr_context {
      segment count (0 = automatic), 1 = every group through the long-sequence form */
   int64_t hamming_stage_refs = 0, hamming_segments = 0, hamming_generic = 0;
   int64_t hamming_link_snapshot = 1;  /* TEST ONLY, of cmpr_hamming_cluster*: 0 = every match goes to link_pair */
+  /* TEST ONLY, of cmpr_edit_* (edit.hip): references staged per LDS piece (0 = as many as fit), the segment count
+     (0 = automatic), at least this many 64-bit words per column (0 = from the reference's length) */
+  int64_t edit_stage_refs = 0, edit_segments = 0, edit_words = 0;
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */
@@ -354,6 +357,7 @@ struct cmpr_context {
   double              ex_ms[5] = {};   /* ... of the last cmpr_existence_csr: edges | group | count | reduce | copy-out */
   double              cl_ms[2] = {};   /* ... of the last cmpr_cluster_table: labels and sizes | the table */
   double              hm_ms[3] = {};   /* ... of the last cmpr_hamming_*: upload, groups, packing | compare | copy-out */
+  double              ed_ms[4] = {};   /* ... of the last cmpr_edit_*: upload, groups, packing, jobs | compare | row order | copy-out */
 };
 
 

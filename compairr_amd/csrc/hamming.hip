@@ -52,7 +52,7 @@
  * the query tiles alone do not fill the machine (S <= ceil(8 x CUs / workgroups)), which bounds it by
  * 256 x (8 x CUs + workgroups) words.  Nothing here writes the resident sets, plans or statistics of the context.
  */
-#include "context.h"
+#include "hamming_sets.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -73,13 +73,6 @@ constexpr uint32_t HM_MAT_CELLS = 1024;        /* a matrix of up to this many ce
 constexpr uint32_t HM_MAX_SEGMENTS = 64;
 constexpr uint32_t HM_LINK_SEGMENT = 16384;    /* link sink: references of the longest automatic segment (32 pieces) */
 constexpr uint32_t AA_PER_WORD = 4, NT_PER_WORD = 16;
-
-/* a group of one set: the sequences at positions start .. start + count - 1 of the sorted order */
-struct HmGroup {
-  uint64_t pk_off;                 /* first packed word of the group */
-  uint32_t start, count;
-  uint32_t stride, len;            /* words per sequence; residues per sequence */
-};
 
 /* a group of set 1 and the group of set 2 with the same key */
 struct HmPair {
@@ -133,16 +126,6 @@ __device__ __forceinline__ uint32_t diff_word(uint32_t a, uint32_t b)
   if (NT)
     return (uint32_t)__popc((x | (x >> 1)) & 0x55555555u);
   return (uint32_t)__popc((x + 0x7f7f7f7fu) & 0x80808080u);
-}
-
-__device__ __forceinline__ unsigned long long pair_score(uint32_t score, unsigned long long f, unsigned long long g)
-{
-  switch (score) {
-  case CMPR_SCORE_MIN: case CMPR_SCORE_JACCARD: return f < g ? f : g;
-  case CMPR_SCORE_MAX:                          return f > g ? f : g;
-  case CMPR_SCORE_MEAN:                         return f + g;             /* 2 x mean */
-  default:                                      return f * g;             /* product, MH */
-  }
 }
 
 /* what a lane keeps of its matches */
@@ -439,9 +422,11 @@ HmKernel hm_kernel_for(uint32_t nw)
   }
 }
 
+}  // namespace
+
 /* words per sequence of a group of `len` residues: the next word count the register form is compiled for, or the
-   words themselves beyond HAMMING_REG_WORDS */
-uint32_t stride_of(uint32_t len, uint32_t per_word)
+   words themselves beyond HAMMING_REG_WORDS (hamming_sets.h) */
+uint32_t cmpr::stride_of(uint32_t len, uint32_t per_word)
 {
   const uint32_t w = std::max<uint32_t>(1, (len + per_word - 1) / per_word);
   static const uint32_t forms[] = {1, 2, 3, 4, 5, 6, 8, 12, HAMMING_REG_WORDS};
@@ -450,6 +435,8 @@ uint32_t stride_of(uint32_t len, uint32_t per_word)
       return f;
   return w;
 }
+
+namespace {
 
 /* ---- grouping and packing ---- */
 
@@ -474,7 +461,7 @@ hm_key_kernel(const KeyParams K)
   K.num[i] = (uint32_t)i;
 }
 
-struct PackParams {
+struct HmPackParams {
   const HmGroup  *groups;
   uint32_t        ngroups, per_word, bits;
   const uint8_t  *res;
@@ -486,7 +473,7 @@ struct PackParams {
 
 /* one thread per packed word: its group by the word offsets, its sequence and its place in it from there */
 __global__ void __launch_bounds__(HM_WG)
-hm_pack_kernel(const PackParams K)
+hm_pack_kernel(const HmPackParams K)
 {
   const uint64_t w = (uint64_t)blockIdx.x * HM_WG + threadIdx.x;
   if (w >= K.words)
@@ -519,15 +506,10 @@ hm_rows_kernel(const unsigned long long *offs, uint64_t n1, uint32_t segments, u
     row_start[i] = offs[i * segments];
 }
 
-/* a set on the device, validated, grouped and packed */
-struct HmSet : StagedSet {
-  Tmp<uint32_t> ord, pk;
-  std::vector<uint64_t> keys;      /* of the groups, increasing */
-  std::vector<HmGroup>  groups;
-};
+}  // namespace
 
-/* the staged set H grouped and packed */
-int hm_prepare(cmpr_context *c, HmSet &H)
+/* the staged set H grouped and packed (hamming_sets.h) */
+int cmpr::hm_prepare(cmpr_context *c, HmSet &H)
 {
   int rc;
   if (H.n == 0)
@@ -598,34 +580,21 @@ int hm_prepare(cmpr_context *c, HmSet &H)
   Tmp<HmGroup> d_groups;
   if ((rc = dev_upload(c, d_groups.b, H.groups.data(), H.groups.size()))) return rc;
   if ((rc = dev_alloc(c, H.pk.b, (size_t)words))) return rc;
-  PackParams Q{d_groups.b.p, G, per_word, 32 / per_word, H.res.b.p, H.off.b.p, H.ord.b.p, words, H.pk.b.p};
+  HmPackParams Q{d_groups.b.p, G, per_word, 32 / per_word, H.res.b.p, H.off.b.p, H.ord.b.p, words, H.pk.b.p};
   hipLaunchKernelGGL(hm_pack_kernel, dim3(blocks_for(words, HM_WG)), dim3(HM_WG), 0, c->stream, Q);
   HIP_TRY(c, hipGetLastError());
   HIP_TRY(c, hipStreamSynchronize(c->stream));             /* (d_groups and the sort's temporaries leave scope) */
   return CMPR_OK;
 }
 
-/* what the four entry points share: the refusals, both sets on the device, the pairs of groups */
-struct HmJob {
-  HmSet          own1, own2;
-  HmSet         *s1 = nullptr, *s2 = nullptr;
-  Tmp<HmPair>    pairs;
-  HmParams       P{};
-  uint32_t       blocks = 0;
-  std::vector<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> runs;   /* stride | first workgroup, workgroups */
-};
-
-/* what a call makes of the pairs: the clusters and the nearest neighbours take no score, so what the reference refuses
-   of scores is not theirs.  HM_NEAREST: `differences` is the call's min_distance */
-enum HmKind { HM_MATRIX, HM_NEIGHBORS, HM_CLUSTERS, HM_NEAREST };
-
-int hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
-                int64_t differences, HmKind kind, bool on_device)
+/* the refusals (hamming_sets.h) */
+int cmpr::hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                      int64_t differences, HmKind kind, bool on_device, bool with_indels)
 {
   if (differences < 0)
     return fail(c, CMPR_EINVAL, kind == HM_NEAREST ? who + ": min_distance cannot be negative"
                                                    : "Differences specified with -d or -differences cannot be negative.");
-  if (c->opt.indels)
+  if (c->opt.indels && !with_indels)
     return fail(c, CMPR_EINVAL, who + ": the all-against-all path has no indels");
   if (kind == HM_CLUSTERS && c->opt.existence)
     return fail(c, CMPR_EINVAL, "cmpr_cluster: clusters are not defined with options.existence");
@@ -646,6 +615,18 @@ int hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_view *se
     return fail(c, CMPR_EUNSUPPORTED, who + ": (length, V, J) does not fit a 64-bit key (n_v_genes x n_j_genes > 2^46)");
   return CMPR_OK;
 }
+
+namespace {
+
+/* what the four entry points share: the refusals, both sets on the device, the pairs of groups */
+struct HmJob {
+  HmSet          own1, own2;
+  HmSet         *s1 = nullptr, *s2 = nullptr;
+  Tmp<HmPair>    pairs;
+  HmParams       P{};
+  uint32_t       blocks = 0;
+  std::vector<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> runs;   /* stride | first workgroup, workgroups */
+};
 
 int hm_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
              int64_t differences, bool on_device, HmJob &J, bool triangular = false)

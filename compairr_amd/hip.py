@@ -39,6 +39,8 @@ EXPORTS = [
     "cmpr_hamming_cluster", "cmpr_hamming_cluster_device",
     "cmpr_hamming_cluster_table", "cmpr_hamming_cluster_table_device",
     "cmpr_hamming_nearest", "cmpr_hamming_nearest_device",
+    "cmpr_edit_neighbors", "cmpr_edit_neighbors_device",
+    "cmpr_edit_matrix", "cmpr_edit_matrix_device",
 ]
 
 NEAREST_OTHER_REPERTOIRE = 1      # CMPR_NEAREST_OTHER_REPERTOIRE
@@ -158,6 +160,8 @@ def _argtypes() -> dict:
         "cmpr_hamming_cluster": [ctx, view, C.c_int64, ptr, ptr, u64p],
         "cmpr_hamming_cluster_table": [ctx, view, C.c_int64, ptr, ptr, ptr, ptr, u64p],
         "cmpr_hamming_nearest": [ctx, view, view, C.c_int64, C.c_uint32, ptr, ptr, ptr, u64p],
+        "cmpr_edit_neighbors": [ctx, view, view, C.c_int64, C.c_uint64, ptr, ptr, ptr, u64p],
+        "cmpr_edit_matrix": [ctx, view, view, C.c_int64, ptr],
     }
     for name, args in twins.items():
         table[name] = table[name + "_device"] = args
@@ -609,6 +613,46 @@ class HipOverlap:
             C.c_void_p(d_distance or None), C.c_void_p(d_ties or None), C.byref(n)))
         return n.value
 
+    # ---- the all-against-all path under edit distance (include/compairr_hip.h: cmpr_edit_*) ----
+
+    def edit_neighbors(self, set1: RepertoireSet, set2: RepertoireSet, differences: int, distances: bool = True):
+        """(row_start uint64[n1 + 1], hits uint32[E], distance uint16[E] or None): the pairs of equal V and J (unless
+        ignore_genes) at a Levenshtein distance of at most `differences` as CSR -- the hits of sequence i of set1,
+        increasing, are hits[row_start[i]:row_start[i + 1]], the distance beside each.  `set2 is set1`: one-file
+        mode, the (i, i) pairs included.  The context's own `differences`, `indels` and resident sets play no part.
+        One count-only call, then one with the exact capacity."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is set1 else _view(set2)
+        return tuple(self._count_then_fill(self._lib.cmpr_edit_neighbors, (C.byref(v1), C.byref(v2), differences),
+                                           lambda: set1.n, (np.uint32, np.uint16 if distances else None)))
+
+    def edit_neighbors_device(self, view1: _SetView, view2: _SetView, differences: int, capacity: int = 0,
+                              d_row_start: int = 0, d_hits: int = 0, d_distance: int = 0) -> int:
+        """The same for views of device pointers into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted),
+        d_hits (uint32[capacity]; 0 with capacity 0: count only) and d_distance (uint16[capacity]; 0: hits only).
+        Returns the edge count; when it exceeds `capacity` nothing was written to d_hits or d_distance."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_edit_neighbors_device(
+            self._ctx, C.byref(view1), C.byref(view2), differences, capacity, C.c_void_p(d_row_start or None),
+            C.c_void_p(d_hits or None), C.c_void_p(d_distance or None), C.byref(n)))
+        return n.value
+
+    def edit_matrix(self, set1: RepertoireSet, set2: RepertoireSet, differences: int) -> np.ndarray:
+        """The R1 x R2 matrix (n1 x R2 with `existence`) of set1 against set2 over the pairs of edit_neighbors() --
+        the integer sums of hamming_matrix()."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is set1 else _view(set2)
+        rows = set1.n if self.opt.existence else set1.n_repertoires
+        out = np.zeros((rows, set2.n_repertoires), dtype=np.uint64)
+        self._check(self._lib.cmpr_edit_matrix(self._ctx, C.byref(v1), C.byref(v2), differences, out.ctypes.data))
+        return out
+
+    def edit_matrix_device(self, view1: _SetView, view2: _SetView, differences: int, d_matrix: int) -> None:
+        """The same for views of device pointers (device_view; the same object twice: one-file mode) into the
+        device array d_matrix (uint64[R1 * R2], or [n1 * R2] with `existence`)."""
+        self._check(self._lib.cmpr_edit_matrix_device(self._ctx, C.byref(view1), C.byref(view2), differences,
+                                                      C.c_void_p(d_matrix or None)))
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -731,6 +775,24 @@ def hamming_nearest(set1: RepertoireSet, set2: RepertoireSet, opt: Options, min_
     them)."""
     with _context(opt, tunables) as h:
         return h.hamming_nearest(set1, set2, min_distance, other_repertoire)
+
+
+def edit_neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, differences: int,
+                   tunables: Optional[dict] = None, distances: bool = True):
+    """Convenience: (row_start, hits, distance) of set1 against set2 at a Levenshtein distance of at most
+    `differences` (HipOverlap.edit_neighbors) on a context of its own; `opt.differences` and `opt.indels` play no
+    part.  `tunables` are set on the context first (the result never depends on them)."""
+    with _context(opt, tunables) as h:
+        return h.edit_neighbors(set1, set2, differences, distances)
+
+
+def edit_matrix(set1: RepertoireSet, set2: RepertoireSet, opt: Options, differences: int,
+                tunables: Optional[dict] = None):
+    """Convenience: the matrix of set1 against set2 over the pairs at a Levenshtein distance of at most
+    `differences` (HipOverlap.edit_matrix) on a context of its own; `opt.differences` and `opt.indels` play no
+    part.  `tunables` are set on the context first (the result never depends on them)."""
+    with _context(opt, tunables) as h:
+        return h.edit_matrix(set1, set2, differences)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -730,6 +730,76 @@ int cmpr_hamming_nearest_device(cmpr_context *ctx, const cmpr_set_view *d_set1, 
                                 uint64_t *n_found_out);
 
 /*
+ * The all-against-all path under EDIT distance, for any d.  The reference allows indels at d = 1 only ("The -i option
+ * is allowed only when d=1": its variant enumeration explodes beyond), and so do cmpr_create() and the hashed calls;
+ * cmpr_hamming_*() take any d but count substitutions only.  These calls take the distance as an ARGUMENT and the two
+ * sets as views, as cmpr_hamming_*() do, and compare by Levenshtein distance.
+ *
+ * The pair relation: (i of set1, j of set2) is a pair when the two sequences have the same V and J gene numbers unless
+ * options.ignore_genes, and the Levenshtein distance of their residues -- substitution, insertion and deletion cost 1
+ * each -- is at most `differences`.  The lengths may differ by up to `differences`; empty sequences take part.  With
+ * set2 == set1 (the same pointer) the set is uploaded once and the (i, i) pairs are included, as in the other calls.
+ *   differences   any value >= 0; negative is CMPR_EINVAL ("Differences specified with -d or -differences cannot be
+ *                 negative.").  A value above the longest sequence behaves as that length.
+ * options.differences and options.indels play no part and are NOT refused: this call is the indel call.
+ *
+ * Relation to the other calls.  At differences = 0 the edges are those of cmpr_hamming_neighbors() at 0; at every d
+ * every edge of cmpr_hamming_neighbors(d) is an edge here, at a distance no larger.  At differences = 1 the edge set
+ * is that of the reference's -d 1 -i -- the hashed calls on a context with options.indels, and
+ * cmpr_neighbors_distance()'s distances -- with ONE exception: the reference generates no deletion from a sequence of
+ * one residue (variants.cc:301, `if (seqlen > 1)`), so it does not pair a one-residue sequence of set1 with an empty
+ * sequence of set2, while it does pair the reverse.  Levenshtein distance is symmetric: these calls pair both.
+ *
+ * cmpr_edit_neighbors() gives the pairs as CSR with the distance of every edge, under the protocol of
+ * cmpr_hamming_neighbors(), word for word:
+ *   row_start_out[n1 + 1]   always written in full and always exact, whatever `capacity` is; may be NULL.
+ *   hit_out[capacity]       row i occupies [row_start[i], row_start[i + 1]): sequence numbers of set2 in strictly
+ *                           increasing order.  With more edges than `capacity` NOTHING is written to hit_out or
+ *                           distance_out and the call still returns CMPR_OK with *n_edges_out > capacity.
+ *                           capacity == 0 with both arrays NULL is the count-only call; capacity > 0 with hit_out
+ *                           NULL is CMPR_EINVAL.  Elements behind the last edge are not written.
+ *   distance_out[capacity]  the Levenshtein distance of the pair, 0 .. differences.  May be NULL (hits only).
+ *   *n_edges_out            required (NULL: CMPR_EINVAL), a HOST pointer in both variants; == row_start[n1].
+ * cmpr_edit_neighbors_device() takes DEVICE views and the three arrays as device memory.
+ *
+ * cmpr_edit_matrix() writes R1 x R2 uint64 -- n1 x R2 with options.existence -- of the integer sums
+ * cmpr_hamming_matrix() documents, over these pairs; the output is overwritten.  cmpr_edit_matrix_device() takes DEVICE
+ * views and d_matrix on the context's device.
+ *
+ * All four: synchronous; callable any time after cmpr_create(); the sets are validated as every other set (same
+ * codes and texts, passed through unchanged); the resident sets, plans and statistics are not disturbed; every
+ * temporary is freed on every return; results are bit-identical from run to run and under every tunable (integer
+ * sums; the hits of a row are distinct, so the row order is total).  n1 == 0 or n2 == 0 is CMPR_OK with a zero matrix,
+ * or row_start all zero.  Refused before any device work, with the codes and texts of cmpr_hamming_neighbors(): a
+ * negative `differences`; a NULL set; the tunable work_shard_count above 1; n_v_genes x n_j_genes above 2^46;
+ * CMPR_SCORE_RATIO without ignore_counts in _matrix; MH / Jaccard with differences > 0.  A set whose longest sequence
+ * has more than 256 residues is CMPR_EUNSUPPORTED ("cmpr_edit: a sequence of more than 256 residues"), decided when the
+ * set has been validated on the device and before anything is compared: 256 residues are four 64-bit words of the
+ * bit-vector column below, and cover every CDR3 and junction, amino acids or nucleotides.  At most 2^31-1 sequences
+ * per set.
+ *
+ * How (compairr_amd/csrc/edit.hip): the sets are grouped by (length, V, J) and packed as for cmpr_hamming_*().  The
+ * host pairs every set-1 group (L, V, J) with the set-2 groups (L', V, J), |L - L'| <= d, by binary search of the
+ * group keys over the lengths set 2 has.  A workgroup compares 256 queries of a group with a segment of every such
+ * partner, staged in LDS as match vectors (per reference and symbol, a bit per position), every lane its own query
+ * through the bit-vector edit distance (Myers 1999; global form of Hyyro 2003): one LDS read and some fifteen 64-bit
+ * operations per query residue and 64 reference residues.  A walk goes partner by partner, so the rows are sorted
+ * afterwards (by the hit; distances carried along).  Device memory for the duration of the call: what
+ * cmpr_hamming_neighbors() / _matrix() take, 32 bytes per set-1 group and 24 per pair of groups, and while the rows
+ * are put in order 4 bytes per row of more than 64 hits and 6 bytes per hit of the longest row beyond 8192.
+ */
+int cmpr_edit_neighbors(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                        int64_t differences, uint64_t capacity, uint64_t *row_start_out,
+                        uint32_t *hit_out, uint16_t *distance_out, uint64_t *n_edges_out);
+int cmpr_edit_neighbors_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                               int64_t differences, uint64_t capacity, uint64_t *d_row_start_out,
+                               uint32_t *d_hit_out, uint16_t *d_distance_out, uint64_t *n_edges_out);
+int cmpr_edit_matrix(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                     int64_t differences, uint64_t *matrix_out);
+int cmpr_edit_matrix_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                            int64_t differences, void *d_matrix);
+
+/*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
  * runtime, the device's context, the code objects of the kernels the given options will run.
  * The reference has no counterpart -- its threads start in microseconds (overlap.cc:926-936);
@@ -859,6 +929,13 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
                              global memory), 0 (default) only groups of more than 16 words per sequence
      "hamming_link_snapshot" TEST ONLY, cmpr_hamming_cluster*(): 1 (default) skips a match whose two staged root
                              snapshots agree, 0 sends every match to the forest; the partition is the same
+     "edit_stage_refs"       TEST ONLY, cmpr_edit_*(): references staged per LDS piece (0 = default: as many match
+                             vectors as fit 16 KiB, at most 512; a larger value is clamped to that)
+     "edit_segments"         TEST ONLY: forces the number of segments every partner group is walked in (1..64; 0 =
+                             default: automatic, from the number of query workgroups)
+     "edit_words"            TEST ONLY: 2 or 4 forces at least that many 64-bit words per column, so that short
+                             sequences run through the multiword forms; 0 (default): 1, 2 or 4 from the reference's
+                             length
    What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
    the state):
      before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",
@@ -890,7 +967,11 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    "hamming_compare_us" (the compare kernel: once for a matrix, the count step, the sum and the fill step for
    neighbours; for cmpr_hamming_cluster*() the link kernel, the flatten and the sizes) and "hamming_copy_us" (host
    variant: the results copied out).  cmpr_hamming_cluster_table*() set these three as well, zero
-   "cluster_links_us" and set "cluster_table_us" (the table pass, its copies included: "hamming_copy_us" stays 0). */
+   "cluster_links_us" and set "cluster_table_us" (the table pass, its copies included: "hamming_copy_us" stays 0);
+   and of the last cmpr_edit_*(), host times, each part ending in a wait: "edit_group_us" (upload, validation, keys,
+   sort, groups, packing, the jobs), "edit_compare_us" (the compare kernel: once for a matrix, the count step, the sum
+   and the fill step for neighbours), "edit_order_us" (the rows sorted; 0 for a matrix or when nothing was filled)
+   and "edit_copy_us" (host variant: the results copied out). */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

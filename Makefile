@@ -21,7 +21,7 @@ HOST_HDR = $(wildcard compairr_amd/host/*.h) include/compairr_hip.h
 KERN_DIR = compairr_amd/csrc
 KERN_HDR = $(KERN_DIR)/kernels.h $(KERN_DIR)/kernels_sliced.h $(KERN_DIR)/kernels_rows.h \
            $(KERN_DIR)/kernels_pairs2.h \
-           $(KERN_DIR)/layout.h $(KERN_DIR)/lds_map.h $(KERN_DIR)/link_forest.h $(KERN_DIR)/select.h $(KERN_DIR)/context.h $(KERN_DIR)/csr_rows.h $(KERN_DIR)/hamming_sets.h include/compairr_hip.h
+           $(KERN_DIR)/layout.h $(KERN_DIR)/lds_map.h $(KERN_DIR)/link_forest.h $(KERN_DIR)/select.h $(KERN_DIR)/context.h $(KERN_DIR)/csr_rows.h $(KERN_DIR)/allpairs.h include/compairr_hip.h
 OBJ_DIR  = compairr_amd/lib/obj
 # the probe kernels are instantiated per (kernel variant, waves per workgroup) in
 # their own translation units, so that `make -j` compiles them side by side
@@ -62,6 +62,10 @@ $(OBJ_DIR)/neighbors.o: $(KERN_DIR)/neighbors.hip $(KERN_HDR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
 $(OBJ_DIR)/existence.o: $(KERN_DIR)/existence.hip $(KERN_HDR)
+	@mkdir -p $(OBJ_DIR)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
+$(OBJ_DIR)/allpairs.o: $(KERN_DIR)/allpairs.hip $(KERN_HDR)
 	@mkdir -p $(OBJ_DIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
@@ -106,7 +110,7 @@ $(OBJ_DIR)/probe_v2wi_nw%.o: $(KERN_DIR)/probe_tu.hip $(KERN_HDR)
 	$(HIPCC) $(HIPFLAGS) -DTU_VARIANT=2 -DTU_NW=$* -DTU_INLINE=1 -DTU_WIDE -c -o $@ $<
 
 $(LIB): $(OBJ_DIR)/main.o $(OBJ_DIR)/query_layout.o $(OBJ_DIR)/ref_index.o $(OBJ_DIR)/dedup.o $(OBJ_DIR)/cluster.o \
-        $(OBJ_DIR)/neighbors.o $(OBJ_DIR)/existence.o $(OBJ_DIR)/hamming.o $(OBJ_DIR)/edit.o $(TU_OBJS)
+        $(OBJ_DIR)/neighbors.o $(OBJ_DIR)/existence.o $(OBJ_DIR)/allpairs.o $(OBJ_DIR)/hamming.o $(OBJ_DIR)/edit.o $(TU_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 # diagnostic build with per-phase cycle counters in the probe kernel (tools/phase_timing.py)

@@ -1,8 +1,7 @@
 /*
- * csr_rows.h -- the passes over CSR rows of hits that neighbors.hip and existence.hip share: every row sorted in
- * place by a key of its hits, on one of four paths by the row's length n.  The thresholds are what each path
- * holds, and this is their only definition: the census that sizes the lists (neighbors.hip nb_census_kernel)
- * counts by them.
+ * csr_rows.h -- the passes over CSR rows of hits that neighbors.hip, existence.hip and allpairs.hip share: every row
+ * sorted in place by a key of its hits, on one of four paths by the row's length n.  The thresholds are what each path
+ * holds, and this is their only definition: the census that sizes the lists (rows_census_kernel) counts by them.
  *
  *   n <= 1              nothing.  Real data: most rows.
  *   n <= LANE_MAX = 8   one lane per row, the row in eight registers, a 19-comparator network
@@ -41,6 +40,8 @@
 #define COMPAIRR_AMD_CSR_ROWS_H
 
 #include "context.h"
+
+#include <hipcub/hipcub.hpp>
 
 namespace cmpr {
 
@@ -259,6 +260,134 @@ inline int rows_fetch_long(cmpr_context *c, const RowLists &L, uint64_t longest,
   }
   return CMPR_OK;
 }
+
+/* ---- the rows ordered by the hit itself (neighbors.hip, allpairs.hip) ---- */
+
+/* nothing to gather, nothing kept */
+struct HitRows {
+  using Key = uint32_t;
+  static constexpr Key  PAD = 0xffffffffu;   /* no sequence number (a set has fewer than 2^32 - 64 sequences) */
+  static constexpr bool COUNT_HEADS = false;
+  uint32_t *hit;
+  __device__ Key load(uint64_t pos) const { return hit[pos]; }
+  __device__ void store(uint64_t pos, Key key) const { hit[pos] = key; }
+  __device__ static bool same_run(Key, Key) { return true; }
+};
+
+/* the same order with the distance of each edge (a D) carried along: a row never holds a hit twice, so the low bits
+   of the key never decide */
+template <typename D>
+struct HitDistRows {
+  using Key = unsigned long long;
+  static constexpr Key  PAD = ~0ull;
+  static constexpr bool COUNT_HEADS = false;
+  uint32_t *hit;
+  D        *dist;
+  __device__ Key load(uint64_t pos) const { return (Key)hit[pos] << 8 * sizeof(D) | dist[pos]; }
+  __device__ void store(uint64_t pos, Key key) const
+  {
+    hit[pos] = (uint32_t)(key >> 8 * sizeof(D));
+    dist[pos] = (D)key;
+  }
+  __device__ static bool same_run(Key, Key) { return true; }
+};
+
+/* census[0] rows longer than a wave, [1] of those the rows longer than LDS, [2] the longest row when it is
+   longer than LDS.  Real data has no such row: a wave that sees none touches nothing. */
+static __global__ void __launch_bounds__(ROW_WG)
+rows_census_kernel(const uint64_t *row_start, uint64_t n, unsigned long long *census)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
+  const uint64_t len = i < n ? row_start[i + 1] - row_start[i] : 0;
+  const uint64_t big = __ballot(len > WAVE);
+  if (!big)
+    return;
+  const uint64_t lng = __ballot(len > LDS_MAX);
+  if (lane_id() == 0) {
+    atomicAdd(census + 0, (unsigned long long)__popcll(big));
+    if (lng)
+      atomicAdd(census + 1, (unsigned long long)__popcll(lng));
+  }
+  if (len > LDS_MAX)
+    atomicMax(census + 2, (unsigned long long)len);
+}
+
+/* queued behind what writes row_start: census[0..2] of the n rows, and [3..4], the two list counters, zero */
+inline int rows_census(cmpr_context *c, const uint64_t *row_start, uint64_t n, unsigned long long *census)
+{
+  HIP_TRY(c, hipMemsetAsync(census, 0, 5 * sizeof(unsigned long long), c->stream));
+  if (n) {
+    hipLaunchKernelGGL(rows_census_kernel, dim3(blocks_for(n, ROW_WG)), dim3(ROW_WG), 0, c->stream, row_start, n, census);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return CMPR_OK;
+}
+
+/* The rows of a filled CSR put in increasing order of the hit, `dist` (or NULL: the hits alone) carried along.  Two
+   steps, so that a caller allocates before it fills: reserve() once the census has reached the host (n_big rows of
+   WAVE + 1 .. LDS_MAX hits, n_long longer ones, the longest of those), run() behind the fill; ctr: census + 3. */
+template <typename D>
+struct RowOrder {
+  uint64_t n_big = 0, n_long = 0, longest = 0;
+  Tmp<uint32_t> big_rows, scratch;
+  Tmp<unsigned long long> long_desc;
+  Tmp<D> dist_scratch;
+  Tmp<char> sort_tmp;
+  size_t sort_bytes = 0;
+
+  int reserve(cmpr_context *c, uint64_t n_big_, uint64_t n_long_, uint64_t longest_, bool with_dist)
+  {
+    int rc;
+    n_big = n_big_; n_long = n_long_; longest = longest_;
+    if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
+    if (!n_long)
+      return CMPR_OK;
+    if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
+    if ((rc = dev_alloc(c, scratch.b, (size_t)longest))) return rc;
+    if (with_dist) {
+      if ((rc = dev_alloc(c, dist_scratch.b, (size_t)longest))) return rc;
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                    (const D *)nullptr, (D *)nullptr, (size_t)longest, 0, 32, c->stream));
+    } else {
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
+                                                   (size_t)longest, 0, 32, c->stream));
+    }
+    return dev_alloc(c, sort_tmp.b, sort_bytes);
+  }
+
+  /* queued, but for the one wait that brings the list of the rows beyond LDS when there are any: each of those
+     through hipcub's device-wide sort into the scratch and back */
+  int run(cmpr_context *c, const char *who, const uint64_t *row_start, uint64_t n, uint64_t total,
+          unsigned long long *ctr, uint32_t *hit, D *dist)
+  {
+    int rc;
+    const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, ctr};   /* (counters: zero) */
+    if ((rc = dist ? rows_sort(c, row_start, n, lists, HitDistRows<D>{hit, dist})
+                   : rows_sort(c, row_start, n, lists, HitRows{hit})))
+      return rc;
+    if (!n_long)
+      return CMPR_OK;
+    std::vector<LongRow> lr;
+    if ((rc = rows_fetch_long(c, lists, longest, total, n, who, lr)))
+      return rc;
+    for (const LongRow &r : lr) {
+      size_t b = sort_bytes;
+      if (dist) {
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
+                                                      (const D *)(dist + r.start), dist_scratch.b.p, (size_t)r.len, 0,
+                                                      32, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(dist + r.start, dist_scratch.b.p, (size_t)r.len * sizeof(D), hipMemcpyDeviceToDevice,
+                                  c->stream));
+      } else {
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
+                                                     (size_t)r.len, 0, 32, c->stream));
+      }
+      HIP_TRY(c, hipMemcpyAsync(hit + r.start, scratch.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
+                                c->stream));
+    }
+    return CMPR_OK;
+  }
+};
 
 }  // namespace cmpr
 

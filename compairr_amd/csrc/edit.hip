@@ -5,8 +5,8 @@
  * is at most `differences`.  The reference has indels at d = 1 only (its variant enumeration explodes beyond); nothing
  * is enumerated or hashed here: every query is compared with every sequence of every group it can match.
  *
- *   group    hamming.hip's, through hamming_sets.h: each set sorted by (length, V, J) with a stable radix sort, its
- *            residues packed in group order.  Sequences of more than ED_MAX_LEN = 256 residues are refused.
+ *   group    allpairs.h's: each set sorted by (length, V, J) with a stable radix sort, its residues packed in group
+ *            order.  Sequences of more than ED_MAX_LEN = 256 residues are refused.
  *   jobs     on the host, from the two group tables: a set-1 group (L, V, J) and its PARTNERS, the set-2 groups
  *            (L', V, J) with |L - L'| <= d, found by binary search of the key for every length L' set 2 has (a huge d
  *            costs nothing).  The partners of a job are contiguous in one array.
@@ -28,22 +28,14 @@
  *            memory (NW = 0: one load per four or sixteen column steps); unrolled, 256 steps of four column words
  *            would be straight-line code far beyond the instruction cache.  No instantiation indexes an array at
  *            run time: private_segment_fixed_size is 0 in every one of them (checked in the code object's metadata).
- *   sinks    matrix: hamming.hip's -- the score of a match is added to a per-lane sum that goes to its cell when the
- *            lane's next match lies in another set-2 repertoire and at the end, into a copy of the matrix in LDS
- *            when it has at most ED_MAT_CELLS cells, else with 64-bit global atomics.  Integer sums.
- *            count / fill: a lane counts the hits of its (query, segment), the counts are summed in (query,
- *            segment) order (hipcub) and the same walk writes every hit and its distance at the lane's running
- *            offset.  The walk goes partner by partner, which is not number order, so the rows are sorted
- *            afterwards by csr_rows.h with the 64-bit key (hit << 16 | distance) -- the hit alone without
- *            distance_out --, rows beyond LDS_MAX by hipcub's device-wide sort.  The hits of a row are distinct: the
- *            order is total, the bytes do not depend on the schedule.
+ *   sinks    allpairs.h's matrix and count / fill.  The walk goes partner by partner, which is not number order, so
+ *            the rows are sorted afterwards by csr_rows.h with the 64-bit key (hit << 16 | distance) -- the hit alone
+ *            without distance_out --, rows beyond LDS_MAX by hipcub's device-wide sort.  The hits of a row are
+ *            distinct: the order is total, the bytes do not depend on the schedule.
  *
  * Nothing here writes the resident sets, plans or statistics of the context.
  */
-#include "csr_rows.h"
-#include "hamming_sets.h"
-
-#include <hipcub/hipcub.hpp>
+#include "allpairs.h"
 
 #include <algorithm>
 #include <string>
@@ -53,13 +45,9 @@ using namespace cmpr;
 
 namespace {
 
-constexpr uint32_t ED_WG = 256;                /* four waves: four 64-query tiles of one job */
 constexpr uint32_t ED_MAX_LEN = 256;           /* residues of the longest sequence: four 64-bit column words */
 constexpr uint32_t ED_REG_RESIDUES = 64;       /* a query of more residues is read from global memory (NW = 0) */
 constexpr uint32_t ED_PEQ_WORDS = 2048;        /* 64-bit words of Peq staged at a time (16 KiB) */
-constexpr uint32_t ED_STAGE_MAX = 512;         /* ... and at most this many references */
-constexpr uint32_t ED_MAT_CELLS = 1024;        /* a matrix of up to this many cells is privatised in LDS (8 KiB) */
-constexpr uint32_t ED_MAX_SEGMENTS = 64;
 
 /* a set-2 group a job is compared with */
 struct EdPartner {
@@ -85,20 +73,8 @@ struct EdParams {
   const uint32_t *ord1, *ord2;     /* sequence numbers in group order */
   uint32_t        d, stage_refs, min_words;
   uint32_t        blk_base;        /* workgroup number of this launch's first workgroup */
-  /* count / fill */
-  uint32_t       *cnt;             /* [n1 x segments]: hits of (query, segment) */
-  const unsigned long long *offs;  /* their exclusive sum; NULL: the count step */
-  uint32_t       *hit;
-  uint16_t       *dist;            /* may be NULL */
-  /* matrix */
-  const uint32_t *rep1, *rep2;
-  const uint64_t *cnt1, *cnt2;     /* NULL: ignore_counts */
-  uint32_t        R2, score, existence, mat_lds;
-  unsigned long long *matrix;
-  uint32_t        cells;
+  PairSinks       sink;            /* count / fill, matrix (allpairs.h) */
 };
-
-enum { SINK_CSR = 0, SINK_MATRIX = 1 };
 
 /* One column of the edit-distance matrix further: the text residue whose Peq words lie at `peq`.  pv / mv: the
    vertical +1 / -1 deltas of the column, W 64-bit words, bit i for row i + 1; the top row's horizontal delta is +1
@@ -135,51 +111,28 @@ __device__ __forceinline__ void ed_step(const unsigned long long *peq, unsigned 
   score -= (uint32_t)(mh_s >> sb) & 1u;
 }
 
-/* what a lane keeps of its matches */
-struct EdLaneSink {
-  /* CSR */
-  uint32_t hits = 0;
-  unsigned long long pos = 0;
-  /* matrix */
-  unsigned long long acc = 0, row = 0, f = 1;
-  uint32_t cur_rep = 0;
-};
-
 /* NW: words of the query held in registers, 0: the query is read from global memory */
 template <int NW, int SINK, bool NT>
-__global__ void __launch_bounds__(ED_WG)
+__global__ void __launch_bounds__(PAIRS_WG)
 ed_compare_kernel(const EdParams P)
 {
   constexpr uint32_t A = NT ? 4 : 20, PER = NT ? 16 : 4, BITS = NT ? 2 : 8, MASK = NT ? 3 : 0xff;
   __shared__ unsigned long long st_peq[ED_PEQ_WORDS];
-  __shared__ uint32_t st_id[ED_STAGE_MAX];
-  __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? ED_STAGE_MAX : 1];
-  __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? ED_STAGE_MAX : 1];
-  __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? ED_MAT_CELLS : 1];
+  __shared__ uint32_t st_id[PAIRS_STAGE_MAX];
+  __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? PAIRS_STAGE_MAX : 1];
+  __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? PAIRS_STAGE_MAX : 1];
+  __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? PAIRS_MAT_CELLS : 1];
 
-  /* the job of this workgroup: the last one whose first workgroup is not behind it */
   const uint32_t blk = P.blk_base + blockIdx.x;
-  uint32_t lo = 0, hi = P.njobs - 1;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi + 1) >> 1;
-    if (P.jobs[mid].blk0 <= blk)
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  const EdJob jb = P.jobs[lo];
-  const uint32_t qi = (blk - jb.blk0) * ED_WG + threadIdx.x;            /* query within the group */
-  const bool active = qi < jb.nq;
-  const uint32_t qpos = jb.q0 + (active ? qi : 0u);                     /* (an idle lane reads the group's first query) */
-  const uint32_t qorig = P.ord1[qpos];
+  const EdJob jb = pairs_entry_of(P.jobs, P.njobs, blk);
+  const PairQuery Q(jb, blk, P.ord1);
+  const uint32_t qpos = Q.qpos, qorig = Q.qorig;
+  const bool active = Q.active();
   const uint32_t qlen = jb.len;
   const uint32_t seg = blockIdx.y;
 
-  const bool mat_lds = SINK == SINK_MATRIX && P.mat_lds;
-  if (mat_lds) {                                                        /* (a barrier follows before the first flush) */
-    for (uint32_t k = threadIdx.x; k < P.cells; k += ED_WG)
-      st_mat[k] = 0;
-  }
+  PairSink<SINK> S(P.sink, P.segments, PairLds(st_id, st_rep, st_cnt, st_mat));
+  S.zero_matrix();                                                      /* (a barrier follows before the first match) */
 
   const uint32_t *const qw = P.pk1 + jb.pk1 + (uint64_t)(qpos - jb.q0) * jb.stride;
   uint32_t q[NW ? NW : 1];
@@ -189,45 +142,7 @@ ed_compare_kernel(const EdParams P)
       q[k] = (uint32_t)k < jb.stride ? qw[k] : 0u;
   }
 
-  EdLaneSink S;
-  if (SINK == SINK_CSR) {
-    if (P.offs)
-      S.pos = P.offs[(uint64_t)qorig * P.segments + seg];
-  } else {
-    S.row = P.existence ? (unsigned long long)qorig : (unsigned long long)P.rep1[qorig];
-    S.f = P.cnt1 ? P.cnt1[qorig] : 1ull;
-  }
-  auto flush = [&]() {
-    if (SINK == SINK_MATRIX && S.acc) {
-      const uint64_t cell = S.row * P.R2 + S.cur_rep;
-      if (mat_lds)
-        atomicAdd(&st_mat[cell], S.acc);
-      else
-        atomicAdd(P.matrix + cell, S.acc);
-      S.acc = 0;
-    }
-  };
-  /* reference r of the staged piece matched at distance `dd` */
-  auto sink = [&](uint32_t r, uint32_t dd) {
-    if (SINK == SINK_CSR) {
-      if (P.offs) {
-        P.hit[S.pos] = st_id[r];
-        if (P.dist)
-          P.dist[S.pos] = (uint16_t)dd;
-        S.pos++;
-      } else {
-        S.hits++;
-      }
-    } else {
-      /* the lane's sum belongs to one set-2 repertoire: a match in another one sends it to its cell first */
-      const uint32_t rp = st_rep[r];
-      if (rp != S.cur_rep) {
-        flush();
-        S.cur_rep = rp;
-      }
-      S.acc += P.cnt1 ? pair_score(P.score, S.f, st_cnt[r]) : 1ull;
-    }
-  };
+  S.init(qorig, seg);
 
   /* the references e0 .. e1 - 1 of partner pt, their columns W words long */
   auto walk = [&](const EdPartner &pt, uint32_t e0, uint32_t e1, auto words) {
@@ -235,13 +150,13 @@ ed_compare_kernel(const EdParams P)
     const uint32_t n = pt.len;
     const uint32_t sw = n ? (n - 1) >> 6 : 0u, sb = n ? (n - 1) & 63u : 0u;
     uint32_t R = ED_PEQ_WORDS / (A * W);
-    if (R > ED_STAGE_MAX) R = ED_STAGE_MAX;
+    if (R > PAIRS_STAGE_MAX) R = PAIRS_STAGE_MAX;
     if (P.stage_refs && P.stage_refs < R) R = P.stage_refs;
     for (uint32_t e = e0; e < e1; e += R) {
       const uint32_t cnt = e1 - e < R ? e1 - e : R;
       __syncthreads();                                                  /* the previous piece has been read */
       /* Peq: one thread per (reference, symbol, word); st_peq[(r x A + symbol) x W + w] */
-      for (uint32_t it = threadIdx.x; it < cnt * A * W; it += ED_WG) {
+      for (uint32_t it = threadIdx.x; it < cnt * A * W; it += PAIRS_WG) {
         const uint32_t r = it / (A * W), sym = it % (A * W) / W, w = it % W;
         const uint32_t *const src = P.pk2 + pt.pk_off + (uint64_t)(e + r) * pt.stride;
         unsigned long long bits = 0;
@@ -257,14 +172,8 @@ ed_compare_kernel(const EdParams P)
         }
         st_peq[it] = bits;
       }
-      for (uint32_t r = threadIdx.x; r < cnt; r += ED_WG) {
-        const uint32_t id = P.ord2[pt.r0 + e + r];
-        st_id[r] = id;
-        if (SINK == SINK_MATRIX) {
-          st_rep[r] = P.rep2[id];
-          st_cnt[r] = P.cnt2 ? P.cnt2[id] : 1ull;
-        }
-      }
+      for (uint32_t r = threadIdx.x; r < cnt; r += PAIRS_WG)
+        S.stage(r, P.ord2[pt.r0 + e + r]);
       __syncthreads();
       for (uint32_t r = 0; r < cnt; r++) {
         uint32_t dd = n;
@@ -298,7 +207,7 @@ ed_compare_kernel(const EdParams P)
           }
         }
         if (dd <= P.d && active)
-          sink(r, dd);
+          S.match(r, dd);
       }
     }
   };
@@ -319,19 +228,7 @@ ed_compare_kernel(const EdParams P)
     else
       walk(pt, e0, e1, std::integral_constant<int, 4>());
   }
-
-  if (SINK == SINK_CSR) {
-    if (!P.offs && active)
-      P.cnt[(uint64_t)qorig * P.segments + seg] = S.hits;
-  } else {
-    flush();
-    if (mat_lds) {
-      __syncthreads();
-      for (uint32_t k = threadIdx.x; k < P.cells; k += ED_WG)
-        if (st_mat[k])
-          atomicAdd(P.matrix + k, st_mat[k]);
-    }
-  }
+  S.end(active, qorig, seg);
 }
 
 typedef void (*EdKernel)(const EdParams);
@@ -366,95 +263,23 @@ EdKernel ed_kernel_for(uint32_t nw, bool nt)
   }
 }
 
-/* row_start[i] = the offset of (query i, segment 0); row_start[n1] = the edge count */
-__global__ void __launch_bounds__(ED_WG)
-ed_rows_kernel(const unsigned long long *offs, uint64_t n1, uint32_t segments, uint64_t *row_start)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * ED_WG + threadIdx.x;
-  if (i <= n1)
-    row_start[i] = offs[i * segments];
-}
-
-/* census[0] rows longer than a wave, [1] of those the rows longer than LDS, [2] the longest row when it is longer than
-   LDS (csr_rows.h sizes its lists by them) */
-__global__ void __launch_bounds__(ROW_WG)
-ed_census_kernel(const uint64_t *row_start, uint64_t n, unsigned long long *census)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
-  const uint64_t len = i < n ? row_start[i + 1] - row_start[i] : 0;
-  const uint64_t big = __ballot(len > WAVE);
-  if (!big)
-    return;
-  const uint64_t lng = __ballot(len > LDS_MAX);
-  if (lane_id() == 0) {
-    atomicAdd(census + 0, (unsigned long long)__popcll(big));
-    if (lng)
-      atomicAdd(census + 1, (unsigned long long)__popcll(lng));
-  }
-  if (len > LDS_MAX)
-    atomicMax(census + 2, (unsigned long long)len);
-}
-
-/* the rows ordered by the hit, the distance of each edge carried along: a row never holds a hit twice, so the low
-   sixteen bits of the key never decide (csr_rows.h) */
-struct EdRows {
-  using Key = unsigned long long;
-  static constexpr Key  PAD = ~0ull;
-  static constexpr bool COUNT_HEADS = false;
-  uint32_t *hit;
-  uint16_t *dist;
-  __device__ Key load(uint64_t pos) const { return (Key)hit[pos] << 16 | dist[pos]; }
-  __device__ void store(uint64_t pos, Key key) const
-  {
-    hit[pos] = (uint32_t)(key >> 16);
-    dist[pos] = (uint16_t)key;
-  }
-  __device__ static bool same_run(Key, Key) { return true; }
-};
-
-/* ... without distance_out: the hits alone */
-struct EdHitRows {
-  using Key = uint32_t;
-  static constexpr Key  PAD = 0xffffffffu;   /* no sequence number (a set has at most 2^31 - 1 sequences) */
-  static constexpr bool COUNT_HEADS = false;
-  uint32_t *hit;
-  __device__ Key load(uint64_t pos) const { return hit[pos]; }
-  __device__ void store(uint64_t pos, Key key) const { hit[pos] = key; }
-  __device__ static bool same_run(Key, Key) { return true; }
-};
-
-/* what the four entry points share: both sets on the device, the jobs */
-struct EdWork {
-  HmSet          own1, own2;
-  HmSet         *s1 = nullptr, *s2 = nullptr;
+/* what the entry points share: both sets on the device, the jobs */
+struct EdWork : PairSets {
   Tmp<EdJob>     jobs;
   Tmp<EdPartner> partners;
   EdParams       P{};
-  std::vector<std::pair<uint32_t, std::pair<uint32_t, uint32_t>>> runs;   /* form | first workgroup, workgroups */
+  PairRuns       runs;             /* form: ed_form_of */
 };
-
-int ed_stage(cmpr_context *c, const cmpr_set_view *set, bool on_device, HmSet &H)
-{
-  int rc;
-  if ((rc = cmpr_stage_set(c, set, on_device, H)))
-    return rc;
-  if (H.longest > ED_MAX_LEN)
-    return fail(c, CMPR_EUNSUPPORTED, "cmpr_edit: a sequence of more than 256 residues");
-  return hm_prepare(c, H);
-}
 
 int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
              int64_t differences, bool on_device, EdWork &J)
 {
   int rc;
-  if ((rc = ed_stage(c, set1, on_device, J.own1))) return rc;
-  J.s1 = &J.own1;
-  if (set2 == set1) {
-    J.s2 = J.s1;
-  } else {
-    if ((rc = ed_stage(c, set2, on_device, J.own2))) return rc;
-    J.s2 = &J.own2;
-  }
+  if ((rc = pairs_stage(c, set1, set2, on_device, J, [&](const HmSet &H) {
+         return H.longest > ED_MAX_LEN ? fail(c, CMPR_EUNSUPPORTED, "cmpr_edit: a sequence of more than 256 residues")
+                                       : CMPR_OK;
+       })))
+    return rc;
   HmSet &A = *J.s1, &B = *J.s2;
   const uint64_t longest = std::max(A.longest, B.longest);
   const uint32_t d = (uint32_t)std::min<uint64_t>((uint64_t)differences, longest);   /* above the longest sequence: as that length */
@@ -487,12 +312,8 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
     }
     if (partners.size() == p0)
       continue;
-    const uint32_t nb = blocks_for(ga.count, ED_WG);
-    const uint32_t form = ed_form_of(ga.len, ga.stride);
-    if (!J.runs.empty() && J.runs.back().first == form)
-      J.runs.back().second.second += nb;
-    else
-      J.runs.push_back({form, {(uint32_t)blocks, nb}});
+    const uint32_t nb = blocks_for(ga.count, PAIRS_WG);
+    J.runs.add(ed_form_of(ga.len, ga.stride), (uint32_t)blocks, nb);
     jobs.push_back(EdJob{ga.pk_off, ga.start, ga.count, ga.len, ga.stride, (uint32_t)p0,
                          (uint32_t)(partners.size() - p0), (uint32_t)blocks, 0u});
     blocks += nb;
@@ -506,20 +327,11 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
     if ((rc = dev_upload(c, J.partners.b, partners.data(), partners.size()))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));           /* (the two vectors leave scope) */
   }
-  /* segments: as many as fill the machine while the query tiles alone do not, none shorter than a wave of references */
-  uint32_t S = 1;
-  if (c->edit_segments) {
-    S = (uint32_t)c->edit_segments;
-  } else if (blocks) {
-    const uint64_t target = (uint64_t)c->cus * 8;
-    S = (uint32_t)std::min<uint64_t>(ED_MAX_SEGMENTS, (target + blocks - 1) / blocks);
-    S = std::max<uint32_t>(1, std::min<uint32_t>(S, (nr_max + 63) / 64));
-  }
   EdParams &P = J.P;
   P.jobs = J.jobs.b.p;
   P.partners = J.partners.b.p;
   P.njobs = (uint32_t)jobs.size();
-  P.segments = S;
+  P.segments = pairs_segments(c, c->edit_segments, blocks, nr_max);
   P.pk1 = A.pk.b.p; P.pk2 = B.pk.b.p;
   P.ord1 = A.ord.b.p; P.ord2 = B.ord.b.p;
   P.d = d;
@@ -533,14 +345,7 @@ template <int SINK>
 int ed_launch(cmpr_context *c, const EdWork &J)
 {
   const bool nt = c->opt.alphabet_size == 4;
-  for (const auto &run : J.runs) {
-    const EdKernel fn = ed_kernel_for<SINK>(run.first, nt);
-    EdParams P = J.P;
-    P.blk_base = run.second.first;
-    hipLaunchKernelGGL(fn, dim3(run.second.second, P.segments), dim3(ED_WG), 0, c->stream, P);
-    HIP_TRY(c, hipGetLastError());
-  }
-  return CMPR_OK;
+  return pairs_launch(c, J.runs, J.P, [nt](uint32_t form) { return ed_kernel_for<SINK>(form, nt); });
 }
 
 int edit_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t differences,
@@ -561,98 +366,7 @@ int edit_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_
   if ((rc = ed_setup(c, who, set1, set2, differences, on_device, J)))
     return rc;
   c->ed_ms[0] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
-
-  const uint64_t rows = c->opt.existence ? J.s1->n : J.s1->R, cells = rows * J.s2->R;
-  if (cells == 0)
-    return CMPR_OK;
-  Out<unsigned long long> matrix((unsigned long long *)matrix_out, on_device);
-  if ((rc = matrix.temp(c, (size_t)cells))) return rc;
-  HIP_TRY(c, hipMemsetAsync(matrix.p, 0, cells * sizeof(unsigned long long), c->stream));
-  EdParams &P = J.P;
-  P.rep1 = J.s1->rep.b.p; P.rep2 = J.s2->rep.b.p;
-  P.cnt1 = c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p;
-  P.cnt2 = c->opt.ignore_counts ? nullptr : J.s2->cnt.b.p;
-  P.R2 = J.s2->R;
-  P.score = (uint32_t)c->opt.score;
-  P.existence = c->opt.existence ? 1u : 0u;
-  P.mat_lds = !c->opt.existence && cells <= ED_MAT_CELLS ? 1u : 0u;
-  P.matrix = matrix.p;
-  P.cells = (uint32_t)std::min<uint64_t>(cells, ED_MAT_CELLS);
-  if ((rc = ed_launch<SINK_MATRIX>(c, J)))
-    return rc;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  c->ed_ms[1] = ms_since(t0);
-  if (!on_device) {
-    t0 = std::chrono::steady_clock::now();
-    if ((rc = matrix.copy_out(c, (size_t)cells))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->ed_ms[3] = ms_since(t0);
-  }
-  return CMPR_OK;
-}
-
-/* every row of the filled CSR put in increasing order of the hit (csr_rows.h; the rows beyond LDS by hipcub) */
-int ed_order_rows(cmpr_context *c, const std::string &who, const uint64_t *row_start, uint64_t n1, uint64_t total,
-                  uint32_t *hit, uint16_t *dist)
-{
-  int rc;
-  Tmp<unsigned long long> census, long_desc;
-  Tmp<uint32_t> big_rows, scratch;
-  Tmp<uint16_t> dist_scratch;
-  Tmp<char> sort_tmp;
-  if ((rc = dev_alloc(c, census.b, 5))) return rc;         /* [0..2] the census, [3..4] the list counters */
-  HIP_TRY(c, hipMemsetAsync(census.b.p, 0, 5 * sizeof(unsigned long long), c->stream));
-  hipLaunchKernelGGL(ed_census_kernel, dim3(blocks_for(n1, ROW_WG)), dim3(ROW_WG), 0, c->stream, row_start, n1,
-                     census.b.p);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long seen[3] = {0, 0, 0};
-  HIP_TRY(c, hipMemcpyAsync(seen, census.b.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  const uint64_t n_long = seen[1], n_big = seen[0] - seen[1], longest = seen[2];
-  if (seen[1] > seen[0] || seen[0] > n1 || longest > total)
-    return fail(c, CMPR_EDEVICE, who + ": the census of the rows is out of range");
-  size_t sort_bytes = 0;
-  if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
-  if (n_long) {
-    if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
-    if ((rc = dev_alloc(c, scratch.b, (size_t)longest))) return rc;
-    if (dist) {
-      if ((rc = dev_alloc(c, dist_scratch.b, (size_t)longest))) return rc;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                    (const uint16_t *)nullptr, (uint16_t *)nullptr, (size_t)longest, 0,
-                                                    32, c->stream));
-    } else {
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                   (size_t)longest, 0, 32, c->stream));
-    }
-    if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
-  }
-  const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, census.b.p + 3};   /* (counters: zero) */
-  if ((rc = dist ? rows_sort(c, row_start, n1, lists, EdRows{hit, dist}) : rows_sort(c, row_start, n1, lists, EdHitRows{hit})))
-    return rc;
-  if (n_long) {
-    std::vector<LongRow> lr;
-    if ((rc = rows_fetch_long(c, lists, longest, total, n1, who.c_str(), lr)))
-      return rc;
-    for (const LongRow &r : lr) {
-      size_t b = sort_bytes;
-      if (dist) {
-        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
-                                                      (const uint16_t *)(dist + r.start), dist_scratch.b.p,
-                                                      (size_t)r.len, 0, 32, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(dist + r.start, dist_scratch.b.p, (size_t)r.len * sizeof(uint16_t),
-                                  hipMemcpyDeviceToDevice, c->stream));
-      } else {
-        HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
-                                                     (size_t)r.len, 0, 32, c->stream));
-      }
-      HIP_TRY(c, hipMemcpyAsync(hit + r.start, scratch.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                                c->stream));
-    }
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));             /* (the temporaries leave scope) */
-  return CMPR_OK;
+  return pairs_matrix(c, J, J.P.sink, matrix_out, on_device, [&] { return ed_launch<SINK_MATRIX>(c, J); }, c->ed_ms, 3);
 }
 
 int edit_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t differences,
@@ -677,69 +391,9 @@ int edit_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
   if ((rc = ed_setup(c, who, set1, set2, differences, on_device, J)))
     return rc;
   c->ed_ms[0] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
-
-  /* count per (query, segment); the sum; the rows (the row order below needs them, asked for or not) */
-  const uint64_t n1 = J.s1->n, S = J.P.segments, slots = n1 * S + 1;   /* (a zero behind the last: the sum's last is the total) */
-  if (slots > 0x7fffffffull)
-    return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^31-1 (query, segment) counts");
-  Out<uint64_t> rows(row_start_out, on_device);
-  Out<uint32_t> hit(hit_out, on_device);
-  Out<uint16_t> dist(dist_out, on_device);
-  Tmp<uint32_t> cnt;
-  Tmp<unsigned long long> offs;
-  Tmp<char> scan_tmp;
-  if ((rc = dev_alloc(c, cnt.b, (size_t)slots))) return rc;
-  if ((rc = dev_alloc(c, offs.b, (size_t)slots))) return rc;
-  HIP_TRY(c, hipMemsetAsync(cnt.b.p, 0, slots * sizeof(uint32_t), c->stream));
-  EdParams &P = J.P;
-  P.cnt = cnt.b.p;
-  if ((rc = ed_launch<SINK_CSR>(c, J)))
-    return rc;
-  hipcub::TransformInputIterator<unsigned long long, U32To64, const uint32_t *> wide(cnt.b.p, U32To64());
-  size_t scan_bytes = 0;
-  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, wide, offs.b.p, (int)slots, c->stream));
-  if ((rc = dev_alloc(c, scan_tmp.b, scan_bytes))) return rc;
-  HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(scan_tmp.b.p, scan_bytes, wide, offs.b.p, (int)slots, c->stream));
-  if ((rc = rows.temp(c, (size_t)(n1 + 1)))) return rc;
-  hipLaunchKernelGGL(ed_rows_kernel, dim3(blocks_for(n1 + 1, ED_WG)), dim3(ED_WG), 0, c->stream, offs.b.p, n1,
-                     (uint32_t)S, rows.p);
-  HIP_TRY(c, hipGetLastError());
-  unsigned long long total = 0;
-  HIP_TRY(c, hipMemcpyAsync(&total, offs.b.p + (slots - 1), sizeof total, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  *n_edges_out = total;
-
-  /* the same walk again, every hit to its place -- when there is room for all of them --, then the rows in order */
-  const bool fill = hit.wanted() && total && total <= capacity;
-  if (fill) {
-    if ((rc = hit.temp(c, (size_t)total))) return rc;
-    if (dist.wanted() && (rc = dist.temp(c, (size_t)total))) return rc;
-    P.offs = offs.b.p;
-    P.hit = hit.p;
-    P.dist = dist.p;
-    if ((rc = ed_launch<SINK_CSR>(c, J)))
-      return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  c->ed_ms[1] = ms_since(t0);
-  if (fill) {
-    t0 = std::chrono::steady_clock::now();
-    if ((rc = ed_order_rows(c, who, rows.p, n1, total, hit.p, dist.p)))
-      return rc;
-    c->ed_ms[2] = ms_since(t0);
-  }
-  if (!on_device) {
-    t0 = std::chrono::steady_clock::now();
-    if ((rc = rows.copy_out(c, (size_t)(n1 + 1)))) return rc;
-    if (fill) {
-      if ((rc = hit.copy_out(c, (size_t)total))) return rc;
-      if ((rc = dist.copy_out(c, (size_t)total))) return rc;
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->ed_ms[3] = ms_since(t0);
-  }
-  return CMPR_OK;
+  /* the rows always (the row order reads them); the row order into ed_ms[2] */
+  return pairs_neighbors(c, who, J, J.P.segments, J.P.sink, capacity, row_start_out, hit_out, dist_out, n_edges_out,
+                         on_device, [&] { return ed_launch<SINK_CSR>(c, J); }, true, c->ed_ms, 2, 3);
 }
 
 }  // namespace

@@ -8,8 +8,8 @@
  *
  *   count   one synchronous step in neighbour mode (kernels.h score_match): degree[query] += 1 per match
  *   scan    row_start = exclusive 64-bit sum of the n1 + 1 degree words (the last one is zero, so
- *           row_start[n1] is the edge count), hipcub; nb_census_kernel counts the rows beyond a wave and
- *           beyond LDS.  The edge count and the census reach the host together: the call's one wait between
+ *           row_start[n1] is the edge count), hipcub; behind it rows_census_kernel (csr_rows.h) counts the rows
+ *           beyond a wave and beyond LDS.  The edge count and the census reach the host together: the call's one wait between
  *           the two steps, after which it knows whether `capacity` suffices and what the ordering will need
  *   fill    the step again: slot = row_start[q] + (atomicSub(degree + q, 1) - 1), hit[slot] = the hit.  The
  *           degree words are the cursors; every word is zero afterwards
@@ -33,8 +33,8 @@
  * cmpr_neighbors_distance / _device: the same call with one byte beside every hit, the reference's --distance of
  * the pair (overlap.cc:491-502).  Count, scan and census are the same code; the fill step also has nb_dist, and the
  * lane that places a hit writes the distance of the kind its variant was verified as beside it (kernels.h
- * kind_distance); the rows are ordered by the 64-bit key hit << 8 | distance (NdRows: 64 KiB of LDS on the workgroup
- * path, as existence.hip), and the rows beyond LDS through hipcub::DeviceRadixSort::SortPairs -- key the hit, value
+ * kind_distance); the rows are ordered by the 64-bit key hit << 8 | distance (HitDistRows: 64 KiB of LDS on the
+ * workgroup path, as existence.hip), and the rows beyond LDS through hipcub::DeviceRadixSort::SortPairs -- key the hit, value
  * the byte -- and back.  On top of the figures above: one byte per edge (the host variant holds them on the device
  * for the call), and for rows beyond LDS one byte per hit of the longest of them and the scratch of the pair sort.
  *
@@ -48,54 +48,6 @@
 using namespace cmpr;
 
 namespace {
-
-/* the rows ordered by the hit: nothing to gather, nothing kept (csr_rows.h) */
-struct NbRows {
-  using Key = uint32_t;
-  static constexpr Key  PAD = 0xffffffffu;   /* no sequence number (n2 < 2^32 - 64) */
-  static constexpr bool COUNT_HEADS = false;
-  uint32_t *hit;
-  __device__ Key load(uint64_t pos) const { return hit[pos]; }
-  __device__ void store(uint64_t pos, Key key) const { hit[pos] = key; }
-  __device__ static bool same_run(Key, Key) { return true; }
-};
-
-/* the same order with the distance of each edge carried along: a row never holds a hit twice, so the low byte of
-   the key never decides (cmpr_neighbors_distance) */
-struct NdRows {
-  using Key = unsigned long long;
-  static constexpr Key  PAD = ~0ull;
-  static constexpr bool COUNT_HEADS = false;
-  uint32_t *hit;
-  uint8_t  *dist;
-  __device__ Key load(uint64_t pos) const { return (Key)hit[pos] << 8 | dist[pos]; }
-  __device__ void store(uint64_t pos, Key key) const
-  {
-    hit[pos] = (uint32_t)(key >> 8);
-    dist[pos] = (uint8_t)key;
-  }
-  __device__ static bool same_run(Key, Key) { return true; }
-};
-
-/* census[0] rows longer than a wave, [1] of those the rows longer than LDS, [2] the longest row when it is
-   longer than LDS.  Real data has no such row: a wave that sees none touches nothing. */
-__global__ void __launch_bounds__(ROW_WG)
-nb_census_kernel(const uint32_t *degree, uint64_t n, unsigned long long *census)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * ROW_WG + threadIdx.x;
-  const uint32_t d = i < n ? degree[i] : 0u;
-  const uint64_t big = __ballot(d > WAVE);
-  if (!big)
-    return;
-  const uint64_t lng = __ballot(d > LDS_MAX);
-  if (lane_id() == 0) {
-    atomicAdd(census + 0, (unsigned long long)__popcll(big));
-    if (lng)
-      atomicAdd(census + 1, (unsigned long long)__popcll(lng));
-  }
-  if (d > LDS_MAX)
-    atomicMax(census + 2, (unsigned long long)d);
-}
 
 /* the fill step's cursors: the hits of row i still to come */
 __global__ void __launch_bounds__(ROW_WG)
@@ -138,11 +90,7 @@ int nb_count(cmpr_context *c, NeighborEdges &e)
   t0 = std::chrono::steady_clock::now();
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(e.scan_tmp.p, e.scan_bytes, wide, (unsigned long long *)row_start,
                                               (size_t)(n1 + 1), c->stream));
-  HIP_TRY(c, hipMemsetAsync(e.census.p, 0, 5 * sizeof(unsigned long long), c->stream));
-  if (n1) {
-    hipLaunchKernelGGL(nb_census_kernel, dim3(blocks_for(n1, ROW_WG)), dim3(ROW_WG), 0, c->stream, degree, n1, e.census.p);
-    HIP_TRY(c, hipGetLastError());
-  }
+  if ((rc = rows_census(c, row_start, n1, e.census.p))) return rc;
   unsigned long long total = 0, seen[3] = {0, 0, 0};
   HIP_TRY(c, hipMemcpyAsync(&total, row_start + n1, sizeof total, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipMemcpyAsync(seen, e.census.p, sizeof seen, hipMemcpyDeviceToHost, c->stream));
@@ -213,60 +161,18 @@ int neighbors_impl(cmpr_context *c, uint64_t capacity, uint64_t *row_start_out, 
   if (!hit_out || (with_dist && !dist_out) || total == 0 || total > capacity)
     return CMPR_OK;
 
-  const uint64_t n_long = e.n_long, n_big = e.n_big, longest = e.longest;
-  Tmp<uint32_t> big_rows, scratch;
-  Tmp<unsigned long long> long_desc;
-  Tmp<uint8_t> dist_scratch;
-  Tmp<char> sort_tmp;
-  size_t sort_bytes = 0;
+  /* what the ordering needs is allocated in front of the fill */
+  RowOrder<uint8_t> order;
   if ((rc = e.hit.temp(c, (size_t)total))) return rc;
   if (with_dist && (rc = dist_o.temp(c, (size_t)total))) return rc;
-  const uint64_t *const row_start = e.row_start.p;
-  uint32_t *const hit = e.hit.p;
-  uint8_t *const dist = dist_o.p;
-  if (n_big && (rc = dev_alloc(c, big_rows.b, (size_t)n_big))) return rc;
-  if (n_long) {
-    if ((rc = dev_alloc(c, long_desc.b, (size_t)(LONG_WORDS * n_long)))) return rc;
-    if ((rc = dev_alloc(c, scratch.b, (size_t)longest))) return rc;
-    if (with_dist) {
-      if ((rc = dev_alloc(c, dist_scratch.b, (size_t)longest))) return rc;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                    (const uint8_t *)nullptr, (uint8_t *)nullptr, (size_t)longest, 0,
-                                                    32, c->stream));
-    } else {
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                   (size_t)longest, 0, 32, c->stream));
-    }
-    if ((rc = dev_alloc(c, sort_tmp.b, sort_bytes))) return rc;
-  }
-  if ((rc = nb_fill(c, e, dist)))
+  if ((rc = order.reserve(c, e.n_big, e.n_long, e.longest, with_dist))) return rc;
+  if ((rc = nb_fill(c, e, dist_o.p)))
     return rc;
 
   /* ---- order the rows ---- */
   auto t0 = std::chrono::steady_clock::now();
-  const RowLists lists{big_rows.b.p, n_big, long_desc.b.p, n_long, e.census.p + 3};   /* (counters: zero) */
-  if ((rc = with_dist ? rows_sort(c, row_start, n1, lists, NdRows{hit, dist})
-                      : rows_sort(c, row_start, n1, lists, NbRows{hit})))
+  if ((rc = order.run(c, who.c_str(), e.row_start.p, n1, total, e.census.p + 3, e.hit.p, dist_o.p)))
     return rc;
-  if (n_long) {
-    std::vector<LongRow> lr;
-    if ((rc = rows_fetch_long(c, lists, longest, total, n1, who.c_str(), lr)))
-      return rc;
-    for (const LongRow &r : lr) {
-      size_t b = sort_bytes;
-      if (with_dist) {
-        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
-                                                      (const uint8_t *)(dist + r.start), dist_scratch.b.p,
-                                                      (size_t)r.len, 0, 32, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(dist + r.start, dist_scratch.b.p, (size_t)r.len, hipMemcpyDeviceToDevice, c->stream));
-      } else {
-        HIP_TRY(c, hipcub::DeviceRadixSort::SortKeys(sort_tmp.b.p, b, (const uint32_t *)(hit + r.start), scratch.b.p,
-                                                     (size_t)r.len, 0, 32, c->stream));
-      }
-      HIP_TRY(c, hipMemcpyAsync(hit + r.start, scratch.b.p, (size_t)r.len * sizeof(uint32_t), hipMemcpyDeviceToDevice,
-                                c->stream));
-    }
-  }
   if ((rc = e.hit.copy_out(c, (size_t)total))) return rc;
   if ((rc = dist_o.copy_out(c, (size_t)total))) return rc;
   HIP_TRY(c, hipStreamSynchronize(c->stream));

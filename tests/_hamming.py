@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 INPUTS = os.path.join(HERE, "golden", "inputs")
 EXPECTED = os.path.join(HERE, "golden", "expected")
 
-# HAMMING_REG_WORDS of compairr_amd/csrc/hamming.hip (tests/test_hamming_cpu.py reads the constant there): a sequence
+# HAMMING_REG_WORDS of compairr_amd/csrc/allpairs.h (tests/test_hamming_cpu.py reads the constant there): a sequence
 # of more 32-bit words -- four amino acids or sixteen nucleotides each -- takes the generic form
 REG_WORDS = 16
 REG_BOUND = {False: REG_WORDS * 4, True: REG_WORDS * 16}        # residues, by `nucleotides`

@@ -455,3 +455,41 @@ def test_empty_sets():
         assert h._lib.cmpr_edit_matrix(h._ctx, C.byref(v_s), C.byref(v_e), 3, m.ctypes.data) == CMPR_OK
         assert not m.any()
         assert h.edit_neighbors(empty, empty, 3)[0].tolist() == [0]
+
+
+# ---- 13. the drivers shared with cmpr_hamming_*: each family's timers are its own; the order of the refusals ----
+
+HAMMING_TIMERS = ("hamming_group_us", "hamming_compare_us", "hamming_copy_us")
+EDIT_TIMERS = ("edit_group_us", "edit_compare_us", "edit_order_us", "edit_copy_us")
+
+
+def test_timers_stay_apart():
+    """a cmpr_edit_* call leaves the three hamming_*_us as they were, a cmpr_hamming_* call the four edit_*_us; the
+    copy-out of either lands in its own family's slot, and a matrix call has no row order"""
+    s1, s2 = _edit.aa_sets()
+    read = lambda h, names: [h.get_tunable(name) for name in names]
+    with HipOverlap(_edit.options_of("aa", True, device=0)) as h:
+        h.hamming_neighbors(s1, s2, 3)
+        hamming = read(h, HAMMING_TIMERS)
+        assert h.get_tunable("hamming_copy_us") > 0
+        h.edit_neighbors(s1, s2, 3)
+        assert read(h, HAMMING_TIMERS) == hamming
+        edit = read(h, EDIT_TIMERS)
+        h.hamming_neighbors(s1, s2, 3)
+        assert read(h, EDIT_TIMERS) == edit
+        assert h.get_tunable("hamming_copy_us") > 0
+        h.edit_matrix(s1, s2, 3)
+        assert h.get_tunable("edit_copy_us") > 0 and h.get_tunable("edit_order_us") == 0
+
+
+def test_a_bad_view_of_set_2_is_refused_before_the_length_of_set_1():
+    """both views are looked at before either set is staged: a NULL view of set 2 is what the call answers, not the
+    257 residues of set 1 that staging would refuse"""
+    rng = np.random.default_rng(257)
+    long = _neighbors._set_of_rows(rng.integers(0, 20, size=(1, 257), dtype=np.uint8), 2, 1)
+    with HipOverlap(Options(differences=1, n_v_genes=2, n_j_genes=2, device=0)) as h:
+        assert raw(h, _view(long), None, 2, 0)[0] == CMPR_EINVAL
+        assert h._lib.cmpr_last_error(h._ctx).decode() == "set view is NULL"
+        with pytest.raises(HipError) as e:
+            h.edit_neighbors(long, long, 2)
+        assert e.value.code == CMPR_EUNSUPPORTED

@@ -18,7 +18,7 @@ from compairr_amd.sets import AA
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "include", "compairr_hip.h")
-SOURCE = os.path.join(HERE, "..", "compairr_amd", "csrc", "hamming.hip")
+SOURCE = os.path.join(HERE, "..", "compairr_amd", "csrc", "allpairs.h")
 NAMES = ("cmpr_hamming_matrix", "cmpr_hamming_matrix_device", "cmpr_hamming_neighbors", "cmpr_hamming_neighbors_device")
 
 

@@ -4,8 +4,8 @@
 #   tools/kernel_resources.sh            main TU + resolve + variant 2 (8 waves)
 #   tools/kernel_resources.sh 1 8        variant 1, 8 waves per workgroup
 #   tools/kernel_resources.sh all        every object of the library that holds a probe or resolve kernel (the
-#                                        Makefile's TU_OBJS) and the two files of the row sorters (csr_rows.h), one
-#                                        "== object ==" block each, JOBS (default 8) compilations side by side
+#                                        Makefile's TU_OBJS), the two files of the row sorters (csr_rows.h) and the
+#                                        three of the all-against-all calls (allpairs.h), one "== object ==" block each, JOBS (default 8) compilations side by side
 cd "$(dirname "$0")/.." || exit 1
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -c -Rpass-analysis=kernel-resource-usage -o /dev/null"
 run() {
@@ -39,6 +39,9 @@ if [ "$1" = all ]; then
   done
   one neighbors compairr_amd/csrc/neighbors.hip
   one existence compairr_amd/csrc/existence.hip
+  one allpairs compairr_amd/csrc/allpairs.hip
+  one hamming compairr_amd/csrc/hamming.hip
+  one edit compairr_amd/csrc/edit.hip
   wait
   cat "$tmp"/* | grep -v 'rocprim::'          # (the library's own kernels: hipcub's instantiations are hundreds)
 elif [ -n "$1" ]; then

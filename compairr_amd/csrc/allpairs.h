@@ -22,6 +22,11 @@
  *            count / fill: a lane counts the hits of its (query, segment), the counts are summed in (query,
  *            segment) order (hipcub), and the same walk writes every hit and its distance at the lane's running
  *            offset.  A caller whose walk is not in number order has the rows sorted afterwards (csr_rows.h).
+ *            link: the cluster calls, the set against itself: a match unites the two sequences' trees in the forest
+ *            of link_forest.h over the ORIGINAL sequence numbers.  The caller's walk visits every unordered pair once.
+ *            Beside every staged reference lies a snapshot of its root; a lane keeps its own root in a register,
+ *            skips a match whose snapshot equals it and looks its root up again after a link it made.  No count
+ *            array, no pair list.  What follows the launch is pairs_clusters (cluster.hip's passes).
  *
  * The (query, segment) count array has n1 x S words, S <= PAIRS_MAX_SEGMENTS; the automatic S is above 1 only while
  * the query tiles alone do not fill the machine (S <= ceil(8 x CUs / workgroups)), which bounds it by
@@ -31,6 +36,7 @@
 #define COMPAIRR_AMD_ALLPAIRS_H
 
 #include "context.h"
+#include "link_forest.h"
 
 namespace cmpr {
 
@@ -119,6 +125,12 @@ struct PairSinks {
   uint32_t        cells;
 };
 
+/* ... and of the link sink, beside them */
+struct PairLinks {
+  uint32_t       *parent;          /* the forest, over original sequence numbers (link_forest.h) */
+  uint32_t        snapshot;        /* 1: matches whose two root snapshots are equal are skipped */
+};
+
 /* The compare kernel, Params::sink filled for the matrix, over the runs (`launch`), and the matrix to the caller.
    ms: the caller's timers, [1] the compare, [copy_slot] the copy-out of the host variant. */
 int pairs_matrix(cmpr_context *c, const PairSets &W, PairSinks &K, void *matrix_out, bool on_device,
@@ -134,6 +146,15 @@ int pairs_neighbors(cmpr_context *c, const std::string &who, const PairSets &W, 
                     uint64_t capacity, uint64_t *row_start_out, uint32_t *hit_out, uint16_t *dist_out,
                     uint64_t *n_edges_out, bool on_device, const std::function<int()> &launch, bool rows_always,
                     double *ms, int order_slot, int copy_slot);
+
+/* The clusters of set S against itself: the forest over the original sequence numbers (cluster.hip), `launch` -- the
+   compare kernel with the link sink over the runs, every unordered matching pair united --, flat labels and sizes, and
+   the results of the plain call (T == NULL: L's label / size) or the table pass (T's four arrays, from labels and sizes
+   of nobody's).  ms[1]: the links, the flatten and the sizes; ms[copy_slot]: the copy-out of the host variant of the
+   plain call; the table pass times itself (cl_ms[1]). */
+int pairs_clusters(cmpr_context *c, const HmSet &S, bool snapshot, bool on_device, ClusterLinks &L, ClusterTableOut *T,
+                   uint64_t *n_clusters_out, const std::function<int(const PairLinks &)> &launch, double *ms,
+                   int copy_slot);
 
 /* kernel_for(form) over every run: Params has blk_base and segments */
 template <typename Params, typename KernelFor>
@@ -185,7 +206,7 @@ struct PairQuery {
   __device__ __forceinline__ bool active() const { return qi < nq; }
 };
 
-enum { SINK_CSR = 0, SINK_MATRIX = 1 };        /* (hamming.hip has two more of its own) */
+enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2 };   /* (hamming.hip has one more of its own, SINK_NEAREST = 3) */
 
 /* a pointer into LDS, typed as such: what is reached through it stays an LDS instruction, also where the code chooses
    between it and a pointer to global memory (the cells of the matrix sink) */
@@ -298,6 +319,44 @@ struct PairSink {
       }
     }
   }
+};
+
+/* link: st_root holds a snapshot of every staged reference's root, `root` the lane's own when it last looked.  The
+   kernel's st_root array has PAIRS_STAGE_MAX words with SINK_LINK (one otherwise) */
+template <>
+struct PairSink<SINK_LINK> {
+  const PairLinks K;               /* (a copy, as the other sinks' K) */
+  const Lds<uint32_t> st_id, st_root;
+  uint32_t qorig = 0, root = 0;
+  __device__ __forceinline__ PairSink(const PairLinks &K_, const PairLds &L, uint32_t *st_root_)
+      : K(K_), st_id(L.id), st_root((Lds<uint32_t>)st_root_) {}
+  __device__ __forceinline__ void zero_matrix() const {}
+  __device__ __forceinline__ void init(uint32_t qorig_, uint32_t)
+  {
+    qorig = qorig_;
+    if (K.snapshot)
+      root = link_root(K.parent, qorig);
+  }
+  __device__ __forceinline__ bool stages() const { return true; }
+  __device__ __forceinline__ void stage(uint32_t r, uint32_t id) const
+  {
+    st_id[r] = id;
+    if (K.snapshot)
+      st_root[r] = link_root(K.parent, id);
+  }
+  /* (cluster.cc:165-211 lists the pair, :276-410 walks the lists: here the two trees become one.)  In a dense
+     group almost every match joins two sequences that share a root already: equal snapshots prove it --
+     trees only merge, whatever was once under a root stays in its component -- and cost no walk; unequal
+     ones, stale or not, fall through to link_pair, after which the lane looks its root up again. */
+  __device__ __forceinline__ void match(uint32_t r, uint32_t)
+  {
+    if (!K.snapshot || st_root[r] != root) {
+      link_pair(K.parent, qorig, st_id[r]);
+      if (K.snapshot)
+        root = link_root(K.parent, qorig);
+    }
+  }
+  __device__ __forceinline__ void end(bool, uint32_t, uint32_t) const {}
 };
 
 }  // namespace cmpr

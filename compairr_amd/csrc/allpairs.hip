@@ -1,6 +1,6 @@
 /*
  * allpairs.hip -- the host side of allpairs.h: the refusals, a staged set grouped and packed, the segment count, and
- * the two drivers around a caller's compare kernel -- the matrix, and the neighbours as CSR.
+ * the drivers around a caller's compare kernel -- the matrix, the neighbours as CSR, and the clusters.
  */
 #include "allpairs.h"
 #include "csr_rows.h"
@@ -350,5 +350,37 @@ int cmpr::pairs_neighbors(cmpr_context *c, const std::string &who, const PairSet
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     ms[copy_slot] = ms_since(t0);
   }
+  return CMPR_OK;
+}
+
+int cmpr::pairs_clusters(cmpr_context *c, const HmSet &S, bool snapshot, bool on_device, ClusterLinks &L,
+                         ClusterTableOut *T, uint64_t *n_clusters_out,
+                         const std::function<int(const PairLinks &)> &launch, double *ms, int copy_slot)
+{
+  int rc;
+  auto t0 = std::chrono::steady_clock::now();
+  const bool table = T != nullptr;
+  const uint64_t n = S.n;
+  if (n) {
+    if ((rc = cmpr_cluster_forest(c, n, L))) return rc;
+    if ((rc = launch(PairLinks{L.parent.b.p, snapshot ? 1u : 0u})))
+      return rc;
+    if ((rc = cmpr_cluster_flatten(c, n, table || L.size.wanted(), L)))
+      return rc;
+  }
+  if (table)
+    return cmpr_cluster_table_pass(c, L, c->opt.ignore_counts ? nullptr : S.cnt.b.p, *T, n_clusters_out, t0, &ms[1]);
+  if (n && !on_device) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ms[1] = ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
+      return rc;
+    ms[copy_slot] = ms_since(t0);
+    return CMPR_OK;
+  }
+  if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
+    return rc;
+  ms[1] = ms_since(t0);
   return CMPR_OK;
 }

@@ -369,6 +369,7 @@ const Tunable TUNABLES[] = {
   {"hamming_segments", F(hamming_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
   {"hamming_generic", F(hamming_generic), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
   {"hamming_link_snapshot", F(hamming_link_snapshot), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  {"edit_link_snapshot", F(edit_link_snapshot), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
   /* TEST ONLY: the staging, the segments and the column words of cmpr_edit_* (edit.hip; tests/test_edit_gpu.py) */
   {"edit_stage_refs", F(edit_stage_refs), 0, 65536, LOCK_NEVER, T_NO_PLAN, " must be 0..65536"},
   {"edit_segments", F(edit_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},

@@ -213,6 +213,7 @@ struct cmpr_context {
   /* TEST ONLY, of cmpr_edit_* (edit.hip): references staged per LDS piece (0 = as many as fit), the segment count
      (0 = automatic), at least this many 64-bit words per column (0 = from the reference's length) */
   int64_t edit_stage_refs = 0, edit_segments = 0, edit_words = 0;
+  int64_t edit_link_snapshot = 1;     /* TEST ONLY, of cmpr_edit_cluster*: 0 = every match goes to link_pair */
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */

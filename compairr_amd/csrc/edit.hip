@@ -1,6 +1,7 @@
 /*
- * edit.hip -- the all-against-all path under EDIT distance, for any d: cmpr_edit_neighbors / _device and
- * cmpr_edit_matrix / _device.  A pair (i of set 1, j of set 2) matches when the two sequences have the same V and J
+ * edit.hip -- the all-against-all path under EDIT distance, for any d: cmpr_edit_neighbors / _device,
+ * cmpr_edit_matrix / _device, and the single-linkage clusters of that relation, cmpr_edit_cluster / _device and
+ * cmpr_edit_cluster_table / _device.  A pair (i of set 1, j of set 2) matches when the two sequences have the same V and J
  * gene numbers unless ignore_genes and their Levenshtein distance -- substitution, insertion and deletion cost 1 each --
  * is at most `differences`.  The reference has indels at d = 1 only (its variant enumeration explodes beyond); nothing
  * is enumerated or hashed here: every query is compared with every sequence of every group it can match.
@@ -32,6 +33,13 @@
  *            the rows are sorted afterwards by csr_rows.h with the 64-bit key (hit << 16 | distance) -- the hit alone
  *            without distance_out --, rows beyond LDS_MAX by hipcub's device-wide sort.  The hits of a row are
  *            distinct: the order is total, the bytes do not depend on the schedule.
+ *            link (the cluster calls: the set against itself): allpairs.h's forest sink.  A job keeps the partners of
+ *            its own length and longer: an unordered pair of two lengths is seen from the shorter side, and a longer
+ *            partner is walked in full.  The job's OWN group is walked as hm_compare_kernel walks a group under this
+ *            sink: the workgroup of the queries [256b, 256b + 256) walks [256b + 1, nr), its segments divide that
+ *            range, a wave skips the staged pieces at or below its first query, a lane links only positions above its
+ *            own.  Every unordered pair once, (i, i) never; the empty group is linked among itself (the distance of
+ *            two empty sequences is 0) and to the groups of up to d residues.  Behind the launch: pairs_clusters.
  *
  * Nothing here writes the resident sets, plans or statistics of the context.
  */
@@ -48,12 +56,19 @@ namespace {
 constexpr uint32_t ED_MAX_LEN = 256;           /* residues of the longest sequence: four 64-bit column words */
 constexpr uint32_t ED_REG_RESIDUES = 64;       /* a query of more residues is read from global memory (NW = 0) */
 constexpr uint32_t ED_PEQ_WORDS = 2048;        /* 64-bit words of Peq staged at a time (16 KiB) */
+/* link sink: references of the longest automatic segment.  A sixteenth of hamming.hip's HM_LINK_SEGMENT, as a reference
+   costs some twenty times as much here: 1M CDR3aa at d = 3, V/J matched (the largest group of 13 154), link kernel
+   132 ms with HM_LINK_SEGMENT (one segment), 63 ms from 16 segments on; with ignore_genes (196 330) 2 218 ms in 12
+   segments, 2 202 in 64 (profiles/r23/edit_cluster.txt) */
+constexpr uint32_t ED_LINK_SEGMENT = 1024;
 
 /* a set-2 group a job is compared with */
 struct EdPartner {
   uint64_t pk_off;                 /* first packed word of the group */
   uint32_t r0, nr;                 /* positions in set 2's sorted order */
-  uint32_t len, stride;            /* residues and packed words per sequence */
+  uint32_t len;                    /* residues per sequence */
+  uint16_t stride, own;            /* packed words per sequence (at most 64); 1: the group IS the job's own one (the
+                                      cluster calls: the set against itself) */
 };
 
 /* a set-1 group and its partners */
@@ -74,6 +89,19 @@ struct EdParams {
   uint32_t        d, stage_refs, min_words;
   uint32_t        blk_base;        /* workgroup number of this launch's first workgroup */
   PairSinks       sink;            /* count / fill, matrix (allpairs.h) */
+  PairLinks       link;            /* link (allpairs.h) */
+};
+
+/* the sinks of ed_compare_kernel: allpairs.h's, each built from its fields of the parameters */
+template <int SINK>
+struct EdSink : PairSink<SINK> {
+  __device__ __forceinline__ EdSink(const EdParams &P, const PairLds &L, uint32_t *)
+      : PairSink<SINK>(P.sink, P.segments, L) {}
+};
+template <>
+struct EdSink<SINK_LINK> : PairSink<SINK_LINK> {
+  __device__ __forceinline__ EdSink(const EdParams &P, const PairLds &L, uint32_t *st_root)
+      : PairSink<SINK_LINK>(P.link, L, st_root) {}
 };
 
 /* One column of the edit-distance matrix further: the text residue whose Peq words lie at `peq`.  pv / mv: the
@@ -122,16 +150,22 @@ ed_compare_kernel(const EdParams P)
   __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? PAIRS_STAGE_MAX : 1];
   __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? PAIRS_STAGE_MAX : 1];
   __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? PAIRS_MAT_CELLS : 1];
+  __shared__ uint32_t st_root[SINK == SINK_LINK ? PAIRS_STAGE_MAX : 1];
 
   const uint32_t blk = P.blk_base + blockIdx.x;
   const EdJob jb = pairs_entry_of(P.jobs, P.njobs, blk);
   const PairQuery Q(jb, blk, P.ord1);
-  const uint32_t qpos = Q.qpos, qorig = Q.qorig;
+  const uint32_t qi = Q.qi, qpos = Q.qpos, qorig = Q.qorig;
   const bool active = Q.active();
   const uint32_t qlen = jb.len;
   const uint32_t seg = blockIdx.y;
+  /* link sink, the job's own group: position order is number order (the stable sort), so an unordered pair is walked
+     once, by the lane of its smaller position, and a wave skips the staged references at or below its first query */
+  const uint32_t wg_q0 = (blk - jb.blk0) * PAIRS_WG;
+  const uint32_t wave_q0 = SINK == SINK_LINK
+      ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(wg_q0 + (threadIdx.x & ~(WAVE - 1u)))) : 0u;
 
-  PairSink<SINK> S(P.sink, P.segments, PairLds(st_id, st_rep, st_cnt, st_mat));
+  EdSink<SINK> S(P, PairLds(st_id, st_rep, st_cnt, st_mat), st_root);
   S.zero_matrix();                                                      /* (a barrier follows before the first match) */
 
   const uint32_t *const qw = P.pk1 + jb.pk1 + (uint64_t)(qpos - jb.q0) * jb.stride;
@@ -147,6 +181,7 @@ ed_compare_kernel(const EdParams P)
   /* the references e0 .. e1 - 1 of partner pt, their columns W words long */
   auto walk = [&](const EdPartner &pt, uint32_t e0, uint32_t e1, auto words) {
     constexpr int W = decltype(words)::value;
+    const bool own = SINK == SINK_LINK && pt.own;
     const uint32_t n = pt.len;
     const uint32_t sw = n ? (n - 1) >> 6 : 0u, sb = n ? (n - 1) & 63u : 0u;
     uint32_t R = ED_PEQ_WORDS / (A * W);
@@ -175,7 +210,8 @@ ed_compare_kernel(const EdParams P)
       for (uint32_t r = threadIdx.x; r < cnt; r += PAIRS_WG)
         S.stage(r, P.ord2[pt.r0 + e + r]);
       __syncthreads();
-      for (uint32_t r = 0; r < cnt; r++) {
+      const uint32_t r0 = own && wave_q0 >= e ? min(wave_q0 - e + 1u, cnt) : 0u;
+      for (uint32_t r = r0; r < cnt; r++) {
         uint32_t dd = n;
         if (n == 0) {
           dd = qlen;                                                    /* an empty reference: every residue inserted */
@@ -206,7 +242,7 @@ ed_compare_kernel(const EdParams P)
             }
           }
         }
-        if (dd <= P.d && active)
+        if (dd <= P.d && active && (!own || e + r > qi))
           S.match(r, dd);
       }
     }
@@ -214,8 +250,11 @@ ed_compare_kernel(const EdParams P)
 
   for (uint32_t p = jb.p0; p < jb.p0 + jb.np; p++) {
     const EdPartner pt = P.partners[p];
-    const uint32_t e0 = (uint32_t)((uint64_t)pt.nr * seg / P.segments);
-    const uint32_t e1 = (uint32_t)((uint64_t)pt.nr * (seg + 1) / P.segments);
+    /* (the own group: the workgroup whose first query sits at position b walks the references behind b only, and its
+       segments divide THAT range) */
+    const uint32_t w0 = SINK == SINK_LINK && pt.own ? min(wg_q0 + 1u, pt.nr) : 0u;
+    const uint32_t e0 = w0 + (uint32_t)((uint64_t)(pt.nr - w0) * seg / P.segments);
+    const uint32_t e1 = w0 + (uint32_t)((uint64_t)(pt.nr - w0) * (seg + 1) / P.segments);
     if (e0 >= e1)
       continue;                                                         /* (the whole workgroup) */
     uint32_t words = pt.len <= 64 ? 1u : pt.len <= 128 ? 2u : 4u;
@@ -271,8 +310,10 @@ struct EdWork : PairSets {
   PairRuns       runs;             /* form: ed_form_of */
 };
 
+/* triangular (the cluster calls, set2 == set1): a job keeps the partners of its own length and longer -- an unordered
+   pair of two lengths is seen from the shorter side -- and its own group is marked as such */
 int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
-             int64_t differences, bool on_device, EdWork &J)
+             int64_t differences, bool on_device, EdWork &J, bool triangular = false)
 {
   int rc;
   if ((rc = pairs_stage(c, set1, set2, on_device, J, [&](const HmSet &H) {
@@ -299,7 +340,7 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
   for (size_t a = 0; a < A.groups.size(); a++) {
     const HmGroup &ga = A.groups[a];
     const uint64_t genes_of = A.keys[a] % vj;
-    const uint32_t first = ga.len > d ? ga.len - d : 0u;
+    const uint32_t first = triangular ? ga.len : ga.len > d ? ga.len - d : 0u;
     const size_t p0 = partners.size();
     for (auto it = std::lower_bound(lens2.begin(), lens2.end(), first); it != lens2.end() && *it <= ga.len + d; ++it) {
       const uint64_t key = (uint64_t)*it * vj + genes_of;
@@ -307,7 +348,8 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
       if (k == B.keys.end() || *k != key)
         continue;
       const HmGroup &gb = B.groups[(size_t)(k - B.keys.begin())];
-      partners.push_back(EdPartner{gb.pk_off, gb.start, gb.count, gb.len, gb.stride});
+      partners.push_back(EdPartner{gb.pk_off, gb.start, gb.count, gb.len, (uint16_t)gb.stride,
+                                   (uint16_t)(triangular && gb.len == ga.len ? 1u : 0u)});
       nr_max = std::max(nr_max, gb.count);
     }
     if (partners.size() == p0)
@@ -331,7 +373,9 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
   P.jobs = J.jobs.b.p;
   P.partners = J.partners.b.p;
   P.njobs = (uint32_t)jobs.size();
-  P.segments = pairs_segments(c, c->edit_segments, blocks, nr_max);
+  /* (the link sink's workgroups walk what lies behind them in their own group: as hm_setup, no segment longer than
+     ED_LINK_SEGMENT references) */
+  P.segments = pairs_segments(c, c->edit_segments, blocks, nr_max, triangular ? ED_LINK_SEGMENT : 0u);
   P.pk1 = A.pk.b.p; P.pk2 = B.pk.b.p;
   P.ord1 = A.ord.b.p; P.ord2 = B.ord.b.p;
   P.d = d;
@@ -396,7 +440,78 @@ int edit_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
                          on_device, [&] { return ed_launch<SINK_CSR>(c, J); }, true, c->ed_ms, 2, 3);
 }
 
+/* cmpr_edit_cluster* and cmpr_edit_cluster_table*: the set against itself through the link sink, every unordered pair
+   once; what follows the launch is pairs_clusters (allpairs.h).  The plain call (T == NULL) fills L's label / size, the
+   table call T's four arrays from labels and sizes of nobody's. */
+int edit_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differences, bool on_device, ClusterLinks &L,
+                      ClusterTableOut *T, uint64_t *n_clusters_out)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  const std::string who = T ? "cmpr_edit_cluster_table" : "cmpr_edit_cluster";
+  if (n_clusters_out)
+    *n_clusters_out = 0;
+  int rc;
+  if ((rc = hm_refusals(c, who, set, set, differences, HM_CLUSTERS, on_device, true)))
+    return rc;
+  auto t0 = std::chrono::steady_clock::now();
+  for (double &t : c->ed_ms)
+    t = 0;
+  if (T)
+    c->cl_ms[0] = c->cl_ms[1] = 0;
+  EdWork J;
+  if ((rc = ed_setup(c, who, set, set, differences, on_device, J, true)))
+    return rc;
+  c->ed_ms[0] = ms_since(t0);
+  return pairs_clusters(c, *J.s1, c->edit_link_snapshot != 0, on_device, L, T, n_clusters_out,
+                        [&](const PairLinks &K) {
+                          J.P.link = K;
+                          return ed_launch<SINK_LINK>(c, J);
+                        },
+                        c->ed_ms, 3);
+}
+
 }  // namespace
+
+extern "C" int cmpr_edit_cluster(cmpr_context *c, const cmpr_set_view *set, int64_t differences, uint32_t *label_out,
+                                 uint32_t *size_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    ClusterLinks L(label_out, size_out, false);
+    return edit_cluster_impl(c, set, differences, false, L, nullptr, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_edit_cluster_device(cmpr_context *c, const cmpr_set_view *d_set, int64_t differences,
+                                        uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    ClusterLinks L(d_label_out, d_size_out, true);
+    return edit_cluster_impl(c, d_set, differences, true, L, nullptr, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_edit_cluster_table(cmpr_context *c, const cmpr_set_view *set, int64_t differences,
+                                       uint32_t *cluster_of_out, uint64_t *cluster_start_out, uint32_t *member_out,
+                                       uint64_t *count_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    ClusterLinks L(nullptr, nullptr, false);
+    ClusterTableOut T(cluster_of_out, cluster_start_out, member_out, count_out, false);
+    return edit_cluster_impl(c, set, differences, false, L, &T, n_clusters_out);
+  });
+}
+
+extern "C" int cmpr_edit_cluster_table_device(cmpr_context *c, const cmpr_set_view *d_set, int64_t differences,
+                                              uint32_t *d_cluster_of_out, uint64_t *d_cluster_start_out,
+                                              uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out)
+{
+  return guarded(c, [&] {
+    ClusterLinks L(nullptr, nullptr, true);
+    ClusterTableOut T(d_cluster_of_out, d_cluster_start_out, d_member_out, d_count_out, true);
+    return edit_cluster_impl(c, d_set, differences, true, L, &T, n_clusters_out);
+  });
+}
 
 extern "C" int cmpr_edit_matrix(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2,
                                 int64_t differences, uint64_t *matrix_out)

@@ -17,9 +17,9 @@
  *            from global memory (generic form: groups of more than HAMMING_REG_WORDS words; a reference that does
  *            not fit the LDS buffer is staged in runs of words).  All lanes read the same reference word: an LDS
  *            broadcast.  Differing residues per word: xor, SWAR, popcount.
- *   sinks    link (the cluster calls: the set against itself, every group paired with itself): the forest of
- *            link_forest.h over the ORIGINAL sequence numbers.  Position order inside a group is number order, so the
- *            lane whose query sits at position qi links only references at positions above qi: every unordered pair
+ *   sinks    link (the cluster calls: the set against itself, every group paired with itself): allpairs.h's sink, the
+ *            forest of link_forest.h over the ORIGINAL sequence numbers.  Position order inside a group is number
+ *            order, so the lane whose query sits at position qi links only references at positions above qi: every unordered pair
  *            once, (i, i) never.  The workgroup of the queries [256b, 256b + 256) walks [256b + 1, nr), its segments
  *            divide that range, and a wave skips what lies at or below its own first query.  Beside every staged
  *            reference lies a snapshot of its root; a lane keeps its own root in a register, skips a match whose
@@ -65,9 +65,7 @@ struct HmParams {
   uint32_t        d, stage_refs;
   uint32_t        blk_base;        /* workgroup number of this launch's first workgroup */
   PairSinks       sink;            /* count / fill, matrix (allpairs.h); rep1, rep2 also of the nearest sink */
-  /* link */
-  uint32_t       *parent;          /* the forest, over original sequence numbers (link_forest.h) */
-  uint32_t        snapshot;        /* 1: matches whose two root snapshots are equal are skipped */
+  PairLinks       link;            /* link (allpairs.h) */
   /* nearest (sink.rep1, sink.rep2 read with other_rep only) */
   uint32_t        floor;           /* a candidate differs at this many positions or more */
   uint32_t        one_set;         /* 1: set 2 IS set 1, a query is no candidate of its own */
@@ -79,7 +77,7 @@ struct HmParams {
   uint32_t       *nn_slot_ties;    /* ... and the references of the segment at that distance */
 };
 
-enum { SINK_LINK = 2, SINK_NEAREST = 3 };      /* (behind allpairs.h's SINK_CSR, SINK_MATRIX) */
+enum { SINK_NEAREST = 3 };                     /* (behind allpairs.h's SINK_CSR, SINK_MATRIX, SINK_LINK) */
 
 constexpr uint32_t HM_NONE = 0xffffffffu;      /* nearest sink: the infinite distance, and "no sequence" */
 
@@ -94,49 +92,19 @@ __device__ __forceinline__ uint32_t diff_word(uint32_t a, uint32_t b)
   return (uint32_t)__popc((x + 0x7f7f7f7fu) & 0x80808080u);
 }
 
-/* The sinks of hm_compare_kernel behind PairSink's interface (allpairs.h): the count / fill and matrix sinks ARE
-   PairSink; the two below are this file's own.  pr, qi: the workgroup's pair and the lane's query within its group. */
+/* The sinks of hm_compare_kernel behind PairSink's interface (allpairs.h): the count / fill, matrix and link sinks ARE
+   PairSink; the nearest one below is this file's own.  pr, qi: the workgroup's pair and the lane's query within its group. */
 template <int SINK>
 struct HmSink : PairSink<SINK> {
   __device__ __forceinline__ HmSink(const HmParams &P, const HmPair &, uint32_t, const PairLds &L, uint32_t *)
       : PairSink<SINK>(P.sink, P.segments, L) {}
 };
 
-/* link: st_root holds a snapshot of every staged reference's root, `root` the lane's own when it last looked */
+/* link: allpairs.h's, with the forest and the snapshot flag of the parameters */
 template <>
-struct HmSink<SINK_LINK> {
-  const HmParams P;                /* (a copy, as PairSink's K) */
-  const Lds<uint32_t> st_id, st_root;
-  uint32_t qorig = 0, root = 0;
-  __device__ __forceinline__ HmSink(const HmParams &P_, const HmPair &, uint32_t, const PairLds &L, uint32_t *st_root_)
-      : P(P_), st_id(L.id), st_root((Lds<uint32_t>)st_root_) {}
-  __device__ __forceinline__ void zero_matrix() const {}
-  __device__ __forceinline__ void init(uint32_t qorig_, uint32_t)
-  {
-    qorig = qorig_;
-    if (P.snapshot)
-      root = link_root(P.parent, qorig);
-  }
-  __device__ __forceinline__ bool stages() const { return true; }
-  __device__ __forceinline__ void stage(uint32_t r, uint32_t id) const
-  {
-    st_id[r] = id;
-    if (P.snapshot)
-      st_root[r] = link_root(P.parent, id);
-  }
-  /* (cluster.cc:165-211 lists the pair, :276-410 walks the lists: here the two trees become one.)  In a dense
-     group almost every match joins two sequences that share a root already: equal snapshots prove it --
-     trees only merge, whatever was once under a root stays in its component -- and cost no walk; unequal
-     ones, stale or not, fall through to link_pair, after which the lane looks its root up again. */
-  __device__ __forceinline__ void match(uint32_t r, uint32_t)
-  {
-    if (!P.snapshot || st_root[r] != root) {
-      link_pair(P.parent, qorig, st_id[r]);
-      if (P.snapshot)
-        root = link_root(P.parent, qorig);
-    }
-  }
-  __device__ __forceinline__ void end(bool, uint32_t, uint32_t) const {}
+struct HmSink<SINK_LINK> : PairSink<SINK_LINK> {
+  __device__ __forceinline__ HmSink(const HmParams &P, const HmPair &, uint32_t, const PairLds &L, uint32_t *st_root)
+      : PairSink<SINK_LINK>(P.link, L, st_root) {}
 };
 
 /* nearest: no threshold, so near() for EVERY reference in place of match() for the matching ones.  The smallest
@@ -558,9 +526,9 @@ int hamming_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_
   return CMPR_OK;
 }
 
-/* cmpr_hamming_cluster* and cmpr_hamming_cluster_table*: the set against itself through the link sink, then the
-   flatten, size and table passes of cluster.hip.  The plain call (T == NULL) fills L's label / size, the table call
-   T's four arrays from labels and sizes of nobody's. */
+/* cmpr_hamming_cluster* and cmpr_hamming_cluster_table*: the set against itself through the link sink, then
+   pairs_clusters (allpairs.h): the flatten, size and table passes of cluster.hip.  The plain call (T == NULL) fills L's
+   label / size, the table call T's four arrays from labels and sizes of nobody's. */
 int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differences, bool on_device,
                          ClusterLinks &L, ClusterTableOut *T, uint64_t *n_clusters_out)
 {
@@ -581,35 +549,12 @@ int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t diff
   if ((rc = hm_setup(c, who, set, set, differences, on_device, J, true)))
     return rc;
   c->hm_ms[0] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
-
-  /* the forest over the original sequence numbers; every unordered pair of every group linked; labels and sizes */
-  const uint64_t n = J.s1->n;
-  if (n) {
-    if ((rc = cmpr_cluster_forest(c, n, L))) return rc;
-    J.P.parent = L.parent.b.p;
-    J.P.snapshot = c->hamming_link_snapshot ? 1u : 0u;
-    if ((rc = hm_launch<SINK_LINK>(c, J)))
-      return rc;
-    if ((rc = cmpr_cluster_flatten(c, n, table || L.size.wanted(), L)))
-      return rc;
-  }
-  if (table)
-    return cmpr_cluster_table_pass(c, L, c->opt.ignore_counts ? nullptr : J.s1->cnt.b.p, *T, n_clusters_out, t0,
-                                   &c->hm_ms[1]);
-  if (n && !on_device) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->hm_ms[1] = ms_since(t0);
-    t0 = std::chrono::steady_clock::now();
-    if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
-      return rc;
-    c->hm_ms[2] = ms_since(t0);
-    return CMPR_OK;
-  }
-  if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
-    return rc;
-  c->hm_ms[1] = ms_since(t0);
-  return CMPR_OK;
+  return pairs_clusters(c, *J.s1, c->hamming_link_snapshot != 0, on_device, L, T, n_clusters_out,
+                        [&](const PairLinks &K) {
+                          J.P.link = K;
+                          return hm_launch<SINK_LINK>(c, J);
+                        },
+                        c->hm_ms, 2);
 }
 
 }  // namespace

@@ -1,6 +1,6 @@
 /*
- * link_forest.h -- the union-find forest that cmpr_cluster (kernels.h score_match, link mode) and
- * cmpr_hamming_cluster (hamming.hip, SINK_LINK) unite their matching pairs in: one 32-bit word per sequence,
+ * link_forest.h -- the union-find forest that cmpr_cluster (kernels.h score_match, link mode), cmpr_hamming_cluster and
+ * cmpr_edit_cluster (allpairs.h, SINK_LINK) unite their matching pairs in: one 32-bit word per sequence,
  * parent[i] == i before the first link.  Written once, included by both.
  */
 #ifndef COMPAIRR_AMD_LINK_FOREST_H

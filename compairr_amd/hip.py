@@ -41,6 +41,8 @@ EXPORTS = [
     "cmpr_hamming_nearest", "cmpr_hamming_nearest_device",
     "cmpr_edit_neighbors", "cmpr_edit_neighbors_device",
     "cmpr_edit_matrix", "cmpr_edit_matrix_device",
+    "cmpr_edit_cluster", "cmpr_edit_cluster_device",
+    "cmpr_edit_cluster_table", "cmpr_edit_cluster_table_device",
 ]
 
 NEAREST_OTHER_REPERTOIRE = 1      # CMPR_NEAREST_OTHER_REPERTOIRE
@@ -162,6 +164,8 @@ def _argtypes() -> dict:
         "cmpr_hamming_nearest": [ctx, view, view, C.c_int64, C.c_uint32, ptr, ptr, ptr, u64p],
         "cmpr_edit_neighbors": [ctx, view, view, C.c_int64, C.c_uint64, ptr, ptr, ptr, u64p],
         "cmpr_edit_matrix": [ctx, view, view, C.c_int64, ptr],
+        "cmpr_edit_cluster": [ctx, view, C.c_int64, ptr, ptr, u64p],
+        "cmpr_edit_cluster_table": [ctx, view, C.c_int64, ptr, ptr, ptr, ptr, u64p],
     }
     for name, args in twins.items():
         table[name] = table[name + "_device"] = args
@@ -653,6 +657,32 @@ class HipOverlap:
         self._check(self._lib.cmpr_edit_matrix_device(self._ctx, C.byref(view1), C.byref(view2), differences,
                                                       C.c_void_p(d_matrix or None)))
 
+    # ---- single-linkage clusters under edit distance at any d (include/compairr_hip.h: cmpr_edit_cluster*) ----
+
+    def edit_cluster(self, s: RepertoireSet, differences: int):
+        """(label uint32[n], size uint32[n], n_clusters) of `s` as cluster() gives them, under the pair relation of
+        edit_neighbors(s, s, differences): any `differences` >= 0.  The context's own `differences`, `indels` and
+        resident sets play no part, and `s` is not resident afterwards."""
+        return self._labels(self._lib.cmpr_edit_cluster, s, differences)
+
+    def edit_cluster_device(self, view: _SetView, differences: int, d_label: int = 0, d_size: int = 0) -> int:
+        """The same for a view of device pointers (device_view): labels and sizes are written to the device
+        arrays d_label and d_size (uint32[n] each; 0: not wanted); returns n_clusters."""
+        return self._into_device(self._lib.cmpr_edit_cluster_device, view, (differences,), d_label, d_size)
+
+    def edit_cluster_table(self, s: RepertoireSet, differences: int):
+        """(cluster_of uint32[n], cluster_start uint64[K + 1], members uint32[n], count uint64[K]) of `s` as
+        cluster_table() gives them, under the pair relation of edit_neighbors(s, s, differences)."""
+        return self._table(self._lib.cmpr_edit_cluster_table, s, differences)
+
+    def edit_cluster_table_device(self, view: _SetView, differences: int, d_cluster_of: int = 0,
+                                  d_cluster_start: int = 0, d_member: int = 0, d_count: int = 0) -> int:
+        """The same for a view of device pointers (device_view), into device arrays: d_cluster_of and d_member
+        (uint32[n]), d_cluster_start (uint64[n + 1], K + 1 written) and d_count (uint64[n], K written); 0: not
+        wanted.  Returns K."""
+        return self._into_device(self._lib.cmpr_edit_cluster_table_device, view, (differences,), d_cluster_of,
+                                 d_cluster_start, d_member, d_count)
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -793,6 +823,22 @@ def edit_matrix(set1: RepertoireSet, set2: RepertoireSet, opt: Options, differen
     part.  `tunables` are set on the context first (the result never depends on them)."""
     with _context(opt, tunables) as h:
         return h.edit_matrix(set1, set2, differences)
+
+
+def edit_cluster(s: RepertoireSet, opt: Options, differences: int, tunables: Optional[dict] = None):
+    """Convenience: (label, size, n_clusters) of `s` at a Levenshtein distance of at most `differences`
+    (HipOverlap.edit_cluster) on a context of its own; `opt.differences` and `opt.indels` play no part.  `tunables`
+    are set on the context first (the result never depends on them)."""
+    with _context(opt, tunables) as h:
+        return h.edit_cluster(s, differences)
+
+
+def edit_cluster_table(s: RepertoireSet, opt: Options, differences: int, tunables: Optional[dict] = None):
+    """Convenience: (cluster_of, cluster_start, members, count) of `s` at a Levenshtein distance of at most
+    `differences` (HipOverlap.edit_cluster_table) on a context of its own; `opt.differences` and `opt.indels` play
+    no part.  `tunables` are set on the context first (the result never depends on them)."""
+    with _context(opt, tunables) as h:
+        return h.edit_cluster_table(s, differences)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

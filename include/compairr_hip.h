@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*, cmpr_edit_cluster*, cmpr_edit_cluster_table*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -785,7 +785,7 @@ int cmpr_hamming_nearest_device(cmpr_context *ctx, const cmpr_set_view *d_set1, 
  * through the bit-vector edit distance (Myers 1999; global form of Hyyro 2003): one LDS read and some fifteen 64-bit
  * operations per query residue and 64 reference residues.  A walk goes partner by partner, so the rows are sorted
  * afterwards (by the hit; distances carried along).  Device memory for the duration of the call: what
- * cmpr_hamming_neighbors() / _matrix() take, 32 bytes per set-1 group and 24 per pair of groups, and while the rows
+ * cmpr_hamming_neighbors() / _matrix() take, 40 bytes per set-1 group and 24 per pair of groups, and while the rows
  * are put in order 4 bytes per row of more than 64 hits and 6 bytes per hit of the longest row beyond 8192.
  */
 int cmpr_edit_neighbors(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
@@ -798,6 +798,74 @@ int cmpr_edit_matrix(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_se
                      int64_t differences, uint64_t *matrix_out);
 int cmpr_edit_matrix_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
                             int64_t differences, void *d_matrix);
+
+/*
+ * Single-linkage clusters under EDIT distance, at ANY d: the clusters of CDR3s that lie within d substitutions,
+ * insertions and deletions of each other -- at d = 2 or 3 the usual TCR clustering question.  cmpr_cluster*() with
+ * options.indels stops at d = 1, as the reference does; cmpr_hamming_cluster*() count substitutions only.  These calls
+ * are to cmpr_edit_neighbors() what cmpr_hamming_cluster*() are to cmpr_hamming_neighbors().
+ *
+ * Sequences i and j of `set` are linked when cmpr_edit_neighbors(set, set, differences) lists (i, j): the same V and J
+ * gene numbers unless options.ignore_genes, Levenshtein distance at most `differences`; the lengths may lie up to
+ * `differences` apart, empty sequences included.  A cluster is a connected component of that graph.
+ *
+ * cmpr_edit_cluster() gives label_out[n], size_out[n] and *n_clusters_out, which mean, word for word, what they mean in
+ * cmpr_cluster(): the smallest sequence number of i's cluster, the number of its members, the number of i with
+ * label_out[i] == i.  cmpr_edit_cluster_device() takes a DEVICE view and writes d_label_out / d_size_out, device memory
+ * of n uint32 each, where they lie.
+ *
+ * cmpr_edit_cluster_table() gives cluster_of_out[n], cluster_start_out (n + 1 provided, K + 1 written), member_out[n],
+ * count_out (n provided, K written) and *n_clusters_out = K, which mean, word for word, what they mean in
+ * cmpr_cluster_table(): the clusters numbered by (members descending, smallest member ascending), the members of each as
+ * CSR in increasing order, the summed duplicate_count per cluster (the number of members with ignore_counts).
+ * cmpr_edit_cluster_table_device() takes a DEVICE view and writes the four arrays -- device memory on the context's
+ * device -- where they lie.
+ *
+ * Relation to the other calls.  At differences = 0 the partition is that of cmpr_hamming_cluster(set, 0).  At
+ * differences = 1 it is the partition cmpr_cluster() gives on a context with differences = 1 and indels = 1, on every
+ * set, without exception: the pair of a one-residue sequence and an empty one, which the reference's deletion rule
+ * leaves out one way (variants.cc:301; see cmpr_edit_neighbors()), is found the other way, and a link has no direction.
+ * At every d each cluster of cmpr_hamming_cluster(set, d) lies inside one cluster here.
+ *
+ * All four: any output may be NULL; n_clusters_out is a HOST pointer in both variants; n == 0 is CMPR_OK with K = 0
+ * and nothing written but cluster_start[0] = 0.  As the rest of cmpr_edit_*() and cmpr_hamming_cluster*():
+ * `differences` is any value >= 0 (a value above the longest sequence behaves as that length); options.differences and
+ * options.indels play no part and are NOT refused; callable any time after cmpr_create(); the resident sets, plans and
+ * statistics are not disturbed and `set` is NOT resident afterwards; synchronous; every temporary is freed on every
+ * return; results are bit-identical from run to run and under every tunable (a root of the forest is the smallest
+ * number of its tree whatever the schedule; stable sorts, integer sums).  Refused before any device work, with the
+ * codes and texts of cmpr_hamming_cluster(): a negative `differences`, a NULL set, the tunable work_shard_count above
+ * 1, n_v_genes x n_j_genes above 2^46; options.existence is CMPR_EINVAL ("clusters are not defined with
+ * options.existence", as cmpr_cluster()).  No score plays a part: MH, Jaccard and the ratio score are NOT refused.  The
+ * set is validated as every other set (same codes and texts, passed through unchanged).  A set whose longest sequence
+ * has more than 256 residues is CMPR_EUNSUPPORTED ("cmpr_edit: a sequence of more than 256 residues"), as for
+ * cmpr_edit_neighbors().  At most 2^31-1 sequences.
+ *
+ * How (compairr_amd/csrc/edit.hip, the link sink of allpairs.h on the compare kernel of cmpr_edit_*()): the set is
+ * grouped and packed once.  A group (L, V, J) keeps as partners only the groups (L', V, J) with L <= L' <= L + d: a pair
+ * of two lengths is seen from the shorter side, and a longer partner is walked in full.  In its own group a lane walks
+ * only the references BEHIND its own query -- the workgroup of queries [256 b, 256 b + 256) walks the positions from
+ * 256 b + 1 on, its segments divide that range, a wave skips the staged pieces at or below its first query -- so every
+ * unordered pair is compared once and the (i, i) pair never.  A match unites the two sequences in a union-find forest
+ * over the original sequence numbers (link_forest.h) unless the snapshots of their roots, staged beside the references,
+ * already agree.  No pair list and no (query, segment) count array exist.  The flatten, size and table passes are those
+ * of cmpr_cluster*() (cluster.hip).  Device memory for the duration of the call: the set copy, group order and packed
+ * words of cmpr_edit_*() above, 40 bytes per group (job) and 24 per pair of groups, 8 bytes per sequence of forest and
+ * labels (the forest's words take the sizes afterwards; either goes to the caller's device array where one is given),
+ * and for the table calls the terms of cmpr_cluster_table(): 4 bytes per sequence each for cluster_of and the members
+ * unless they go to the caller's device arrays, 8 and a few histograms for the radix sort's scratch, 16 per cluster, and
+ * in the host variant 8 each per cluster for cluster_start and the counts.
+ */
+int cmpr_edit_cluster(cmpr_context *ctx, const cmpr_set_view *set, int64_t differences,
+                      uint32_t *label_out, uint32_t *size_out, uint64_t *n_clusters_out);
+int cmpr_edit_cluster_device(cmpr_context *ctx, const cmpr_set_view *d_set, int64_t differences,
+                             uint32_t *d_label_out, uint32_t *d_size_out, uint64_t *n_clusters_out);
+int cmpr_edit_cluster_table(cmpr_context *ctx, const cmpr_set_view *set, int64_t differences,
+                            uint32_t *cluster_of_out, uint64_t *cluster_start_out,
+                            uint32_t *member_out, uint64_t *count_out, uint64_t *n_clusters_out);
+int cmpr_edit_cluster_table_device(cmpr_context *ctx, const cmpr_set_view *d_set, int64_t differences,
+                                   uint32_t *d_cluster_of_out, uint64_t *d_cluster_start_out,
+                                   uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out);
 
 /*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
@@ -929,6 +997,8 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
                              global memory), 0 (default) only groups of more than 16 words per sequence
      "hamming_link_snapshot" TEST ONLY, cmpr_hamming_cluster*(): 1 (default) skips a match whose two staged root
                              snapshots agree, 0 sends every match to the forest; the partition is the same
+     "edit_link_snapshot"    TEST ONLY, cmpr_edit_cluster*(): 1 (default) skips a match whose two staged root
+                             snapshots agree, 0 sends every match to the forest; the partition is the same
      "edit_stage_refs"       TEST ONLY, cmpr_edit_*(): references staged per LDS piece (0 = default: as many match
                              vectors as fit 16 KiB, at most 512; a larger value is clamped to that)
      "edit_segments"         TEST ONLY: forces the number of segments every partner group is walked in (1..64; 0 =
@@ -970,8 +1040,11 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    "cluster_links_us" and set "cluster_table_us" (the table pass, its copies included: "hamming_copy_us" stays 0);
    and of the last cmpr_edit_*(), host times, each part ending in a wait: "edit_group_us" (upload, validation, keys,
    sort, groups, packing, the jobs), "edit_compare_us" (the compare kernel: once for a matrix, the count step, the sum
-   and the fill step for neighbours), "edit_order_us" (the rows sorted; 0 for a matrix or when nothing was filled)
-   and "edit_copy_us" (host variant: the results copied out). */
+   and the fill step for neighbours; for cmpr_edit_cluster*() the link kernel, the flatten and the sizes),
+   "edit_order_us" (the rows sorted; 0 for a matrix, for clusters or when nothing was filled) and "edit_copy_us" (host
+   variant: the results copied out).  cmpr_edit_cluster_table*() set these four as well, zero "cluster_links_us" and
+   set "cluster_table_us" (the table pass, its copies included: "edit_copy_us" stays 0); no cmpr_edit_*() call touches
+   the "hamming_*_us" timers. */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

@@ -27,6 +27,9 @@
  *            Beside every staged reference lies a snapshot of its root; a lane keeps its own root in a register,
  *            skips a match whose snapshot equals it and looks its root up again after a link it made.  No count
  *            array, no pair list.  What follows the launch is pairs_clusters (cluster.hip's passes).
+ *            nearest: the sink itself is the caller's (HmSink / EdSink<SINK_NEAREST>: the walks differ in what "the
+ *            first reference at the minimum" means); what surrounds the launch is pairs_nearest: the outputs or the
+ *            (query, segment) slots set to "none", the fold of the slots, the count of the queries that found somebody.
  *
  * The (query, segment) count array has n1 x S words, S <= PAIRS_MAX_SEGMENTS; the automatic S is above 1 only while
  * the query tiles alone do not fill the machine (S <= ceil(8 x CUs / workgroups)), which bounds it by
@@ -147,6 +150,25 @@ int pairs_neighbors(cmpr_context *c, const std::string &who, const PairSets &W, 
                     uint64_t *n_edges_out, bool on_device, const std::function<int()> &launch, bool rows_always,
                     double *ms, int order_slot, int copy_slot);
 
+/* where a lane of a nearest sink (the callers' own, HmSink / EdSink<SINK_NEAREST>) leaves its results: filled by
+   pairs_nearest and handed to its `launch` */
+struct PairNearest {
+  uint32_t       *nearest;         /* one segment: the three results, each may be NULL */
+  uint16_t       *dist;
+  uint32_t       *ties;
+  unsigned long long *key;         /* several: [n1 x segments] (distance << 32 | number), all ones: none */
+  uint32_t       *slot_ties;       /* ... and the references of the segment at that distance */
+};
+
+/* The nearest neighbour of every sequence of set 1: the three outputs (one segment) or the (query, segment) slots
+   (several) set to "none" on the stream, `launch` -- the compare kernel with the caller's nearest sink over the runs,
+   which writes where the PairNearest says --, with several segments the fold of a query's slots (the smallest key, the
+   ties of the slots at its distance summed), and the number of queries that found somebody counted over the finished
+   ties.  ms[1]: all of that; ms[copy_slot]: the copy-out of the host variant. */
+int pairs_nearest(cmpr_context *c, const PairSets &W, uint32_t segments, uint32_t *nearest_out, uint16_t *dist_out,
+                  uint32_t *ties_out, uint64_t *n_found_out, bool on_device,
+                  const std::function<int(const PairNearest &)> &launch, double *ms, int copy_slot);
+
 /* The clusters of set S against itself: the forest over the original sequence numbers (cluster.hip), `launch` -- the
    compare kernel with the link sink over the runs, every unordered matching pair united --, flat labels and sizes, and
    the results of the plain call (T == NULL: L's label / size) or the table pass (T's four arrays, from labels and sizes
@@ -206,7 +228,10 @@ struct PairQuery {
   __device__ __forceinline__ bool active() const { return qi < nq; }
 };
 
-enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2 };   /* (hamming.hip has one more of its own, SINK_NEAREST = 3) */
+/* (SINK_NEAREST: PairSink has no such form; hamming.hip and edit.hip each have a sink of their own behind its interface) */
+enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2, SINK_NEAREST = 3 };
+
+constexpr uint32_t HM_NONE = 0xffffffffu;      /* nearest sinks: the infinite distance, and "no sequence" */
 
 /* a pointer into LDS, typed as such: what is reached through it stays an LDS instruction, also where the code chooses
    between it and a pointer to global memory (the cells of the matrix sink) */

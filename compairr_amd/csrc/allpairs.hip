@@ -1,6 +1,7 @@
 /*
  * allpairs.hip -- the host side of allpairs.h: the refusals, a staged set grouped and packed, the segment count, and
- * the drivers around a caller's compare kernel -- the matrix, the neighbours as CSR, and the clusters.
+ * the drivers around a caller's compare kernel -- the matrix, the neighbours as CSR, the clusters, and the nearest
+ * neighbours.
  */
 #include "allpairs.h"
 #include "csr_rows.h"
@@ -94,6 +95,35 @@ pairs_rows_kernel(const unsigned long long *offs, uint64_t n1, uint32_t segments
   if (i <= n1)
     row_start[i] = offs[i * segments];
 }
+
+/* the slots of a query folded: the smallest key, and the ties of the slots at its distance summed */
+__global__ void __launch_bounds__(PAIRS_WG)
+pairs_nearest_fold_kernel(const unsigned long long *key, const uint32_t *slot_ties, uint64_t n1, uint32_t segments,
+                       uint32_t *nearest, uint16_t *dist, uint32_t *ties)
+{
+  const uint64_t i = (uint64_t)blockIdx.x * PAIRS_WG + threadIdx.x;
+  if (i >= n1)
+    return;
+  unsigned long long best = ~0ull;
+  for (uint32_t s = 0; s < segments; s++)
+    best = min(best, key[i * segments + s]);
+  const uint32_t d = (uint32_t)(best >> 32);
+  uint32_t t = 0;
+  for (uint32_t s = 0; s < segments; s++)
+    t += (uint32_t)(key[i * segments + s] >> 32) == d ? slot_ties[i * segments + s] : 0u;
+  const bool none = d == HM_NONE;
+  if (nearest)
+    nearest[i] = none ? HM_NONE : (uint32_t)best;
+  if (dist)
+    dist[i] = none ? (uint16_t)0xffffu : (uint16_t)d;
+  if (ties)
+    ties[i] = none ? 0u : t;
+}
+
+/* 1 for a query that has a candidate (hipcub::TransformInputIterator over the finished ties) */
+struct HasTies {
+  __host__ __device__ unsigned long long operator()(uint32_t t) const { return t ? 1ull : 0ull; }
+};
 
 }  // namespace
 
@@ -382,5 +412,71 @@ int cmpr::pairs_clusters(cmpr_context *c, const HmSet &S, bool snapshot, bool on
   if ((rc = cmpr_cluster_results(c, L, n_clusters_out)))
     return rc;
   ms[1] = ms_since(t0);
+  return CMPR_OK;
+}
+
+int cmpr::pairs_nearest(cmpr_context *c, const PairSets &W, uint32_t segments, uint32_t *nearest_out, uint16_t *dist_out,
+                        uint32_t *ties_out, uint64_t *n_found_out, bool on_device,
+                        const std::function<int(const PairNearest &)> &launch, double *ms, int copy_slot)
+{
+  int rc;
+  auto t0 = std::chrono::steady_clock::now();
+  const uint64_t n1 = W.s1->n, S = segments;
+  if (n1 == 0)
+    return CMPR_OK;
+  Out<uint32_t> nearest(nearest_out, on_device);
+  Out<uint16_t> dist(dist_out, on_device);
+  Out<uint32_t> ties(ties_out, on_device);
+  if (nearest.wanted() && (rc = nearest.temp(c, (size_t)n1))) return rc;
+  if (dist.wanted() && (rc = dist.temp(c, (size_t)n1))) return rc;
+  if ((ties.wanted() || n_found_out) && (rc = ties.temp(c, (size_t)n1))) return rc;
+  PairNearest N{};
+  Tmp<unsigned long long> key, found;
+  Tmp<uint32_t> slot_ties;
+  Tmp<char> sum_tmp;
+  if (S == 1) {
+    /* "none" everywhere first: a query whose group set 2 lacks is no lane's */
+    if (nearest.p) HIP_TRY(c, hipMemsetAsync(nearest.p, 0xff, n1 * sizeof(uint32_t), c->stream));
+    if (dist.p) HIP_TRY(c, hipMemsetAsync(dist.p, 0xff, n1 * sizeof(uint16_t), c->stream));
+    if (ties.p) HIP_TRY(c, hipMemsetAsync(ties.p, 0, n1 * sizeof(uint32_t), c->stream));
+    N.nearest = nearest.p; N.dist = dist.p; N.ties = ties.p;
+  } else {
+    /* ... nor is a (query, segment) whose range is empty: the fold writes every query from its slots */
+    if ((rc = dev_alloc(c, key.b, (size_t)(n1 * S)))) return rc;
+    if ((rc = dev_alloc(c, slot_ties.b, (size_t)(n1 * S)))) return rc;
+    HIP_TRY(c, hipMemsetAsync(key.b.p, 0xff, n1 * S * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(slot_ties.b.p, 0, n1 * S * sizeof(uint32_t), c->stream));
+    N.key = key.b.p; N.slot_ties = slot_ties.b.p;
+  }
+  if ((rc = launch(N)))
+    return rc;
+  if (S > 1) {
+    hipLaunchKernelGGL(pairs_nearest_fold_kernel, dim3(blocks_for(n1, PAIRS_WG)), dim3(PAIRS_WG), 0, c->stream,
+                       (const unsigned long long *)key.b.p, (const uint32_t *)slot_ties.b.p, n1, (uint32_t)S,
+                       nearest.p, dist.p, ties.p);
+    HIP_TRY(c, hipGetLastError());
+  }
+  unsigned long long n_found = 0;
+  if (n_found_out) {
+    hipcub::TransformInputIterator<unsigned long long, HasTies, const uint32_t *> has(ties.p, HasTies());
+    size_t sum_bytes = 0;
+    if ((rc = dev_alloc(c, found.b, 1))) return rc;
+    HIP_TRY(c, hipcub::DeviceReduce::Sum(nullptr, sum_bytes, has, found.b.p, (int)n1, c->stream));
+    if ((rc = dev_alloc(c, sum_tmp.b, sum_bytes))) return rc;
+    HIP_TRY(c, hipcub::DeviceReduce::Sum(sum_tmp.b.p, sum_bytes, has, found.b.p, (int)n1, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&n_found, found.b.p, sizeof n_found, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (n_found_out)
+    *n_found_out = n_found;
+  ms[1] = ms_since(t0);
+  if (!on_device) {
+    t0 = std::chrono::steady_clock::now();
+    if (nearest.wanted() && (rc = nearest.copy_out(c, (size_t)n1))) return rc;
+    if (dist.wanted() && (rc = dist.copy_out(c, (size_t)n1))) return rc;
+    if (ties.wanted() && (rc = ties.copy_out(c, (size_t)n1))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    ms[copy_slot] = ms_since(t0);
+  }
   return CMPR_OK;
 }

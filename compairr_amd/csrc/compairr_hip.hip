@@ -374,6 +374,7 @@ const Tunable TUNABLES[] = {
   {"edit_stage_refs", F(edit_stage_refs), 0, 65536, LOCK_NEVER, T_NO_PLAN, " must be 0..65536"},
   {"edit_segments", F(edit_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
   {"edit_words", F(edit_words), 0, 4, LOCK_NEVER, T_NO_PLAN, " must be 0 (from the length), 2 or 4", edit_words_ok},
+  {"edit_nearest_prune", F(edit_nearest_prune), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
   {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
   {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
   {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},

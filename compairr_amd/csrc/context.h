@@ -214,6 +214,7 @@ struct cmpr_context {
      (0 = automatic), at least this many 64-bit words per column (0 = from the reference's length) */
   int64_t edit_stage_refs = 0, edit_segments = 0, edit_words = 0;
   int64_t edit_link_snapshot = 1;     /* TEST ONLY, of cmpr_edit_cluster*: 0 = every match goes to link_pair */
+  int64_t edit_nearest_prune = 1;     /* TEST ONLY, of cmpr_edit_nearest*: 0 = every partner within the cap is walked */
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */

@@ -1,7 +1,8 @@
 /*
  * edit.hip -- the all-against-all path under EDIT distance, for any d: cmpr_edit_neighbors / _device,
- * cmpr_edit_matrix / _device, and the single-linkage clusters of that relation, cmpr_edit_cluster / _device and
- * cmpr_edit_cluster_table / _device.  A pair (i of set 1, j of set 2) matches when the two sequences have the same V and J
+ * cmpr_edit_matrix / _device, the single-linkage clusters of that relation, cmpr_edit_cluster / _device and
+ * cmpr_edit_cluster_table / _device, and the nearest neighbour of every sequence under that distance, whatever it is:
+ * cmpr_edit_nearest / _device.  A pair (i of set 1, j of set 2) matches when the two sequences have the same V and J
  * gene numbers unless ignore_genes and their Levenshtein distance -- substitution, insertion and deletion cost 1 each --
  * is at most `differences`.  The reference has indels at d = 1 only (its variant enumeration explodes beyond); nothing
  * is enumerated or hashed here: every query is compared with every sequence of every group it can match.
@@ -28,7 +29,8 @@
  *            residues: every CDR3 and junction of amino acids.  A longer query is read word by word from global
  *            memory (NW = 0: one load per four or sixteen column steps); unrolled, 256 steps of four column words
  *            would be straight-line code far beyond the instruction cache.  No instantiation indexes an array at
- *            run time: private_segment_fixed_size is 0 in every one of them (checked in the code object's metadata).
+ *            run time: private_segment_fixed_size is 0 in every one of them, the nearest sink's included (checked in
+ *            the code object's metadata).
  *   sinks    allpairs.h's matrix and count / fill.  The walk goes partner by partner, which is not number order, so
  *            the rows are sorted afterwards by csr_rows.h with the 64-bit key (hit << 16 | distance) -- the hit alone
  *            without distance_out --, rows beyond LDS_MAX by hipcub's device-wide sort.  The hits of a row are
@@ -40,6 +42,18 @@
  *            range, a wave skips the staged pieces at or below its first query, a lane links only positions above its
  *            own.  Every unordered pair once, (i, i) never; the empty group is linked among itself (the distance of
  *            two empty sequences is 0) and to the groups of up to d residues.  Behind the launch: pairs_clusters.
+ *            nearest (cmpr_edit_nearest): no threshold -- the kernel hands EVERY reference's distance to the sink, and a
+ *            lane keeps the smallest distance so far, the smallest ORIGINAL number at it (the staged st_id[r], one LDS
+ *            address for the wave: position order is number order inside a partner only) and the number of references
+ *            at it: compares and selects, nothing indexed by the distance.  A reference that is no candidate (below the
+ *            floor, above the cap, the query itself in one-set mode, the query's own repertoire with the flag) takes
+ *            part at an infinite distance.  The job's partners are those within the cap BY INCREASING LENGTH GAP: the
+ *            Levenshtein distance is never below the gap, so in front of every partner the workgroup votes
+ *            (__syncthreads_or) whether any lane's best still reaches that partner's gap, and leaves the loop when none
+ *            does -- every later reference is further than what each lane holds, so it can neither improve on it nor tie
+ *            with it.  A (workgroup, segment) stops on its own partial best, an upper bound of the final one.  One
+ *            segment: the lane writes its three results; several: a slot per (query, segment), folded by pairs_nearest
+ *            (allpairs.h), which also sets outputs or slots to "none" first and counts the queries that found somebody.
  *
  * Nothing here writes the resident sets, plans or statistics of the context.
  */
@@ -88,8 +102,14 @@ struct EdParams {
   const uint32_t *ord1, *ord2;     /* sequence numbers in group order */
   uint32_t        d, stage_refs, min_words;
   uint32_t        blk_base;        /* workgroup number of this launch's first workgroup */
-  PairSinks       sink;            /* count / fill, matrix (allpairs.h) */
+  PairSinks       sink;            /* count / fill, matrix (allpairs.h); rep1, rep2 also of the nearest sink */
   PairLinks       link;            /* link (allpairs.h) */
+  /* nearest: d is the cap (sink.rep1, sink.rep2 read with other_rep only) */
+  uint32_t        floor;           /* a candidate lies at this distance or further */
+  uint32_t        one_set;         /* 1: set 2 IS set 1, a query is no candidate of its own */
+  uint32_t        other_rep;       /* 1: a candidate comes from another repertoire than the query */
+  uint32_t        prune;           /* 1: a workgroup leaves the partners once no lane's best reaches the length gap */
+  PairNearest     nn;              /* where the results or the (query, segment) slots go (allpairs.h) */
 };
 
 /* the sinks of ed_compare_kernel: allpairs.h's, each built from its fields of the parameters */
@@ -102,6 +122,73 @@ template <>
 struct EdSink<SINK_LINK> : PairSink<SINK_LINK> {
   __device__ __forceinline__ EdSink(const EdParams &P, const PairLds &L, uint32_t *st_root)
       : PairSink<SINK_LINK>(P.link, L, st_root) {}
+};
+
+/* nearest: no threshold, so near() for EVERY reference in place of match() for the matching ones.  The smallest
+   distance so far, the smallest ORIGINAL number at it -- a walk goes partner by partner, so position order is not
+   number order across partners, and the staged number st_id[r], one LDS address for the whole wave, is compared
+   instead --, how many at it.  What is no candidate (below the floor, above the cap, the query itself in one-set
+   mode, the query's own repertoire with the flag) is infinitely far.  Compares and selects only. */
+template <>
+struct EdSink<SINK_NEAREST> {
+  const EdParams P;                /* (a copy, as PairSink's K) */
+  const Lds<uint32_t> st_id, st_rep;
+  /* the number that is the lane's own query (one-set mode) and the repertoire a candidate must not come from;
+     HM_NONE is no number and no repertoire */
+  uint32_t nn_self = HM_NONE, nn_rep = HM_NONE;
+  uint32_t best = HM_NONE, bid = HM_NONE, ties = 0;
+  __device__ __forceinline__ EdSink(const EdParams &P_, const PairLds &L, uint32_t *)
+      : P(P_), st_id(L.id), st_rep(L.rep) {}
+  __device__ __forceinline__ void zero_matrix() const {}
+  __device__ __forceinline__ void init(uint32_t qorig, uint32_t)
+  {
+    nn_self = P.one_set ? qorig : HM_NONE;
+    nn_rep = P.other_rep ? P.sink.rep1[qorig] : HM_NONE;
+  }
+  __device__ __forceinline__ void stage(uint32_t r, uint32_t id) const
+  {
+    st_id[r] = id;
+    if (P.other_rep)
+      st_rep[r] = P.sink.rep2[id];
+  }
+  /* the reference staged as r lies at distance `dd`: (smaller: its number) and (equal: the smaller number, one more
+     at it), as selects.  While nobody has been found "equal" also holds between two infinities: what it leaves in bid
+     and ties is overwritten by the first candidate and dropped at the end */
+  __device__ __forceinline__ void near(uint32_t r, uint32_t dd)
+  {
+    const uint32_t id = st_id[r];
+    uint32_t rp = 0;                                                    /* (without the flag: not HM_NONE) */
+    if (P.other_rep)                                                    /* (the same for every lane) */
+      rp = st_rep[r];
+    const bool ok = (dd >= P.floor) & (dd <= P.d) & (id != nn_self) & (rp != nn_rep);
+    const uint32_t de = ok ? dd : HM_NONE;
+    const bool lt = de < best;
+    ties = lt ? 1u : ties + (de == best ? 1u : 0u);
+    bid = lt ? id : de == best ? min(id, bid) : bid;
+    best = lt ? de : best;
+  }
+  /* (a partner whose sequences are `gap` residues longer or shorter than the query holds nothing below `gap`) */
+  __device__ __forceinline__ bool wants(bool active, uint32_t gap) const { return active && best >= gap; }
+  __device__ __forceinline__ void end(bool active, uint32_t qorig, uint32_t seg) const
+  {
+    if (!active)
+      return;
+    const bool none = best == HM_NONE;
+    const uint32_t id = none ? HM_NONE : bid;
+    const uint32_t t = none ? 0u : ties;
+    if (P.segments == 1) {
+      if (P.nn.nearest)
+        P.nn.nearest[qorig] = id;
+      if (P.nn.dist)
+        P.nn.dist[qorig] = none ? (uint16_t)0xffffu : (uint16_t)best;
+      if (P.nn.ties)
+        P.nn.ties[qorig] = t;
+    } else {
+      const uint64_t slot = (uint64_t)qorig * P.segments + seg;
+      P.nn.key[slot] = (unsigned long long)best << 32 | id;
+      P.nn.slot_ties[slot] = t;
+    }
+  }
 };
 
 /* One column of the edit-distance matrix further: the text residue whose Peq words lie at `peq`.  pv / mv: the
@@ -147,7 +234,7 @@ ed_compare_kernel(const EdParams P)
   constexpr uint32_t A = NT ? 4 : 20, PER = NT ? 16 : 4, BITS = NT ? 2 : 8, MASK = NT ? 3 : 0xff;
   __shared__ unsigned long long st_peq[ED_PEQ_WORDS];
   __shared__ uint32_t st_id[PAIRS_STAGE_MAX];
-  __shared__ uint32_t st_rep[SINK == SINK_MATRIX ? PAIRS_STAGE_MAX : 1];
+  __shared__ uint32_t st_rep[SINK == SINK_MATRIX || SINK == SINK_NEAREST ? PAIRS_STAGE_MAX : 1];
   __shared__ unsigned long long st_cnt[SINK == SINK_MATRIX ? PAIRS_STAGE_MAX : 1];
   __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? PAIRS_MAT_CELLS : 1];
   __shared__ uint32_t st_root[SINK == SINK_LINK ? PAIRS_STAGE_MAX : 1];
@@ -242,7 +329,9 @@ ed_compare_kernel(const EdParams P)
             }
           }
         }
-        if (dd <= P.d && active && (!own || e + r > qi))
+        if constexpr (SINK == SINK_NEAREST)
+          S.near(r, dd);
+        else if (dd <= P.d && active && (!own || e + r > qi))
           S.match(r, dd);
       }
     }
@@ -250,6 +339,14 @@ ed_compare_kernel(const EdParams P)
 
   for (uint32_t p = jb.p0; p < jb.p0 + jb.np; p++) {
     const EdPartner pt = P.partners[p];
+    if constexpr (SINK == SINK_NEAREST) {
+      /* the partners come by increasing length gap, and no distance is below the gap: once no lane's best reaches
+         it, nothing here or later can improve on or tie with what a lane holds.  The whole workgroup votes, in front
+         of the staging barrier; an idle lane votes no.  (P.prune is the launch's: 0 walks every partner) */
+      const uint32_t gap = pt.len > qlen ? pt.len - qlen : qlen - pt.len;
+      if (P.prune && !__syncthreads_or(S.wants(active, gap)))
+        break;
+    }
     /* (the own group: the workgroup whose first query sits at position b walks the references behind b only, and its
        segments divide THAT range) */
     const uint32_t w0 = SINK == SINK_LINK && pt.own ? min(wg_q0 + 1u, pt.nr) : 0u;
@@ -310,11 +407,16 @@ struct EdWork : PairSets {
   PairRuns       runs;             /* form: ed_form_of */
 };
 
-/* triangular (the cluster calls, set2 == set1): a job keeps the partners of its own length and longer -- an unordered
-   pair of two lengths is seen from the shorter side -- and its own group is marked as such */
+/* the order of a job's partners.  ED_BY_LENGTH: by increasing length.  ED_TRIANGULAR (the cluster calls, set2 == set1):
+   a job keeps the partners of its own length and longer -- an unordered pair of two lengths is seen from the shorter
+   side -- and its own group is marked as such.  ED_BY_GAP (the nearest calls): by increasing |L - L'|, of two at one gap
+   the shorter first, so that a walk can stop at the first gap above what it holds */
+enum EdOrder { ED_BY_LENGTH, ED_TRIANGULAR, ED_BY_GAP };
+
 int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1, const cmpr_set_view *set2,
-             int64_t differences, bool on_device, EdWork &J, bool triangular = false)
+             int64_t differences, bool on_device, EdWork &J, EdOrder order = ED_BY_LENGTH)
 {
+  const bool triangular = order == ED_TRIANGULAR;
   int rc;
   if ((rc = pairs_stage(c, set1, set2, on_device, J, [&](const HmSet &H) {
          return H.longest > ED_MAX_LEN ? fail(c, CMPR_EUNSUPPORTED, "cmpr_edit: a sequence of more than 256 residues")
@@ -354,6 +456,10 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
     }
     if (partners.size() == p0)
       continue;
+    if (order == ED_BY_GAP)
+      std::stable_sort(partners.begin() + (ptrdiff_t)p0, partners.end(), [&](const EdPartner &x, const EdPartner &y) {
+        return (x.len > ga.len ? x.len - ga.len : ga.len - x.len) < (y.len > ga.len ? y.len - ga.len : ga.len - y.len);
+      });
     const uint32_t nb = blocks_for(ga.count, PAIRS_WG);
     J.runs.add(ed_form_of(ga.len, ga.stride), (uint32_t)blocks, nb);
     jobs.push_back(EdJob{ga.pk_off, ga.start, ga.count, ga.len, ga.stride, (uint32_t)p0,
@@ -460,7 +566,7 @@ int edit_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differe
   if (T)
     c->cl_ms[0] = c->cl_ms[1] = 0;
   EdWork J;
-  if ((rc = ed_setup(c, who, set, set, differences, on_device, J, true)))
+  if ((rc = ed_setup(c, who, set, set, differences, on_device, J, ED_TRIANGULAR)))
     return rc;
   c->ed_ms[0] = ms_since(t0);
   return pairs_clusters(c, *J.s1, c->edit_link_snapshot != 0, on_device, L, T, n_clusters_out,
@@ -471,7 +577,71 @@ int edit_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differe
                         c->ed_ms, 3);
 }
 
+/* cmpr_edit_nearest*: one walk through the nearest sink, the partners of a job by increasing length gap and no further
+   than the cap; what surrounds the launch is pairs_nearest (allpairs.h) */
+int edit_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t min_distance,
+                      int64_t max_distance, uint32_t flags, uint32_t *nearest_out, uint16_t *dist_out,
+                      uint32_t *ties_out, uint64_t *n_found_out, bool on_device)
+{
+  if (!c)
+    return CMPR_EINVAL;
+  const std::string who = "cmpr_edit_nearest";
+  if (n_found_out)
+    *n_found_out = 0;
+  int rc;
+  if ((rc = hm_refusals(c, who, set1, set2, min_distance, HM_NEAREST, on_device, true)))
+    return rc;
+  if (max_distance < 0)
+    return fail(c, CMPR_EINVAL, who + ": max_distance cannot be negative");
+  if (flags & ~(uint32_t)CMPR_NEAREST_OTHER_REPERTOIRE)
+    return fail(c, CMPR_EINVAL, who + ": unknown bits in flags");
+  const bool other_rep = (flags & CMPR_NEAREST_OTHER_REPERTOIRE) != 0;
+  if (other_rep && set2 != set1)
+    return fail(c, CMPR_EINVAL, who + ": CMPR_NEAREST_OTHER_REPERTOIRE needs set2 == set1 (two sets have two numberings "
+                                      "of their repertoires)");
+  auto t0 = std::chrono::steady_clock::now();
+  for (double &t : c->ed_ms)
+    t = 0;
+  EdWork J;
+  if ((rc = ed_setup(c, who, set1, set2, max_distance, on_device, J, ED_BY_GAP)))
+    return rc;
+  c->ed_ms[0] = ms_since(t0);
+  EdParams &P = J.P;
+  P.sink.rep1 = J.s1->rep.b.p; P.sink.rep2 = J.s2->rep.b.p;
+  P.floor = (uint32_t)std::min<int64_t>(min_distance, 0x10000);        /* (no distance is above 256) */
+  P.one_set = J.s2 == J.s1 ? 1u : 0u;
+  P.other_rep = other_rep ? 1u : 0u;
+  P.prune = c->edit_nearest_prune ? 1u : 0u;
+  return pairs_nearest(c, J, P.segments, nearest_out, dist_out, ties_out, n_found_out, on_device,
+                       [&](const PairNearest &N) {
+                         P.nn = N;
+                         return ed_launch<SINK_NEAREST>(c, J);
+                       },
+                       c->ed_ms, 3);
+}
+
 }  // namespace
+
+extern "C" int cmpr_edit_nearest(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                                 int64_t min_distance, int64_t max_distance, uint32_t flags, uint32_t *nearest_out,
+                                 uint16_t *distance_out, uint32_t *ties_out, uint64_t *n_found_out)
+{
+  return guarded(c, [&] {
+    return edit_nearest_impl(c, set1, set2, min_distance, max_distance, flags, nearest_out, distance_out, ties_out,
+                             n_found_out, false);
+  });
+}
+
+extern "C" int cmpr_edit_nearest_device(cmpr_context *c, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                        int64_t min_distance, int64_t max_distance, uint32_t flags,
+                                        uint32_t *d_nearest_out, uint16_t *d_distance_out, uint32_t *d_ties_out,
+                                        uint64_t *n_found_out)
+{
+  return guarded(c, [&] {
+    return edit_nearest_impl(c, d_set1, d_set2, min_distance, max_distance, flags, d_nearest_out, d_distance_out,
+                             d_ties_out, n_found_out, true);
+  });
+}
 
 extern "C" int cmpr_edit_cluster(cmpr_context *c, const cmpr_set_view *set, int64_t differences, uint32_t *label_out,
                                  uint32_t *size_out, uint64_t *n_clusters_out)

@@ -32,12 +32,11 @@
  *            distance.  Position order is number order, so the first reference at the minimum is the one of the
  *            smallest number, looked up in the group order once, at the end.  One segment: the lane writes its three
  *            results.  Several: every (query, segment) writes a slot -- the 64-bit key (distance << 32 | number) and
- *            the ties -- and hm_nearest_fold_kernel takes the smallest key of a query and sums the ties of the slots
- *            at its distance.  Outputs and slots are set to "none" on the stream first: what no lane visits stays so.
+ *            the ties -- and pairs_nearest (allpairs.h) folds them: the smallest key of a query, the ties of the slots
+ *            at its distance summed.  Outputs and slots are set to "none" on the stream first: what no lane visits
+ *            stays so.
  */
 #include "allpairs.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <string>
@@ -76,10 +75,6 @@ struct HmParams {
   unsigned long long *nn_key;      /* several: [n1 x segments] (distance << 32 | number), all ones: none */
   uint32_t       *nn_slot_ties;    /* ... and the references of the segment at that distance */
 };
-
-enum { SINK_NEAREST = 3 };                     /* (behind allpairs.h's SINK_CSR, SINK_MATRIX, SINK_LINK) */
-
-constexpr uint32_t HM_NONE = 0xffffffffu;      /* nearest sink: the infinite distance, and "no sequence" */
 
 /* differing residues of two packed words.  Amino acids: a byte each, codes below 0x80, so neither the xor nor the
    sum carries into the next byte and bit 7 says "this byte is not zero".  Nucleotides: two bits each. */
@@ -271,35 +266,6 @@ hm_compare_kernel(const HmParams P)
   S.end(active, qorig, seg);
 }
 
-/* the slots of a query folded: the smallest key, and the ties of the slots at its distance summed */
-__global__ void __launch_bounds__(PAIRS_WG)
-hm_nearest_fold_kernel(const unsigned long long *key, const uint32_t *slot_ties, uint64_t n1, uint32_t segments,
-                       uint32_t *nearest, uint16_t *dist, uint32_t *ties)
-{
-  const uint64_t i = (uint64_t)blockIdx.x * PAIRS_WG + threadIdx.x;
-  if (i >= n1)
-    return;
-  unsigned long long best = ~0ull;
-  for (uint32_t s = 0; s < segments; s++)
-    best = min(best, key[i * segments + s]);
-  const uint32_t d = (uint32_t)(best >> 32);
-  uint32_t t = 0;
-  for (uint32_t s = 0; s < segments; s++)
-    t += (uint32_t)(key[i * segments + s] >> 32) == d ? slot_ties[i * segments + s] : 0u;
-  const bool none = d == HM_NONE;
-  if (nearest)
-    nearest[i] = none ? HM_NONE : (uint32_t)best;
-  if (dist)
-    dist[i] = none ? (uint16_t)0xffffu : (uint16_t)d;
-  if (ties)
-    ties[i] = none ? 0u : t;
-}
-
-/* 1 for a query that has a candidate (hipcub::TransformInputIterator over the finished ties) */
-struct HasTies {
-  __host__ __device__ unsigned long long operator()(uint32_t t) const { return t ? 1ull : 0ull; }
-};
-
 typedef void (*HmKernel)(const HmParams);
 
 template <int SINK, bool NT>
@@ -434,8 +400,8 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
                          on_device, [&] { return hm_launch<SINK_CSR>(c, J); }, false, c->hm_ms, -1, 2);
 }
 
-/* cmpr_hamming_nearest*: one walk through the nearest sink, with several segments the fold of the slots behind it, and
-   the number of queries that found somebody counted over the finished ties */
+/* cmpr_hamming_nearest*: one walk through the nearest sink; what surrounds the launch -- "none" everywhere first, with
+   several segments the fold of the slots, the number of queries that found somebody -- is pairs_nearest (allpairs.h) */
 int hamming_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, int64_t min_distance,
                          uint32_t flags, uint32_t *nearest_out, uint16_t *dist_out, uint32_t *ties_out,
                          uint64_t *n_found_out, bool on_device)
@@ -460,70 +426,18 @@ int hamming_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_
   if ((rc = hm_setup(c, who, set1, set2, 0, on_device, J)))
     return rc;
   c->hm_ms[0] = ms_since(t0);
-  t0 = std::chrono::steady_clock::now();
-
-  const uint64_t n1 = J.s1->n, S = J.P.segments;
-  if (n1 == 0)
-    return CMPR_OK;
-  Out<uint32_t> nearest(nearest_out, on_device);
-  Out<uint16_t> dist(dist_out, on_device);
-  Out<uint32_t> ties(ties_out, on_device);
-  if (nearest.wanted() && (rc = nearest.temp(c, (size_t)n1))) return rc;
-  if (dist.wanted() && (rc = dist.temp(c, (size_t)n1))) return rc;
-  if ((ties.wanted() || n_found_out) && (rc = ties.temp(c, (size_t)n1))) return rc;
   HmParams &P = J.P;
   P.sink.rep1 = J.s1->rep.b.p; P.sink.rep2 = J.s2->rep.b.p;
   P.floor = (uint32_t)std::min<int64_t>(min_distance, 0x10000);        /* (no distance is above 65535) */
   P.one_set = J.s2 == J.s1 ? 1u : 0u;
   P.other_rep = other_rep ? 1u : 0u;
-  Tmp<unsigned long long> key, found;
-  Tmp<uint32_t> slot_ties;
-  Tmp<char> sum_tmp;
-  if (S == 1) {
-    /* "none" everywhere first: a query whose group set 2 lacks is no lane's */
-    if (nearest.p) HIP_TRY(c, hipMemsetAsync(nearest.p, 0xff, n1 * sizeof(uint32_t), c->stream));
-    if (dist.p) HIP_TRY(c, hipMemsetAsync(dist.p, 0xff, n1 * sizeof(uint16_t), c->stream));
-    if (ties.p) HIP_TRY(c, hipMemsetAsync(ties.p, 0, n1 * sizeof(uint32_t), c->stream));
-    P.nn_nearest = nearest.p; P.nn_dist = dist.p; P.nn_ties = ties.p;
-  } else {
-    /* ... nor is a (query, segment) whose range is empty: the fold writes every query from its slots */
-    if ((rc = dev_alloc(c, key.b, (size_t)(n1 * S)))) return rc;
-    if ((rc = dev_alloc(c, slot_ties.b, (size_t)(n1 * S)))) return rc;
-    HIP_TRY(c, hipMemsetAsync(key.b.p, 0xff, n1 * S * sizeof(unsigned long long), c->stream));
-    HIP_TRY(c, hipMemsetAsync(slot_ties.b.p, 0, n1 * S * sizeof(uint32_t), c->stream));
-    P.nn_key = key.b.p; P.nn_slot_ties = slot_ties.b.p;
-  }
-  if ((rc = hm_launch<SINK_NEAREST>(c, J)))
-    return rc;
-  if (S > 1) {
-    hipLaunchKernelGGL(hm_nearest_fold_kernel, dim3(blocks_for(n1, PAIRS_WG)), dim3(PAIRS_WG), 0, c->stream,
-                       (const unsigned long long *)key.b.p, (const uint32_t *)slot_ties.b.p, n1, (uint32_t)S,
-                       nearest.p, dist.p, ties.p);
-    HIP_TRY(c, hipGetLastError());
-  }
-  unsigned long long n_found = 0;
-  if (n_found_out) {
-    hipcub::TransformInputIterator<unsigned long long, HasTies, const uint32_t *> has(ties.p, HasTies());
-    size_t sum_bytes = 0;
-    if ((rc = dev_alloc(c, found.b, 1))) return rc;
-    HIP_TRY(c, hipcub::DeviceReduce::Sum(nullptr, sum_bytes, has, found.b.p, (int)n1, c->stream));
-    if ((rc = dev_alloc(c, sum_tmp.b, sum_bytes))) return rc;
-    HIP_TRY(c, hipcub::DeviceReduce::Sum(sum_tmp.b.p, sum_bytes, has, found.b.p, (int)n1, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(&n_found, found.b.p, sizeof n_found, hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (n_found_out)
-    *n_found_out = n_found;
-  c->hm_ms[1] = ms_since(t0);
-  if (!on_device) {
-    t0 = std::chrono::steady_clock::now();
-    if (nearest.wanted() && (rc = nearest.copy_out(c, (size_t)n1))) return rc;
-    if (dist.wanted() && (rc = dist.copy_out(c, (size_t)n1))) return rc;
-    if (ties.wanted() && (rc = ties.copy_out(c, (size_t)n1))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->hm_ms[2] = ms_since(t0);
-  }
-  return CMPR_OK;
+  return pairs_nearest(c, J, P.segments, nearest_out, dist_out, ties_out, n_found_out, on_device,
+                       [&](const PairNearest &N) {
+                         P.nn_nearest = N.nearest; P.nn_dist = N.dist; P.nn_ties = N.ties;
+                         P.nn_key = N.key; P.nn_slot_ties = N.slot_ties;
+                         return hm_launch<SINK_NEAREST>(c, J);
+                       },
+                       c->hm_ms, 2);
 }
 
 /* cmpr_hamming_cluster* and cmpr_hamming_cluster_table*: the set against itself through the link sink, then

@@ -43,9 +43,11 @@ EXPORTS = [
     "cmpr_edit_matrix", "cmpr_edit_matrix_device",
     "cmpr_edit_cluster", "cmpr_edit_cluster_device",
     "cmpr_edit_cluster_table", "cmpr_edit_cluster_table_device",
+    "cmpr_edit_nearest", "cmpr_edit_nearest_device",
 ]
 
 NEAREST_OTHER_REPERTOIRE = 1      # CMPR_NEAREST_OTHER_REPERTOIRE
+UNCAPPED = 2 ** 63 - 1            # max_distance of cmpr_edit_nearest*: above every sequence, no cap
 NO_NEAREST = 0xFFFFFFFF           # nearest of a sequence without a candidate (its ties are 0, its distance 0xFFFF)
 
 
@@ -166,6 +168,7 @@ def _argtypes() -> dict:
         "cmpr_edit_matrix": [ctx, view, view, C.c_int64, ptr],
         "cmpr_edit_cluster": [ctx, view, C.c_int64, ptr, ptr, u64p],
         "cmpr_edit_cluster_table": [ctx, view, C.c_int64, ptr, ptr, ptr, ptr, u64p],
+        "cmpr_edit_nearest": [ctx, view, view, C.c_int64, C.c_int64, C.c_uint32, ptr, ptr, ptr, u64p],
     }
     for name, args in twins.items():
         table[name] = table[name + "_device"] = args
@@ -683,6 +686,39 @@ class HipOverlap:
         return self._into_device(self._lib.cmpr_edit_cluster_table_device, view, (differences,), d_cluster_of,
                                  d_cluster_start, d_member, d_count)
 
+    # ---- the nearest neighbour under edit distance (include/compairr_hip.h: cmpr_edit_nearest*) ----
+
+    def edit_nearest(self, set1: RepertoireSet, set2: Optional[RepertoireSet] = None, min_distance: int = 1,
+                     max_distance: Optional[int] = None, other_repertoire: bool = False):
+        """(nearest uint32[n1], distance uint16[n1], ties uint32[n1]): for every sequence of set1 the smallest
+        Levenshtein distance over the sequences of set2 of its V and J (unless ignore_genes), of any length, that lie
+        at `min_distance` or more and at `max_distance` or less (None: uncapped), the smallest sequence number at
+        that distance and how many lie at it.  `set2` None or `set2 is set1`: one-set mode, a sequence is never its
+        own neighbour; `other_repertoire` (one-set mode only) admits only sequences of another repertoire.  Nobody:
+        (NO_NEAREST, 0xFFFF, 0).  The context's own `differences`, `indels` and resident sets play no part."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is None or set2 is set1 else _view(set2)
+        nearest = np.zeros(set1.n, dtype=np.uint32)
+        distance = np.zeros(set1.n, dtype=np.uint16)
+        ties = np.zeros(set1.n, dtype=np.uint32)
+        self._check(self._lib.cmpr_edit_nearest(
+            self._ctx, C.byref(v1), C.byref(v2), min_distance, UNCAPPED if max_distance is None else max_distance,
+            NEAREST_OTHER_REPERTOIRE if other_repertoire else 0, nearest.ctypes.data, distance.ctypes.data,
+            ties.ctypes.data, None))
+        return nearest, distance, ties
+
+    def edit_nearest_device(self, view1: _SetView, view2: _SetView, min_distance: int, max_distance: Optional[int],
+                            flags: int, d_nearest: int = 0, d_distance: int = 0, d_ties: int = 0) -> int:
+        """The same for views of device pointers (device_view; the same object twice: one-set mode) into the device
+        arrays d_nearest (uint32[n1]), d_distance (uint16[n1]) and d_ties (uint32[n1]); 0: not wanted.  Returns the
+        number of sequences of set1 that have a neighbour."""
+        n = C.c_uint64()
+        self._check(self._lib.cmpr_edit_nearest_device(
+            self._ctx, C.byref(view1), C.byref(view2), min_distance,
+            UNCAPPED if max_distance is None else max_distance, flags, C.c_void_p(d_nearest or None),
+            C.c_void_p(d_distance or None), C.c_void_p(d_ties or None), C.byref(n)))
+        return n.value
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -839,6 +875,16 @@ def edit_cluster_table(s: RepertoireSet, opt: Options, differences: int, tunable
     no part.  `tunables` are set on the context first (the result never depends on them)."""
     with _context(opt, tunables) as h:
         return h.edit_cluster_table(s, differences)
+
+
+def edit_nearest(set1: RepertoireSet, set2: Optional[RepertoireSet], opt: Options, min_distance: int = 1,
+                 max_distance: Optional[int] = None, other_repertoire: bool = False,
+                 tunables: Optional[dict] = None):
+    """Convenience: (nearest, distance, ties) of set1 against set2 under edit distance (HipOverlap.edit_nearest) on a
+    context of its own; `opt.differences` and `opt.indels` play no part.  `tunables` are set on the context first (the
+    result never depends on them)."""
+    with _context(opt, tunables) as h:
+        return h.edit_nearest(set1, set2, min_distance, max_distance, other_repertoire)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

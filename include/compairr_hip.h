@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*, cmpr_edit_cluster*, cmpr_edit_cluster_table*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*, cmpr_edit_cluster*, cmpr_edit_cluster_table*, cmpr_edit_nearest*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -868,6 +868,71 @@ int cmpr_edit_cluster_table_device(cmpr_context *ctx, const cmpr_set_view *d_set
                                    uint32_t *d_member_out, uint64_t *d_count_out, uint64_t *n_clusters_out);
 
 /*
+ * The nearest neighbour of every sequence under EDIT distance: cmpr_hamming_nearest() with the Levenshtein distance of
+ * cmpr_edit_*() in place of the number of differing positions.  cmpr_hamming_nearest() is blind to indels -- a CDR3
+ * whose only close relative is one residue longer has a far neighbour there, or none --, and cmpr_edit_cluster*() and
+ * cmpr_edit_neighbors() need a `differences`, which is read from the histogram of these distances.
+ *
+ * The candidates of sequence i of set1 are the sequences j of set2 that
+ *   - have the same V and J gene numbers unless options.ignore_genes; their LENGTH may be any, empty sequences
+ *     included;
+ *   - lie at a Levenshtein distance from i -- substitution, insertion and deletion cost 1 each -- of `min_distance` or
+ *     more and of `max_distance` or less.  min_distance: 0 admits everything, 1 leaves out the sequences with i's own
+ *     residues; negative is CMPR_EINVAL ("min_distance cannot be negative").  max_distance: the cap; negative is
+ *     CMPR_EINVAL ("max_distance cannot be negative"); a value above the longest sequence of either set behaves as that
+ *     length -- no edit distance exceeds it --, which is the uncapped call (INT64_MAX).  min_distance > max_distance is
+ *     CMPR_OK with nobody found;
+ *   - with set2 == set1 (the same pointer; the set is uploaded once) are not i itself, as in cmpr_hamming_nearest();
+ *   - with CMPR_NEAREST_OTHER_REPERTOIRE in `flags` come from another repertoire than i.  The flag is defined only
+ *     with set2 == set1: with two sets it is CMPR_EINVAL, and so is any other bit of `flags`.
+ *
+ * cmpr_edit_nearest() writes n1 elements of each output; any of them may be NULL:
+ *   distance_out[i]   the smallest distance D over the candidates of i.
+ *   nearest_out[i]    the smallest sequence number of set2 among the candidates at distance D.
+ *   ties_out[i]       the number of candidates at distance D.
+ * A sequence without a candidate gets nearest = 0xFFFFFFFF, distance = 0xFFFF and ties = 0; HERE 0xFFFF is
+ * unambiguous: the sequences have at most 256 residues, and so has every distance.  Elements behind n1 are not written.
+ *   *n_found_out      a HOST pointer in both variants, may be NULL: the number of i that have a candidate.
+ * cmpr_edit_nearest_device() takes DEVICE views and the three arrays as device memory on the context's device.
+ *
+ * Relation to the other calls.  The three arrays are what cmpr_edit_neighbors(differences = max_distance) gives when
+ * every row is filtered (floor, self, repertoire) and reduced to its minimum.  Uncapped, every i that
+ * cmpr_hamming_nearest() finds is found here, at a distance no larger.
+ *
+ * Both, as the rest of cmpr_edit_*(): synchronous; callable any time after cmpr_create(); options.differences and
+ * options.indels play no part and are NOT refused; the resident sets, plans and statistics are not disturbed; the sets
+ * are validated as every other set (same codes and texts, passed through unchanged); every temporary is freed on every
+ * return; results are bit-identical from run to run and under every tunable ((smallest distance, then smallest number)
+ * is a minimum, a tie count is an integer sum).  n1 == 0 or n2 == 0 is CMPR_OK with every i "none".  Refused before any
+ * device work, with the codes and texts of cmpr_hamming_nearest(): a NULL set, the tunable work_shard_count above 1,
+ * n_v_genes x n_j_genes above 2^46.  No score plays a part: MH, Jaccard, the ratio score and options.existence are NOT
+ * refused.  A set whose longest sequence has more than 256 residues is CMPR_EUNSUPPORTED ("cmpr_edit: a sequence of
+ * more than 256 residues"), as for cmpr_edit_neighbors().  At most 2^31-1 sequences per set.
+ *
+ * How (compairr_amd/csrc/edit.hip, the nearest sink of the compare kernel of cmpr_edit_*()): that kernel computes the
+ * full distance of every pair it walks.  A lane keeps three registers -- the smallest distance, the smallest sequence
+ * number at it, the number of references at it --, updated by compares and selects per reference; a walk goes partner
+ * by partner, which is not number order, so the numbers themselves are compared (staged beside the references).  A
+ * reference that is no candidate takes part at an infinite distance.  The partners of a group (L, V, J) are the set-2
+ * groups (L', V, J) with |L - L'| <= max_distance IN ORDER OF |L - L'|: no distance is below the length gap, so a
+ * workgroup leaves its partners at the first gap that no lane's smallest distance reaches any more -- exactly, nothing
+ * behind it can improve on or tie with what a lane holds; Hamming, with one partner per group, has nothing of the kind.
+ * With several segments every (query, segment) writes a slot and a small kernel folds them, as for
+ * cmpr_hamming_nearest(); a (workgroup, segment) stops on its own partial minimum, an upper bound of the final one.
+ * Device memory for the duration of the call: the set copies, group order, packed words, jobs and partners of
+ * cmpr_edit_*() above, 12 bytes per (query, segment) when there are several segments, and in the host variant the 10
+ * bytes per query of the outputs.
+ */
+int cmpr_edit_nearest(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                      int64_t min_distance, int64_t max_distance, uint32_t flags,
+                      uint32_t *nearest_out, uint16_t *distance_out, uint32_t *ties_out,
+                      uint64_t *n_found_out);
+int cmpr_edit_nearest_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                             int64_t min_distance, int64_t max_distance, uint32_t flags,
+                             uint32_t *d_nearest_out, uint16_t *d_distance_out, uint32_t *d_ties_out,
+                             uint64_t *n_found_out);
+
+/*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
  * runtime, the device's context, the code objects of the kernels the given options will run.
  * The reference has no counterpart -- its threads start in microseconds (overlap.cc:926-936);
@@ -1006,6 +1071,9 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
      "edit_words"            TEST ONLY: 2 or 4 forces at least that many 64-bit words per column, so that short
                              sequences run through the multiword forms; 0 (default): 1, 2 or 4 from the reference's
                              length
+     "edit_nearest_prune"    TEST ONLY, cmpr_edit_nearest*(): 1 (default) a workgroup leaves its partners at the first
+                             length gap no lane's smallest distance reaches; 0 walks every partner within the cap; the
+                             results are the same
    What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
    the state):
      before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",
@@ -1043,8 +1111,9 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    and the fill step for neighbours; for cmpr_edit_cluster*() the link kernel, the flatten and the sizes),
    "edit_order_us" (the rows sorted; 0 for a matrix, for clusters or when nothing was filled) and "edit_copy_us" (host
    variant: the results copied out).  cmpr_edit_cluster_table*() set these four as well, zero "cluster_links_us" and
-   set "cluster_table_us" (the table pass, its copies included: "edit_copy_us" stays 0); no cmpr_edit_*() call touches
-   the "hamming_*_us" timers. */
+   set "cluster_table_us" (the table pass, its copies included: "edit_copy_us" stays 0); cmpr_edit_nearest*() set
+   "edit_group_us", "edit_compare_us" (the walk, the fold of the slots, the count of the found) and "edit_copy_us" and
+   zero "edit_order_us"; no cmpr_edit_*() call touches the "hamming_*_us" timers. */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

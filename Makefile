@@ -77,6 +77,10 @@ $(OBJ_DIR)/edit.o: $(KERN_DIR)/edit.hip $(KERN_HDR)
 	@mkdir -p $(OBJ_DIR)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 
+$(OBJ_DIR)/tcrdist.o: $(KERN_DIR)/tcrdist.hip $(KERN_HDR)
+	@mkdir -p $(OBJ_DIR)
+	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+
 $(OBJ_DIR)/probe_v0.o: $(KERN_DIR)/probe_tu.hip $(KERN_HDR)
 	@mkdir -p $(OBJ_DIR)
 	$(HIPCC) $(HIPFLAGS) -DTU_VARIANT=0 -c -o $@ $<
@@ -110,7 +114,7 @@ $(OBJ_DIR)/probe_v2wi_nw%.o: $(KERN_DIR)/probe_tu.hip $(KERN_HDR)
 	$(HIPCC) $(HIPFLAGS) -DTU_VARIANT=2 -DTU_NW=$* -DTU_INLINE=1 -DTU_WIDE -c -o $@ $<
 
 $(LIB): $(OBJ_DIR)/main.o $(OBJ_DIR)/query_layout.o $(OBJ_DIR)/ref_index.o $(OBJ_DIR)/dedup.o $(OBJ_DIR)/cluster.o \
-        $(OBJ_DIR)/neighbors.o $(OBJ_DIR)/existence.o $(OBJ_DIR)/allpairs.o $(OBJ_DIR)/hamming.o $(OBJ_DIR)/edit.o $(TU_OBJS)
+        $(OBJ_DIR)/neighbors.o $(OBJ_DIR)/existence.o $(OBJ_DIR)/allpairs.o $(OBJ_DIR)/hamming.o $(OBJ_DIR)/edit.o $(OBJ_DIR)/tcrdist.o $(TU_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $^
 
 # diagnostic build with per-phase cycle counters in the probe kernel (tools/phase_timing.py)

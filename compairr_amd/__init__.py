@@ -8,12 +8,13 @@ no compute path of its own and no CPU fallback.
 """
 
 from .sets import RepertoireSet  # noqa: F401
-from .hip import (HipOverlap, HipError, Options, Stats, cluster, cluster_table, deduplicate, edit_cluster,  # noqa: F401
+from .hip import (HipOverlap, HipError, Options, Stats, TcrdistParams, cluster, cluster_table, deduplicate, edit_cluster,  # noqa: F401
                   edit_cluster_table, edit_matrix, edit_nearest, edit_neighbors, existence_csr,
                   hamming_cluster, hamming_cluster_table, hamming_matrix, hamming_nearest, hamming_neighbors,
-                  library_path, neighbors, neighbors_distance)
+                  library_path, neighbors, neighbors_distance, tcrdist_matrix, tcrdist_neighbors)
 
 __all__ = ["RepertoireSet", "HipOverlap", "HipError", "Options", "Stats", "cluster", "cluster_table", "deduplicate",
            "edit_cluster", "edit_cluster_table", "edit_matrix", "edit_nearest", "edit_neighbors", "existence_csr",
            "hamming_cluster", "hamming_cluster_table", "hamming_matrix",
-           "hamming_nearest", "hamming_neighbors", "library_path", "neighbors", "neighbors_distance"]
+           "hamming_nearest", "hamming_neighbors", "library_path", "neighbors", "neighbors_distance",
+           "TcrdistParams", "tcrdist_matrix", "tcrdist_neighbors"]

@@ -63,14 +63,22 @@ struct HmSet : StagedSet {
   Tmp<uint32_t> ord, pk;           /* sequence numbers in group order; the packed words */
   std::vector<uint64_t> keys;      /* of the groups, increasing: ((length x n_v) + V) x n_j + J, the length with ignore_genes */
   std::vector<HmGroup>  groups;
+  uint64_t per_len = 1;            /* keys per length: key / per_len is the length, key % per_len the genes */
 };
+
+/* what the key of a sequence holds: HM_KEY_LENGTH (ignore_genes), HM_KEY_LENGTH_V_J: ((length x n_v) + V) x n_j + J,
+   HM_KEY_LENGTH_V: length x n_v + V (cmpr_tcrdist_* with a V table: the J gene plays no part) */
+enum HmKeyMode { HM_KEY_LENGTH, HM_KEY_LENGTH_V_J, HM_KEY_LENGTH_V };
+
+/* the mode of every call whose pairs share both genes unless ignore_genes */
+inline HmKeyMode hm_key_mode(const cmpr_context *c) { return c->opt.ignore_genes ? HM_KEY_LENGTH : HM_KEY_LENGTH_V_J; }
 
 /* words per sequence of a group of `len` residues: the next word count the register form is compiled for, or the
    words themselves beyond HAMMING_REG_WORDS */
 uint32_t stride_of(uint32_t len, uint32_t per_word);
 
-/* the staged set H grouped and packed */
-int hm_prepare(cmpr_context *c, HmSet &H);
+/* the staged set H grouped by `mode` and packed */
+int hm_prepare(cmpr_context *c, HmSet &H, HmKeyMode mode);
 
 /* what a call makes of the pairs: the clusters and the nearest neighbours take no score, so what the reference refuses
    of scores is not theirs.  HM_NEAREST: `differences` is the call's min_distance */
@@ -87,11 +95,11 @@ struct PairSets {
   HmSet *s1 = nullptr, *s2 = nullptr;
 };
 
-/* Each set staged, handed to `check` (or none) and prepared, set 1 first: what `check` refuses of set 1 is refused
+/* Each set staged, handed to `check` (or none) and prepared (grouped by `mode`), set 1 first: what `check` refuses of set 1 is refused
    before set 2 is staged.  (hm_refusals has refused a bad view of either set before the first is staged: the look
    at it in cmpr_stage_set changes nothing.) */
 int pairs_stage(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, bool on_device, PairSets &W,
-                const std::function<int(const HmSet &)> &check = nullptr);
+                HmKeyMode mode, const std::function<int(const HmSet &)> &check = nullptr);
 
 /* the workgroups of a call in runs of one form of the compare kernel: a launch each */
 struct PairRuns {

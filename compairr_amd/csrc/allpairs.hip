@@ -32,7 +32,7 @@ namespace {
 
 struct KeyParams {
   const uint64_t *off;
-  const uint32_t *v, *j;           /* NULL: ignore_genes */
+  const uint32_t *v, *j;           /* NULL: not in the key */
   uint64_t        n, n_v, n_j;
   uint64_t       *key;
   uint32_t       *num;
@@ -46,7 +46,9 @@ hm_key_kernel(const KeyParams K)
     return;
   uint64_t key = K.off[i + 1] - K.off[i];
   if (K.v)
-    key = (key * K.n_v + K.v[i]) * K.n_j + K.j[i];
+    key = key * K.n_v + K.v[i];
+  if (K.j)
+    key = key * K.n_j + K.j[i];
   K.key[i] = key;
   K.num[i] = (uint32_t)i;
 }
@@ -127,8 +129,8 @@ struct HasTies {
 
 }  // namespace
 
-/* the staged set H grouped and packed */
-int cmpr::hm_prepare(cmpr_context *c, HmSet &H)
+/* the staged set H grouped by `mode` and packed */
+int cmpr::hm_prepare(cmpr_context *c, HmSet &H, HmKeyMode mode)
 {
   int rc;
   if (H.n == 0)
@@ -138,8 +140,9 @@ int cmpr::hm_prepare(cmpr_context *c, HmSet &H)
 
   /* keys, the stable sort, the runs */
   const uint64_t n = H.n;
-  const bool genes = !c->opt.ignore_genes;
+  const bool with_v = mode != HM_KEY_LENGTH, with_j = mode == HM_KEY_LENGTH_V_J;
   const uint64_t n_v = std::max<uint32_t>(1, c->opt.n_v_genes), n_j = std::max<uint32_t>(1, c->opt.n_j_genes);
+  H.per_len = (with_v ? n_v : 1) * (with_j ? n_j : 1);
   Tmp<uint64_t> key, key_sorted, run_key;
   Tmp<uint32_t> num, run_len, nruns;
   Tmp<char> scratch;
@@ -147,10 +150,10 @@ int cmpr::hm_prepare(cmpr_context *c, HmSet &H)
   if ((rc = dev_alloc(c, key_sorted.b, (size_t)n))) return rc;
   if ((rc = dev_alloc(c, num.b, (size_t)n))) return rc;
   if ((rc = dev_alloc(c, H.ord.b, (size_t)n))) return rc;
-  KeyParams K{H.off.b.p, genes ? H.v.b.p : nullptr, genes ? H.j.b.p : nullptr, n, n_v, n_j, key.b.p, num.b.p};
+  KeyParams K{H.off.b.p, with_v ? H.v.b.p : nullptr, with_j ? H.j.b.p : nullptr, n, n_v, n_j, key.b.p, num.b.p};
   hipLaunchKernelGGL(hm_key_kernel, dim3(blocks_for(n, PAIRS_WG)), dim3(PAIRS_WG), 0, c->stream, K);
   HIP_TRY(c, hipGetLastError());
-  const uint64_t key_max = genes ? ((uint64_t)H.longest + 1) * n_v * n_j : (uint64_t)H.longest + 1;
+  const uint64_t key_max = ((uint64_t)H.longest + 1) * H.per_len;
   int end_bit = 1;
   while (end_bit < 64 && (key_max >> end_bit))
     end_bit++;
@@ -184,7 +187,7 @@ int cmpr::hm_prepare(cmpr_context *c, HmSet &H)
   uint64_t start = 0, words = 0;
   for (uint32_t g = 0; g < G; g++) {
     HmGroup &x = H.groups[g];
-    x.len = (uint32_t)(genes ? H.keys[g] / (n_v * n_j) : H.keys[g]);
+    x.len = (uint32_t)(H.keys[g] / H.per_len);
     x.stride = stride_of(x.len, per_word);
     x.start = (uint32_t)start;
     x.count = lens[g];
@@ -236,13 +239,13 @@ int cmpr::hm_refusals(cmpr_context *c, const std::string &who, const cmpr_set_vi
 }
 
 int cmpr::pairs_stage(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, bool on_device, PairSets &W,
-                      const std::function<int(const HmSet &)> &check)
+                      HmKeyMode mode, const std::function<int(const HmSet &)> &check)
 {
   int rc;
   const auto stage = [&](const cmpr_set_view *set, HmSet &H) -> int {
     if ((rc = cmpr_stage_set(c, set, on_device, H)) || (check && (rc = check(H))))
       return rc;
-    return hm_prepare(c, H);
+    return hm_prepare(c, H, mode);
   };
   if ((rc = stage(set1, W.own1))) return rc;
   W.s1 = W.s2 = &W.own1;

@@ -375,6 +375,9 @@ const Tunable TUNABLES[] = {
   {"edit_segments", F(edit_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
   {"edit_words", F(edit_words), 0, 4, LOCK_NEVER, T_NO_PLAN, " must be 0 (from the length), 2 or 4", edit_words_ok},
   {"edit_nearest_prune", F(edit_nearest_prune), 0, 1, LOCK_NEVER, T_NO_PLAN, BOOL_RANGE},
+  /* TEST ONLY: the staging and the segments of cmpr_tcrdist_* (tcrdist.hip; tests/test_tcrdist_gpu.py) */
+  {"tcrdist_stage_refs", F(tcrdist_stage_refs), 0, 65536, LOCK_NEVER, T_NO_PLAN, " must be 0..65536"},
+  {"tcrdist_segments", F(tcrdist_segments), 0, 64, LOCK_NEVER, T_NO_PLAN, " must be 0..64"},
   {"resolve_blocks_per_cu", F(resolve_blocks_per_cu), 1, 8, LOCK_NEVER, 0, " must be 1..8"},
   {"pos_segments", F(pos_segments), 1, 256, LOCK_QUERIES, 0, " must be a power of two, 1..256", power_of_two},
   {"pos_grow", F(pos_grow), -1, 1, LOCK_NEVER, 0, AUTO_RANGE},
@@ -499,6 +502,10 @@ extern "C" int cmpr_get_tunable(cmpr_context *c, const char *name, int64_t *valu
   else if (n == "edit_compare_us") *value = (int64_t)(c->ed_ms[1] * 1e3);
   else if (n == "edit_order_us") *value = (int64_t)(c->ed_ms[2] * 1e3);
   else if (n == "edit_copy_us") *value = (int64_t)(c->ed_ms[3] * 1e3);
+  else if (n == "tcrdist_group_us") *value = (int64_t)(c->td_ms[0] * 1e3);
+  else if (n == "tcrdist_compare_us") *value = (int64_t)(c->td_ms[1] * 1e3);
+  else if (n == "tcrdist_order_us") *value = (int64_t)(c->td_ms[2] * 1e3);
+  else if (n == "tcrdist_copy_us") *value = (int64_t)(c->td_ms[3] * 1e3);
   else if (n == "never_overflows") *value = c->never_overflows ? 1 : 0;
   else if (n == "heavy_buckets") {
     *value = 0;

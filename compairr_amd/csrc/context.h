@@ -215,6 +215,9 @@ struct cmpr_context {
   int64_t edit_stage_refs = 0, edit_segments = 0, edit_words = 0;
   int64_t edit_link_snapshot = 1;     /* TEST ONLY, of cmpr_edit_cluster*: 0 = every match goes to link_pair */
   int64_t edit_nearest_prune = 1;     /* TEST ONLY, of cmpr_edit_nearest*: 0 = every partner within the cap is walked */
+  /* TEST ONLY, of cmpr_tcrdist_* (tcrdist.hip): references staged per LDS piece (0 = as many as fit), the segment
+     count (0 = automatic) */
+  int64_t tcrdist_stage_refs = 0, tcrdist_segments = 0;
   uint32_t chunk_cap = 0;         /* tiles per chunk in effect since cmpr_set_queries */
 
   /* sliced Bloom layout (variant 1) */
@@ -360,6 +363,7 @@ struct cmpr_context {
   double              cl_ms[2] = {};   /* ... of the last cmpr_cluster_table: labels and sizes | the table */
   double              hm_ms[3] = {};   /* ... of the last cmpr_hamming_*: upload, groups, packing | compare | copy-out */
   double              ed_ms[4] = {};   /* ... of the last cmpr_edit_*: upload, groups, packing, jobs | compare | row order | copy-out */
+  double              td_ms[4] = {};   /* ... of the last cmpr_tcrdist_*: the same four */
 };
 
 

@@ -418,7 +418,7 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
 {
   const bool triangular = order == ED_TRIANGULAR;
   int rc;
-  if ((rc = pairs_stage(c, set1, set2, on_device, J, [&](const HmSet &H) {
+  if ((rc = pairs_stage(c, set1, set2, on_device, J, hm_key_mode(c), [&](const HmSet &H) {
          return H.longest > ED_MAX_LEN ? fail(c, CMPR_EUNSUPPORTED, "cmpr_edit: a sequence of more than 256 residues")
                                        : CMPR_OK;
        })))

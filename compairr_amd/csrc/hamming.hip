@@ -297,7 +297,7 @@ int hm_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
              int64_t differences, bool on_device, HmJob &J, bool triangular = false)
 {
   int rc;
-  if ((rc = pairs_stage(c, set1, set2, on_device, J))) return rc;
+  if ((rc = pairs_stage(c, set1, set2, on_device, J, hm_key_mode(c)))) return rc;
   HmSet &A = *J.s1, &B = *J.s2;
   /* the groups of the two sets with one key; their workgroups, in runs of one form */
   std::vector<HmPair> pairs;

@@ -44,11 +44,14 @@ EXPORTS = [
     "cmpr_edit_cluster", "cmpr_edit_cluster_device",
     "cmpr_edit_cluster_table", "cmpr_edit_cluster_table_device",
     "cmpr_edit_nearest", "cmpr_edit_nearest_device",
+    "cmpr_tcrdist_neighbors", "cmpr_tcrdist_neighbors_device",
+    "cmpr_tcrdist_matrix", "cmpr_tcrdist_matrix_device",
 ]
 
 NEAREST_OTHER_REPERTOIRE = 1      # CMPR_NEAREST_OTHER_REPERTOIRE
 UNCAPPED = 2 ** 63 - 1            # max_distance of cmpr_edit_nearest*: above every sequence, no cap
 NO_NEAREST = 0xFFFFFFFF           # nearest of a sequence without a candidate (its ties are 0, its distance 0xFFFF)
+GAP_FIXED, GAP_SLIDING = 0, 1     # CMPR_GAP_FIXED, CMPR_GAP_SLIDING
 
 
 class HipError(RuntimeError):
@@ -80,6 +83,51 @@ class _Stats(C.Structure):
                 ("kernel_ms", C.c_double), ("total_ms", C.c_double),
                 ("kernel_launches", C.c_uint32), ("reserved", C.c_uint32),
                 ("probe_ms", C.c_double), ("filter_reads", C.c_uint64)]
+
+
+class _TcrdistParams(C.Structure):
+    _fields_ = [("substitution", C.c_void_p), ("v_distance", C.c_void_p),
+                ("gap_penalty", C.c_uint32), ("ntrim", C.c_uint32), ("ctrim", C.c_uint32), ("gap_mode", C.c_uint32),
+                ("reserved", C.c_uint32 * 4)]
+
+
+class TcrdistParams:
+    """The parameters of tcrdist_neighbors() / tcrdist_matrix() (include/compairr_hip.h: cmpr_tcrdist_params):
+    `substitution` uint8[A, A] indexed [set-1 residue][set-2 residue] (A = 20), optionally `v_distance`
+    uint16[n_v_genes, n_v_genes] indexed [set-1 V][set-2 V], the gap penalty per residue of length difference, the
+    trims and the gap mode.  Shapes and dtypes are checked here -- a table is converted only where no value changes
+    -- and the holder keeps the arrays the C struct points to alive."""
+
+    def __init__(self, substitution, gap_penalty: int, ntrim: int = 3, ctrim: int = 2, gap_mode: int = GAP_FIXED,
+                 v_distance=None):
+        self.substitution = self._table(substitution, np.uint8, "substitution")
+        if self.substitution.shape[0] != 20:
+            raise ValueError("substitution must be 20 x 20 (amino acids)")
+        self.v_distance = None if v_distance is None else self._table(v_distance, np.uint16, "v_distance")
+        for name, value in (("gap_penalty", gap_penalty), ("ntrim", ntrim), ("ctrim", ctrim), ("gap_mode", gap_mode)):
+            if not 0 <= int(value) < 2 ** 32:
+                raise ValueError("%s must fit an unsigned 32-bit word" % name)
+        self.gap_penalty, self.ntrim, self.ctrim, self.gap_mode = int(gap_penalty), int(ntrim), int(ctrim), int(gap_mode)
+
+    @staticmethod
+    def _table(a, dtype, name):
+        a = np.asarray(a)
+        if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] == 0:
+            raise ValueError("%s must be a square table" % name)
+        if a.dtype.kind not in "iu" or a.min() < 0 or a.max() > np.iinfo(dtype).max:
+            raise ValueError("%s must hold integers that fit %s" % (name, np.dtype(dtype).name))
+        return np.ascontiguousarray(a, dtype=dtype)
+
+    def struct(self, opt: "Options") -> _TcrdistParams:
+        """the C struct for a context of these options: the V table must have the context's V genes (a context of
+        nucleotides is the library's to refuse)"""
+        if self.v_distance is not None and self.v_distance.shape[0] != max(1, opt.n_v_genes):
+            raise ValueError("v_distance must be n_v_genes x n_v_genes")
+        t = _TcrdistParams()
+        t.substitution = self.substitution.ctypes.data
+        t.v_distance = None if self.v_distance is None else self.v_distance.ctypes.data
+        t.gap_penalty, t.ntrim, t.ctrim, t.gap_mode = self.gap_penalty, self.ntrim, self.ctrim, self.gap_mode
+        return t
 
 
 @dataclass
@@ -126,6 +174,7 @@ def _argtypes() -> dict:
     """argtypes per entry point; a host variant and its _device twin that take the same arguments are written once."""
     ctx = ptr = C.c_void_p
     opts, view, u64p = C.POINTER(_Options), C.POINTER(_SetView), C.POINTER(C.c_uint64)
+    tcr = C.POINTER(_TcrdistParams)
     table = {
         "cmpr_create": [opts, C.POINTER(C.c_void_p)],
         "cmpr_destroy": [ctx],
@@ -169,6 +218,8 @@ def _argtypes() -> dict:
         "cmpr_edit_cluster": [ctx, view, C.c_int64, ptr, ptr, u64p],
         "cmpr_edit_cluster_table": [ctx, view, C.c_int64, ptr, ptr, ptr, ptr, u64p],
         "cmpr_edit_nearest": [ctx, view, view, C.c_int64, C.c_int64, C.c_uint32, ptr, ptr, ptr, u64p],
+        "cmpr_tcrdist_neighbors": [ctx, view, view, tcr, C.c_int64, C.c_uint64, ptr, ptr, ptr, u64p],
+        "cmpr_tcrdist_matrix": [ctx, view, view, tcr, C.c_int64, ptr],
     }
     for name, args in twins.items():
         table[name] = table[name + "_device"] = args
@@ -719,6 +770,55 @@ class HipOverlap:
             C.c_void_p(d_distance or None), C.c_void_p(d_ties or None), C.byref(n)))
         return n.value
 
+    # ---- the all-against-all path under the weighted CDR3 distance (include/compairr_hip.h: cmpr_tcrdist_*) ----
+
+    def tcrdist_neighbors(self, set1: RepertoireSet, set2: RepertoireSet, params: TcrdistParams, cutoff: int,
+                          distances: bool = True):
+        """(row_start uint64[n1 + 1], hits uint32[E], distance uint16[E] or None): the pairs at a weighted CDR3
+        distance of at most `cutoff` under `params` as CSR -- the hits of sequence i of set1, increasing, are
+        hits[row_start[i]:row_start[i + 1]], the distance beside each.  Without a V table the pairs share V and J
+        (unless ignore_genes); with one any two V genes pair at the table's price.  `set2 is set1`: one-file mode,
+        the (i, i) pairs included.  One count-only call, then one with the exact capacity."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is set1 else _view(set2)
+        t = params.struct(self.opt)
+        return tuple(self._count_then_fill(self._lib.cmpr_tcrdist_neighbors,
+                                           (C.byref(v1), C.byref(v2), C.byref(t), cutoff),
+                                           lambda: set1.n, (np.uint32, np.uint16 if distances else None)))
+
+    def tcrdist_neighbors_device(self, view1: _SetView, view2: _SetView, params: TcrdistParams, cutoff: int,
+                                 capacity: int = 0, d_row_start: int = 0, d_hits: int = 0, d_distance: int = 0) -> int:
+        """The same for views of device pointers into device arrays: d_row_start (uint64[n1 + 1]; 0: not wanted),
+        d_hits (uint32[capacity]; 0 with capacity 0: count only) and d_distance (uint16[capacity]; 0: hits only);
+        `params` stays host memory.  Returns the edge count; when it exceeds `capacity` nothing was written to
+        d_hits or d_distance."""
+        n = C.c_uint64()
+        t = params.struct(self.opt)
+        self._check(self._lib.cmpr_tcrdist_neighbors_device(
+            self._ctx, C.byref(view1), C.byref(view2), C.byref(t), cutoff, capacity, C.c_void_p(d_row_start or None),
+            C.c_void_p(d_hits or None), C.c_void_p(d_distance or None), C.byref(n)))
+        return n.value
+
+    def tcrdist_matrix(self, set1: RepertoireSet, set2: RepertoireSet, params: TcrdistParams, cutoff: int) -> np.ndarray:
+        """The R1 x R2 matrix (n1 x R2 with `existence`) of set1 against set2 over the pairs of tcrdist_neighbors()
+        -- the integer sums of edit_matrix()."""
+        v1 = _view(set1)
+        v2 = v1 if set2 is set1 else _view(set2)
+        t = params.struct(self.opt)
+        rows = set1.n if self.opt.existence else set1.n_repertoires
+        out = np.zeros((rows, set2.n_repertoires), dtype=np.uint64)
+        self._check(self._lib.cmpr_tcrdist_matrix(self._ctx, C.byref(v1), C.byref(v2), C.byref(t), cutoff,
+                                                  out.ctypes.data))
+        return out
+
+    def tcrdist_matrix_device(self, view1: _SetView, view2: _SetView, params: TcrdistParams, cutoff: int,
+                              d_matrix: int) -> None:
+        """The same for views of device pointers (device_view; the same object twice: one-file mode) into the
+        device array d_matrix (uint64[R1 * R2], or [n1 * R2] with `existence`)."""
+        t = params.struct(self.opt)
+        self._check(self._lib.cmpr_tcrdist_matrix_device(self._ctx, C.byref(view1), C.byref(view2), C.byref(t), cutoff,
+                                                         C.c_void_p(d_matrix or None)))
+
     def _queries(self) -> int:
         return self.stats().queries
 
@@ -885,6 +985,24 @@ def edit_nearest(set1: RepertoireSet, set2: Optional[RepertoireSet], opt: Option
     result never depends on them)."""
     with _context(opt, tunables) as h:
         return h.edit_nearest(set1, set2, min_distance, max_distance, other_repertoire)
+
+
+def tcrdist_neighbors(set1: RepertoireSet, set2: RepertoireSet, opt: Options, params: TcrdistParams, cutoff: int,
+                      distances: bool = True, tunables: Optional[dict] = None):
+    """Convenience: (row_start, hits, distance) of set1 against set2 at a weighted CDR3 distance of at most `cutoff`
+    (HipOverlap.tcrdist_neighbors) on a context of its own; `opt.differences` and `opt.indels` play no part.
+    `tunables`: {name: value}."""
+    with _context(opt, tunables) as h:
+        return h.tcrdist_neighbors(set1, set2, params, cutoff, distances)
+
+
+def tcrdist_matrix(set1: RepertoireSet, set2: RepertoireSet, opt: Options, params: TcrdistParams, cutoff: int,
+                   tunables: Optional[dict] = None):
+    """Convenience: the matrix of set1 against set2 over the pairs at a weighted CDR3 distance of at most `cutoff`
+    (HipOverlap.tcrdist_matrix) on a context of its own; `opt.differences` and `opt.indels` play no part.
+    `tunables`: {name: value}."""
+    with _context(opt, tunables) as h:
+        return h.tcrdist_matrix(set1, set2, params, cutoff)
 
 
 def existence_csr(set1: RepertoireSet, set2: RepertoireSet, opt: Options, tunables: Optional[dict] = None):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*, cmpr_edit_cluster*, cmpr_edit_cluster_table*, cmpr_edit_nearest*) break
+/* Counts INCOMPATIBLE changes: entry points and tunables added since (cmpr_deduplicate*, cmpr_cluster*, cmpr_neighbors*, cmpr_neighbors_distance*, cmpr_existence_csr*, cmpr_cluster_table*, cmpr_hamming_matrix*, cmpr_hamming_neighbors*, cmpr_hamming_cluster*, cmpr_hamming_cluster_table*, cmpr_hamming_nearest*, cmpr_edit_neighbors*, cmpr_edit_matrix*, cmpr_edit_cluster*, cmpr_edit_cluster_table*, cmpr_edit_nearest*, cmpr_tcrdist_neighbors*, cmpr_tcrdist_matrix*) break
    no caller and leave it as it is. */
 #define CMPR_ABI_VERSION 5
 
@@ -933,6 +933,88 @@ int cmpr_edit_nearest_device(cmpr_context *ctx, const cmpr_set_view *d_set1, con
                              uint64_t *n_found_out);
 
 /*
+ * The all-against-all path under the WEIGHTED CDR3 distance of the TCR field -- the metric behind tcrdist3 and scirpy's
+ * "tcrdist": a substitution-table-weighted mismatch sum over the CDR3, the ends trimmed, ONE gap block charged per
+ * residue of length difference, optionally a V-gene term on top.  Neither cmpr_hamming_*() nor cmpr_edit_*() can
+ * express it: there "L -> I" costs what "L -> D" costs, the conserved CAS... / ...QYF ends count, two lengths align with
+ * free indels, and two V genes are equal or not.  The reference has no counterpart.
+ *
+ * The distance.  W = params->substitution, alphabet_size x alphabet_size uint8, indexed [residue of the set-1 sequence]
+ * [residue of the set-2 sequence]; no symmetry and no zero diagonal are assumed.  For x of set 1 and y of set 2:
+ *   equal length L     D = sum over k = ntrim .. L - 1 - ctrim of W[x_k][y_k]; an empty range gives 0.
+ *   different lengths  s the shorter (Ls residues), l the longer, delta = Ll - Ls.  For a gap position g, 0 <= g <= Ls,
+ *                        cost(g) = sum_{k = ntrim}^{g - 1} w(s_k, l_k) + sum_{k = g}^{Ls - 1 - ctrim} w(s_k, l_{k + delta})
+ *                      where w is W indexed [set-1 residue][set-2 residue] WHICHEVER of the two is the shorter, and
+ *                        D = min_{g = lo .. hi} cost(g) + delta x gap_penalty.
+ *                      CMPR_GAP_FIXED:   lo = hi = min(6, 3 + floor((Ls - 5) / 2)) (a mathematical floor: Ls = 0 gives 0);
+ *                      CMPR_GAP_SLIDING: lo = 5, hi = Ls - 5; while lo > hi: lo -= 1, hi += 1.
+ *                      Both keep 0 <= lo <= hi <= Ls for every Ls.
+ *   with a V table     D += params->v_distance[v1][v2], n_v_genes x n_v_genes uint16, v1 the V gene number of x.
+ * (i, j) is a pair when D <= cutoff and the genes admit it: without v_distance the same V and J gene numbers unless
+ * options.ignore_genes, as in every other call; WITH v_distance any two V genes pair, at the table's price, and the J
+ * gene plays no part.  With set2 == set1 (the same pointer) the set is uploaded once and the (i, i) pairs are included.
+ *
+ * cmpr_tcrdist_neighbors() gives the pairs as CSR with the distance of every edge, under the protocol of
+ * cmpr_edit_neighbors(), word for word: row_start_out[n1 + 1] always written in full and always exact, may be NULL;
+ * hit_out[capacity] the rows, sequence numbers of set2 in strictly increasing order; with more edges than `capacity`
+ * NOTHING is written to hit_out or distance_out and the call still returns CMPR_OK with *n_edges_out > capacity;
+ * capacity == 0 with both arrays NULL is the count-only call; capacity > 0 with hit_out NULL is CMPR_EINVAL; elements
+ * behind the last edge are not written; distance_out[capacity] is D, 0 .. cutoff, and may be NULL (hits only);
+ * *n_edges_out is required (NULL: CMPR_EINVAL), a HOST pointer in both variants, == row_start[n1].
+ * cmpr_tcrdist_matrix() writes R1 x R2 uint64 -- n1 x R2 with options.existence -- of the integer sums
+ * cmpr_edit_matrix() documents, over these pairs; the output is overwritten.  The _device variants take DEVICE views
+ * and device arrays; `params` and the two tables it points to are HOST memory in both variants, read during the call.
+ *
+ * All four: synchronous; callable any time after cmpr_create(); options.differences and options.indels play no part and
+ * are NOT refused; the sets are validated as every other set; the resident sets, plans and statistics are not disturbed;
+ * every temporary is freed on every return; results are bit-identical from run to run and under every tunable (integer
+ * sums; the hits of a row are distinct, so the row order is total).  n1 == 0 or n2 == 0 is CMPR_OK with a zero matrix,
+ * or row_start all zero.  Refused before any device work: what cmpr_edit_*() refuse, with `cutoff` in the place of
+ * `differences` and the same codes and texts (negative; a NULL set; the tunable work_shard_count above 1;
+ * n_v_genes x n_j_genes above 2^46; CMPR_SCORE_RATIO without ignore_counts in _matrix; MH / Jaccard with cutoff > 0);
+ * NULL params or params->substitution (CMPR_EINVAL); cutoff > 65535 (CMPR_EINVAL: the distance column is uint16); a
+ * nonzero reserved word or a gap_mode other than the two (CMPR_EINVAL); v_distance with options.ignore_genes
+ * (CMPR_EINVAL: there are no V gene numbers); alphabet_size == 4 (CMPR_EUNSUPPORTED, "cmpr_tcrdist: amino acids only").
+ * A set whose longest sequence has more than 256 residues is CMPR_EUNSUPPORTED
+ * ("cmpr_tcrdist: a sequence of more than 256 residues"), decided when the set has been validated on the device, as for
+ * cmpr_edit_neighbors().  At most 2^31-1 sequences per set.
+ *
+ * How (compairr_amd/csrc/tcrdist.hip): the sets are grouped by (length, V, J) -- (length, V) with a V table, the length
+ * with ignore_genes -- and packed as for cmpr_edit_*().  The host pairs every set-1 group with the set-2 groups whose
+ * base = |L - L'| x gap_penalty + V[v1][v2] (64 bits) is at most the cutoff -- a positive penalty bounds the lengths, 0
+ * admits every length -- and works out, per pair of groups, everything the alignment needs: the kernel never touches
+ * genes.  A workgroup compares 256 queries of a group with a segment of every such partner, staged in LDS as packed;
+ * W lies in LDS transposed, a padded row per reference residue, so that the reference residue a wave meets is one
+ * broadcast read and the lanes' costs come from one short row.  Per aligned position a lookup and an add, two in the
+ * zone of gap positions SLIDING tries; the running minimum over the gap positions needs one pass and no array.  A walk
+ * goes partner by partner, so the rows are sorted afterwards (by the hit; distances carried along).  Device memory for
+ * the duration of the call: what cmpr_edit_neighbors() / _matrix() take, with 64 bytes per pair of groups.
+ *
+ * Out of scope: clusters and nearest neighbours under this metric; nucleotides; a shipped BLOSUM-derived default table
+ * (the caller supplies W already multiplied by its weight); paired chains; the command line.
+ */
+enum { CMPR_GAP_FIXED = 0, CMPR_GAP_SLIDING = 1 };
+typedef struct cmpr_tcrdist_params {
+  const uint8_t  *substitution;  /* alphabet_size x alphabet_size, [set-1 residue][set-2 residue]; HOST memory in both variants */
+  const uint16_t *v_distance;    /* n_v_genes x n_v_genes or NULL; HOST memory in both variants */
+  uint32_t gap_penalty, ntrim, ctrim, gap_mode;
+  uint32_t reserved[4];          /* must be zero */
+} cmpr_tcrdist_params;
+
+int cmpr_tcrdist_neighbors(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                           const cmpr_tcrdist_params *params, int64_t cutoff, uint64_t capacity,
+                           uint64_t *row_start_out, uint32_t *hit_out, uint16_t *distance_out,
+                           uint64_t *n_edges_out);
+int cmpr_tcrdist_neighbors_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                                  const cmpr_tcrdist_params *params, int64_t cutoff, uint64_t capacity,
+                                  uint64_t *d_row_start_out, uint32_t *d_hit_out, uint16_t *d_distance_out,
+                                  uint64_t *n_edges_out);
+int cmpr_tcrdist_matrix(cmpr_context *ctx, const cmpr_set_view *set1, const cmpr_set_view *set2,
+                        const cmpr_tcrdist_params *params, int64_t cutoff, uint64_t *matrix_out);
+int cmpr_tcrdist_matrix_device(cmpr_context *ctx, const cmpr_set_view *d_set1, const cmpr_set_view *d_set2,
+                               const cmpr_tcrdist_params *params, int64_t cutoff, void *d_matrix);
+
+/*
  * (ABI v4)  What a process pays once before its first launch, asked for early: the HIP
  * runtime, the device's context, the code objects of the kernels the given options will run.
  * The reference has no counterpart -- its threads start in microseconds (overlap.cc:926-936);
@@ -1074,6 +1156,10 @@ uint32_t cmpr_cols(const cmpr_context *ctx);      /* R2, after set_reference */
      "edit_nearest_prune"    TEST ONLY, cmpr_edit_nearest*(): 1 (default) a workgroup leaves its partners at the first
                              length gap no lane's smallest distance reaches; 0 walks every partner within the cap; the
                              results are the same
+     "tcrdist_stage_refs"    TEST ONLY, cmpr_tcrdist_*(): references staged per LDS piece (0 = default: as many packed
+                             sequences as fit 16 KiB, at most 512; a larger value is clamped to that)
+     "tcrdist_segments"      TEST ONLY: forces the number of segments every partner group is walked in (1..64; 0 =
+                             default: automatic, from the number of query workgroups)
    What locks when (a locked name is refused with CMPR_ESTATE; a value out of range with CMPR_EINVAL, whatever
    the state):
      before cmpr_set_reference():  "variant", "bloom_bits_log2_delta", "class_residues", "class_anchor",
@@ -1113,7 +1199,9 @@ int cmpr_set_tunable(cmpr_context *ctx, const char *name, int64_t value);
    variant: the results copied out).  cmpr_edit_cluster_table*() set these four as well, zero "cluster_links_us" and
    set "cluster_table_us" (the table pass, its copies included: "edit_copy_us" stays 0); cmpr_edit_nearest*() set
    "edit_group_us", "edit_compare_us" (the walk, the fold of the slots, the count of the found) and "edit_copy_us" and
-   zero "edit_order_us"; no cmpr_edit_*() call touches the "hamming_*_us" timers. */
+   zero "edit_order_us"; no cmpr_edit_*() call touches the "hamming_*_us" timers; and of the last cmpr_tcrdist_*(), with
+   the meaning of their edit_* twins: "tcrdist_group_us", "tcrdist_compare_us", "tcrdist_order_us" and
+   "tcrdist_copy_us" (no cmpr_tcrdist_*() call touches the timers of another family). */
 int cmpr_get_tunable(cmpr_context *ctx, const char *name, int64_t *value);
 
 #ifdef __cplusplus

@@ -41,6 +41,8 @@
 #include "context.h"
 #include "link_forest.h"
 
+#include <algorithm>
+
 namespace cmpr {
 
 constexpr uint32_t PAIRS_WG = 256;             /* four waves: four 64-query tiles of one group */
@@ -50,6 +52,9 @@ constexpr uint32_t PAIRS_MAX_SEGMENTS = 64;
 constexpr uint32_t HAMMING_REG_WORDS = 16;     /* the bound between the two forms: a group of more words per sequence
                                                   (64 amino acids, 256 nucleotides) takes the generic form */
 constexpr uint32_t AA_PER_WORD = 4, NT_PER_WORD = 16;
+/* the calls that walk jobs (edit.hip, tcrdist.hip) */
+constexpr uint32_t PAIRS_MAX_LEN = 256;        /* residues of the longest sequence: four 64-bit column words */
+constexpr uint32_t PAIRS_REG_RESIDUES = 64;    /* a query of more residues is read from global memory (NW = 0) */
 
 /* a group of one set: the sequences at positions start .. start + count - 1 of the sorted order */
 struct HmGroup {
@@ -101,6 +106,10 @@ struct PairSets {
 int pairs_stage(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_view *set2, bool on_device, PairSets &W,
                 HmKeyMode mode, const std::function<int(const HmSet &)> &check = nullptr);
 
+/* pairs_stage's `check` of the calls that walk jobs: a set with a sequence of more than PAIRS_MAX_LEN residues is
+   refused, in the name of `prefix` (cmpr_edit, cmpr_tcrdist) */
+std::function<int(const HmSet &)> pairs_length_check(cmpr_context *c, const char *prefix);
+
 /* the workgroups of a call in runs of one form of the compare kernel: a launch each */
 struct PairRuns {
   struct Run { uint32_t form, blk0, blocks; };
@@ -120,6 +129,107 @@ struct PairRuns {
    longest_piece, none longer than that many references. */
 uint32_t pairs_segments(const cmpr_context *c, int64_t tunable, uint64_t blocks, uint32_t nr_max,
                         uint32_t longest_piece = 0);
+
+/* ---- jobs: a set-1 group against SEVERAL set-2 groups (edit.hip, tcrdist.hip) ---- */
+
+/* a set-1 group and its partners; what a partner record holds is the caller's (EdPartner, TdPartner: pk_off, r0 and nr
+   of the set-2 group and what the compare needs of the two lengths) */
+struct PairJob {
+  uint64_t pk1;                    /* first packed word of the group */
+  uint32_t q0, nq;                 /* positions in set 1's sorted order */
+  uint32_t len, stride;
+  uint32_t p0, np;                 /* its partners in the partner array */
+  uint32_t blk0, pad;              /* first workgroup (grid x) of the job */
+};
+
+/* the register form of a query of `len` residues in `stride` packed words: 2, 4, 8, 16, or 0 */
+uint32_t pairs_form_of(uint32_t len, uint32_t stride);
+
+/* the lengths a set has, increasing, and the first group of each (the keys increase with the length) */
+struct PairLengths {
+  std::vector<uint32_t> len;
+  std::vector<size_t>   first;
+  explicit PairLengths(const HmSet &S);
+};
+
+/* the group of S with this key, or NULL: a binary search */
+const HmGroup *hm_group_of(const HmSet &S, uint64_t key);
+
+/* both sets of a call and its job table on the device */
+template <typename Partner>
+struct PairJobs : PairSets {
+  Tmp<PairJob>   jobs;
+  Tmp<Partner>   partners;
+  PairRuns       runs;             /* form: pairs_form_of */
+  uint64_t       blocks = 0;       /* workgroups of query tiles */
+  uint32_t       nr_max = 0;       /* sequences of the largest partner: both for the caller's pairs_segments */
+};
+
+/* The job table of the two prepared sets of J.  partners_of(ga, genes, L2, partners) appends the partners of the set-1
+   group ga, whose key holds `genes` behind the length, to `partners` -- L2: the lengths of set 2 -- and may reorder
+   what it appended; a group it appends nothing for gets no job.  The jobs in set 1's group order, their workgroups in
+   runs of one query form, the two tables uploaded, and the fields of the parameters every such kernel has: jobs,
+   partners, njobs, pk1, pk2, ord1, ord2. */
+template <typename Partner, typename Params, typename PartnersOf>
+int pairs_jobs(cmpr_context *c, const std::string &who, PairJobs<Partner> &J, Params &P, PartnersOf partners_of)
+{
+  int rc;
+  const HmSet &A = *J.s1, &B = *J.s2;
+  const PairLengths L2(B);
+  std::vector<PairJob> jobs;
+  std::vector<Partner> partners;
+  for (size_t a = 0; a < A.groups.size(); a++) {
+    const HmGroup &ga = A.groups[a];
+    const size_t p0 = partners.size();
+    partners_of(ga, A.keys[a] % A.per_len, L2, partners);
+    if (partners.size() == p0)
+      continue;
+    if (partners.size() > 0xffffffffull)
+      return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^32-1 pairs of groups");
+    for (size_t p = p0; p < partners.size(); p++)
+      J.nr_max = std::max(J.nr_max, partners[p].nr);
+    const uint32_t nb = blocks_for(ga.count, PAIRS_WG);
+    J.runs.add(pairs_form_of(ga.len, ga.stride), (uint32_t)J.blocks, nb);
+    jobs.push_back(PairJob{ga.pk_off, ga.start, ga.count, ga.len, ga.stride, (uint32_t)p0,
+                           (uint32_t)(partners.size() - p0), (uint32_t)J.blocks, 0u});
+    J.blocks += nb;
+    if (J.blocks > 0xffffffu)
+      return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^24 workgroups of queries");
+  }
+  if (!jobs.empty()) {
+    if ((rc = dev_upload(c, J.jobs.b, jobs.data(), jobs.size()))) return rc;
+    if ((rc = dev_upload(c, J.partners.b, partners.data(), partners.size()))) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));           /* (the two vectors leave scope) */
+  }
+  P.jobs = J.jobs.b.p;
+  P.partners = J.partners.b.p;
+  P.njobs = (uint32_t)jobs.size();
+  P.pk1 = A.pk.b.p; P.pk2 = B.pk.b.p;
+  P.ord1 = A.ord.b.p; P.ord2 = B.ord.b.p;
+  return CMPR_OK;
+}
+
+/* ---- what the entry points do around their setup ---- */
+
+/* `setup` between the caller's timers zeroed -- and the cluster table's, for the table calls -- and ms[0], the time it
+   took */
+template <size_t N, typename Setup>
+int pairs_timed_setup(cmpr_context *c, double (&ms)[N], bool table, Setup setup)
+{
+  const auto t0 = std::chrono::steady_clock::now();
+  for (double &t : ms)
+    t = 0;
+  if (table)
+    c->cl_ms[0] = c->cl_ms[1] = 0;
+  const int rc = setup();
+  if (!rc)
+    ms[0] = ms_since(t0);
+  return rc;
+}
+
+/* the argument checks of the *_neighbors calls, in front of their refusals; the edge count is zeroed */
+int pairs_neighbors_args(cmpr_context *c, const std::string &who, uint64_t capacity, const uint32_t *hit_out,
+                         uint64_t *n_edges_out);
 
 /* the sink fields of a compare kernel's parameters */
 struct PairSinks {
@@ -236,10 +346,67 @@ struct PairQuery {
   __device__ __forceinline__ bool active() const { return qi < nq; }
 };
 
+/* the lane's query in packed words: `w` its first one, `stride` of them; q[] the first NW in registers (zero beyond the
+   stride), indexed at compile time only.  NW = 0: no registers, the words are read through w */
+template <int NW>
+struct PairWords {
+  const uint32_t *const w;
+  uint32_t q[NW ? NW : 1];
+  template <typename T>
+  __device__ __forceinline__ PairWords(const uint32_t *pk1, const T &t, const PairQuery &Q, uint32_t stride)
+      : w(pk1 + t.pk1 + (uint64_t)(Q.qpos - t.q0) * stride)
+  {
+    if (NW) {
+#pragma unroll
+      for (int k = 0; k < NW; k++)
+        q[k] = (uint32_t)k < stride ? w[k] : 0u;
+    }
+  }
+};
+
+/* segment `seg` of `segments`, [e0, e1), of the references behind w0 of a group of nr */
+__device__ __forceinline__ void pairs_segment(uint32_t nr, uint32_t w0, uint32_t seg, uint32_t segments, uint32_t &e0,
+                                              uint32_t &e1)
+{
+  e0 = w0 + (uint32_t)((uint64_t)(nr - w0) * seg / segments);
+  e1 = w0 + (uint32_t)((uint64_t)(nr - w0) * (seg + 1) / segments);
+}
+
+/* references of a staged piece: as many as fit the kernel's buffer, the id arrays and the stage_refs tunable (0: none,
+   it wraps to the largest number) */
+__device__ __forceinline__ uint32_t pairs_piece(uint32_t fit, uint32_t stage_refs)
+{
+  const uint32_t R = fit > PAIRS_STAGE_MAX ? PAIRS_STAGE_MAX : fit;
+  return stage_refs - 1u < R - 1u ? stage_refs : R;
+}
+
 /* (SINK_NEAREST: PairSink has no such form; hamming.hip and edit.hip each have a sink of their own behind its interface) */
 enum { SINK_CSR = 0, SINK_MATRIX = 1, SINK_LINK = 2, SINK_NEAREST = 3 };
 
 constexpr uint32_t HM_NONE = 0xffffffffu;      /* nearest sinks: the infinite distance, and "no sequence" */
+
+/* the end of a nearest sink: the lane's smallest distance `best` (HM_NONE: nobody), the sequence `number` of the first
+   reference at it and the references at it, to the three results (one segment) or the slot of (query, segment).  What
+   the walk left in number and ties while nobody was found is dropped */
+__device__ __forceinline__ void pairs_nearest_end(const PairNearest &N, uint32_t segments, uint32_t qorig, uint32_t seg,
+                                                  uint32_t best, uint32_t number, uint32_t ties)
+{
+  const bool none = best == HM_NONE;
+  const uint32_t id = none ? HM_NONE : number;
+  const uint32_t t = none ? 0u : ties;
+  if (segments == 1) {
+    if (N.nearest)
+      N.nearest[qorig] = id;
+    if (N.dist)
+      N.dist[qorig] = none ? (uint16_t)0xffffu : (uint16_t)best;
+    if (N.ties)
+      N.ties[qorig] = t;
+  } else {
+    const uint64_t slot = (uint64_t)qorig * segments + seg;
+    N.key[slot] = (unsigned long long)best << 32 | id;
+    N.slot_ties[slot] = t;
+  }
+}
 
 /* a pointer into LDS, typed as such: what is reached through it stays an LDS instruction, also where the code chooses
    between it and a pointer to global memory (the cells of the matrix sink) */

@@ -1,6 +1,7 @@
 /*
- * allpairs.hip -- the host side of allpairs.h: the refusals, a staged set grouped and packed, the segment count, and
- * the drivers around a caller's compare kernel -- the matrix, the neighbours as CSR, the clusters, and the nearest
+ * allpairs.hip -- the host side of allpairs.h: the refusals, a staged set grouped and packed, the segment count, what
+ * the job tables of edit.hip and tcrdist.hip are built from (the length limit, the query form, the lengths of a set),
+ * and the drivers around a caller's compare kernel -- the matrix, the neighbours as CSR, the clusters, and the nearest
  * neighbours.
  */
 #include "allpairs.h"
@@ -253,6 +254,50 @@ int cmpr::pairs_stage(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set
     if ((rc = stage(set2, W.own2))) return rc;
     W.s2 = &W.own2;
   }
+  return CMPR_OK;
+}
+
+std::function<int(const HmSet &)> cmpr::pairs_length_check(cmpr_context *c, const char *prefix)
+{
+  return [c, prefix](const HmSet &H) {
+    return H.longest > PAIRS_MAX_LEN
+        ? fail(c, CMPR_EUNSUPPORTED, std::string(prefix) + ": a sequence of more than 256 residues") : CMPR_OK;
+  };
+}
+
+uint32_t cmpr::pairs_form_of(uint32_t len, uint32_t stride)
+{
+  if (len > PAIRS_REG_RESIDUES)
+    return 0;
+  for (uint32_t f : {2u, 4u, 8u, 16u})
+    if (stride <= f)
+      return f;
+  return 0;
+}
+
+cmpr::PairLengths::PairLengths(const HmSet &S)
+{
+  for (size_t g = 0; g < S.groups.size(); g++)
+    if (len.empty() || len.back() != S.groups[g].len) {
+      len.push_back(S.groups[g].len);
+      first.push_back(g);
+    }
+}
+
+const HmGroup *cmpr::hm_group_of(const HmSet &S, uint64_t key)
+{
+  const auto k = std::lower_bound(S.keys.begin(), S.keys.end(), key);
+  return k != S.keys.end() && *k == key ? &S.groups[(size_t)(k - S.keys.begin())] : nullptr;
+}
+
+int cmpr::pairs_neighbors_args(cmpr_context *c, const std::string &who, uint64_t capacity, const uint32_t *hit_out,
+                               uint64_t *n_edges_out)
+{
+  if (!n_edges_out)
+    return fail(c, CMPR_EINVAL, who + ": n_edges_out is NULL");
+  *n_edges_out = 0;
+  if (capacity && !hit_out)
+    return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
   return CMPR_OK;
 }
 

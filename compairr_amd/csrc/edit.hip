@@ -8,10 +8,12 @@
  * is enumerated or hashed here: every query is compared with every sequence of every group it can match.
  *
  *   group    allpairs.h's: each set sorted by (length, V, J) with a stable radix sort, its residues packed in group
- *            order.  Sequences of more than ED_MAX_LEN = 256 residues are refused.
- *   jobs     on the host, from the two group tables: a set-1 group (L, V, J) and its PARTNERS, the set-2 groups
- *            (L', V, J) with |L - L'| <= d, found by binary search of the key for every length L' set 2 has (a huge d
- *            costs nothing).  The partners of a job are contiguous in one array.
+ *            order.  Sequences of more than PAIRS_MAX_LEN = 256 residues are refused.
+ *   jobs     allpairs.h's frame (PairJob, pairs_jobs: the table, the runs of one query form, the limits, the upload;
+ *            in the kernel PairWords, pairs_segment, pairs_piece), on the host, from the two group tables: a set-1
+ *            group (L, V, J) and its PARTNERS.  This file's own is the partner rule: the set-2 groups (L', V, J) with
+ *            |L - L'| <= d, found by binary search of the key for every length L' set 2 has (a huge d costs nothing).
+ *            The partners of a job are contiguous in one array.
  *   compare  ed_compare_kernel.  A workgroup of four waves takes four 64-query tiles of one job and one segment
  *            (grid y) of EVERY partner, one partner after the other.  Of the staged references the workgroup builds
  *            Peq[reference][symbol][w] in LDS, ED_PEQ_WORDS 64-bit words at a time: bit i of word w is set where the
@@ -25,7 +27,7 @@
  *            is masked), and the score is read at bit (n - 1) % 64 of word (n - 1) / 64, which is the same for all
  *            lanes.  An empty reference is at the query's length.
  *            The query's packed words sit in registers (NW = 2, 4, 8, 16 words, the residues peeled by loops
- *            unrolled at compile time under the uniform `pos < len`) while it has at most ED_REG_RESIDUES = 64
+ *            unrolled at compile time under the uniform `pos < len`) while it has at most PAIRS_REG_RESIDUES = 64
  *            residues: every CDR3 and junction of amino acids.  A longer query is read word by word from global
  *            memory (NW = 0: one load per four or sixteen column steps); unrolled, 256 steps of four column words
  *            would be straight-line code far beyond the instruction cache.  No instantiation indexes an array at
@@ -67,8 +69,6 @@ using namespace cmpr;
 
 namespace {
 
-constexpr uint32_t ED_MAX_LEN = 256;           /* residues of the longest sequence: four 64-bit column words */
-constexpr uint32_t ED_REG_RESIDUES = 64;       /* a query of more residues is read from global memory (NW = 0) */
 constexpr uint32_t ED_PEQ_WORDS = 2048;        /* 64-bit words of Peq staged at a time (16 KiB) */
 /* link sink: references of the longest automatic segment.  A sixteenth of hamming.hip's HM_LINK_SEGMENT, as a reference
    costs some twenty times as much here: 1M CDR3aa at d = 3, V/J matched (the largest group of 13 154), link kernel
@@ -85,17 +85,8 @@ struct EdPartner {
                                       cluster calls: the set against itself) */
 };
 
-/* a set-1 group and its partners */
-struct EdJob {
-  uint64_t pk1;                    /* first packed word of the group */
-  uint32_t q0, nq;                 /* positions in set 1's sorted order */
-  uint32_t len, stride;
-  uint32_t p0, np;                 /* its partners in the partner array */
-  uint32_t blk0, pad;              /* first workgroup (grid x) of the job */
-};
-
 struct EdParams {
-  const EdJob     *jobs;
+  const PairJob   *jobs;           /* a set-1 group and its partners (allpairs.h) */
   const EdPartner *partners;
   uint32_t        njobs, segments;
   const uint32_t *pk1, *pk2;       /* packed words */
@@ -171,23 +162,8 @@ struct EdSink<SINK_NEAREST> {
   __device__ __forceinline__ bool wants(bool active, uint32_t gap) const { return active && best >= gap; }
   __device__ __forceinline__ void end(bool active, uint32_t qorig, uint32_t seg) const
   {
-    if (!active)
-      return;
-    const bool none = best == HM_NONE;
-    const uint32_t id = none ? HM_NONE : bid;
-    const uint32_t t = none ? 0u : ties;
-    if (P.segments == 1) {
-      if (P.nn.nearest)
-        P.nn.nearest[qorig] = id;
-      if (P.nn.dist)
-        P.nn.dist[qorig] = none ? (uint16_t)0xffffu : (uint16_t)best;
-      if (P.nn.ties)
-        P.nn.ties[qorig] = t;
-    } else {
-      const uint64_t slot = (uint64_t)qorig * P.segments + seg;
-      P.nn.key[slot] = (unsigned long long)best << 32 | id;
-      P.nn.slot_ties[slot] = t;
-    }
+    if (active)
+      pairs_nearest_end(P.nn, P.segments, qorig, seg, best, bid, ties);
   }
 };
 
@@ -240,9 +216,9 @@ ed_compare_kernel(const EdParams P)
   __shared__ uint32_t st_root[SINK == SINK_LINK ? PAIRS_STAGE_MAX : 1];
 
   const uint32_t blk = P.blk_base + blockIdx.x;
-  const EdJob jb = pairs_entry_of(P.jobs, P.njobs, blk);
+  const PairJob jb = pairs_entry_of(P.jobs, P.njobs, blk);
   const PairQuery Q(jb, blk, P.ord1);
-  const uint32_t qi = Q.qi, qpos = Q.qpos, qorig = Q.qorig;
+  const uint32_t qi = Q.qi, qorig = Q.qorig;
   const bool active = Q.active();
   const uint32_t qlen = jb.len;
   const uint32_t seg = blockIdx.y;
@@ -255,13 +231,9 @@ ed_compare_kernel(const EdParams P)
   EdSink<SINK> S(P, PairLds(st_id, st_rep, st_cnt, st_mat), st_root);
   S.zero_matrix();                                                      /* (a barrier follows before the first match) */
 
-  const uint32_t *const qw = P.pk1 + jb.pk1 + (uint64_t)(qpos - jb.q0) * jb.stride;
-  uint32_t q[NW ? NW : 1];
-  if (NW) {
-#pragma unroll
-    for (int k = 0; k < NW; k++)
-      q[k] = (uint32_t)k < jb.stride ? qw[k] : 0u;
-  }
+  const PairWords<NW> QW(P.pk1, jb, Q, jb.stride);
+  const uint32_t *const qw = QW.w;
+  const uint32_t (&q)[NW ? NW : 1] = QW.q;
 
   S.init(qorig, seg);
 
@@ -271,9 +243,7 @@ ed_compare_kernel(const EdParams P)
     const bool own = SINK == SINK_LINK && pt.own;
     const uint32_t n = pt.len;
     const uint32_t sw = n ? (n - 1) >> 6 : 0u, sb = n ? (n - 1) & 63u : 0u;
-    uint32_t R = ED_PEQ_WORDS / (A * W);
-    if (R > PAIRS_STAGE_MAX) R = PAIRS_STAGE_MAX;
-    if (P.stage_refs && P.stage_refs < R) R = P.stage_refs;
+    const uint32_t R = pairs_piece(ED_PEQ_WORDS / (A * W), P.stage_refs);
     for (uint32_t e = e0; e < e1; e += R) {
       const uint32_t cnt = e1 - e < R ? e1 - e : R;
       __syncthreads();                                                  /* the previous piece has been read */
@@ -350,8 +320,8 @@ ed_compare_kernel(const EdParams P)
     /* (the own group: the workgroup whose first query sits at position b walks the references behind b only, and its
        segments divide THAT range) */
     const uint32_t w0 = SINK == SINK_LINK && pt.own ? min(wg_q0 + 1u, pt.nr) : 0u;
-    const uint32_t e0 = w0 + (uint32_t)((uint64_t)(pt.nr - w0) * seg / P.segments);
-    const uint32_t e1 = w0 + (uint32_t)((uint64_t)(pt.nr - w0) * (seg + 1) / P.segments);
+    uint32_t e0, e1;
+    pairs_segment(pt.nr, w0, seg, P.segments, e0, e1);
     if (e0 >= e1)
       continue;                                                         /* (the whole workgroup) */
     uint32_t words = pt.len <= 64 ? 1u : pt.len <= 128 ? 2u : 4u;
@@ -368,17 +338,6 @@ ed_compare_kernel(const EdParams P)
 }
 
 typedef void (*EdKernel)(const EdParams);
-
-/* the register form of a query of `len` residues in `stride` packed words: 2, 4, 8, 16, or 0 */
-uint32_t ed_form_of(uint32_t len, uint32_t stride)
-{
-  if (len > ED_REG_RESIDUES)
-    return 0;
-  for (uint32_t f : {2u, 4u, 8u, 16u})
-    if (stride <= f)
-      return f;
-  return 0;
-}
 
 template <int SINK>
 EdKernel ed_kernel_for(uint32_t nw, bool nt)
@@ -399,12 +358,9 @@ EdKernel ed_kernel_for(uint32_t nw, bool nt)
   }
 }
 
-/* what the entry points share: both sets on the device, the jobs */
-struct EdWork : PairSets {
-  Tmp<EdJob>     jobs;
-  Tmp<EdPartner> partners;
+/* what the entry points share: both sets on the device, the jobs (allpairs.h) */
+struct EdWork : PairJobs<EdPartner> {
   EdParams       P{};
-  PairRuns       runs;             /* form: ed_form_of */
 };
 
 /* the order of a job's partners.  ED_BY_LENGTH: by increasing length.  ED_TRIANGULAR (the cluster calls, set2 == set1):
@@ -418,72 +374,32 @@ int ed_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
 {
   const bool triangular = order == ED_TRIANGULAR;
   int rc;
-  if ((rc = pairs_stage(c, set1, set2, on_device, J, hm_key_mode(c), [&](const HmSet &H) {
-         return H.longest > ED_MAX_LEN ? fail(c, CMPR_EUNSUPPORTED, "cmpr_edit: a sequence of more than 256 residues")
-                                       : CMPR_OK;
+  if ((rc = pairs_stage(c, set1, set2, on_device, J, hm_key_mode(c), pairs_length_check(c, "cmpr_edit"))))
+    return rc;
+  const HmSet &B = *J.s2;
+  const uint64_t longest = std::max(J.s1->longest, B.longest);
+  const uint32_t d = (uint32_t)std::min<uint64_t>((uint64_t)differences, longest);   /* above the longest sequence: as that length */
+  EdParams &P = J.P;
+
+  /* per set-1 group the set-2 groups of its V and J at the lengths within d, by binary search of their key */
+  if ((rc = pairs_jobs(c, who, J, P, [&](const HmGroup &ga, uint64_t genes_of, const PairLengths &L2,
+                                         std::vector<EdPartner> &partners) {
+         const size_t p0 = partners.size();
+         const uint32_t first = triangular ? ga.len : ga.len > d ? ga.len - d : 0u;
+         for (auto it = std::lower_bound(L2.len.begin(), L2.len.end(), first);
+              it != L2.len.end() && *it <= ga.len + d; ++it)
+           if (const HmGroup *gb = hm_group_of(B, (uint64_t)*it * B.per_len + genes_of))
+             partners.push_back(EdPartner{gb->pk_off, gb->start, gb->count, gb->len, (uint16_t)gb->stride,
+                                          (uint16_t)(triangular && gb->len == ga.len ? 1u : 0u)});
+         const auto gap = [&](const EdPartner &x) { return x.len > ga.len ? x.len - ga.len : ga.len - x.len; };
+         if (order == ED_BY_GAP)
+           std::stable_sort(partners.begin() + (ptrdiff_t)p0, partners.end(),
+                            [&](const EdPartner &x, const EdPartner &y) { return gap(x) < gap(y); });
        })))
     return rc;
-  HmSet &A = *J.s1, &B = *J.s2;
-  const uint64_t longest = std::max(A.longest, B.longest);
-  const uint32_t d = (uint32_t)std::min<uint64_t>((uint64_t)differences, longest);   /* above the longest sequence: as that length */
-
-  /* the lengths set 2 has (the keys increase with the length); per set-1 group the set-2 groups of its V and J at
-     the lengths within d, by binary search of their key */
-  const bool genes = !c->opt.ignore_genes;
-  const uint64_t vj = genes ? (uint64_t)std::max<uint32_t>(1, c->opt.n_v_genes) * std::max<uint32_t>(1, c->opt.n_j_genes) : 1;
-  std::vector<uint32_t> lens2;
-  for (const HmGroup &g : B.groups)
-    if (lens2.empty() || lens2.back() != g.len)
-      lens2.push_back(g.len);
-  std::vector<EdJob> jobs;
-  std::vector<EdPartner> partners;
-  uint64_t blocks = 0;
-  uint32_t nr_max = 0;
-  for (size_t a = 0; a < A.groups.size(); a++) {
-    const HmGroup &ga = A.groups[a];
-    const uint64_t genes_of = A.keys[a] % vj;
-    const uint32_t first = triangular ? ga.len : ga.len > d ? ga.len - d : 0u;
-    const size_t p0 = partners.size();
-    for (auto it = std::lower_bound(lens2.begin(), lens2.end(), first); it != lens2.end() && *it <= ga.len + d; ++it) {
-      const uint64_t key = (uint64_t)*it * vj + genes_of;
-      const auto k = std::lower_bound(B.keys.begin(), B.keys.end(), key);
-      if (k == B.keys.end() || *k != key)
-        continue;
-      const HmGroup &gb = B.groups[(size_t)(k - B.keys.begin())];
-      partners.push_back(EdPartner{gb.pk_off, gb.start, gb.count, gb.len, (uint16_t)gb.stride,
-                                   (uint16_t)(triangular && gb.len == ga.len ? 1u : 0u)});
-      nr_max = std::max(nr_max, gb.count);
-    }
-    if (partners.size() == p0)
-      continue;
-    if (order == ED_BY_GAP)
-      std::stable_sort(partners.begin() + (ptrdiff_t)p0, partners.end(), [&](const EdPartner &x, const EdPartner &y) {
-        return (x.len > ga.len ? x.len - ga.len : ga.len - x.len) < (y.len > ga.len ? y.len - ga.len : ga.len - y.len);
-      });
-    const uint32_t nb = blocks_for(ga.count, PAIRS_WG);
-    J.runs.add(ed_form_of(ga.len, ga.stride), (uint32_t)blocks, nb);
-    jobs.push_back(EdJob{ga.pk_off, ga.start, ga.count, ga.len, ga.stride, (uint32_t)p0,
-                         (uint32_t)(partners.size() - p0), (uint32_t)blocks, 0u});
-    blocks += nb;
-    if (blocks > 0xffffffu)
-      return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^24 workgroups of queries");
-  }
-  if (partners.size() > 0xffffffffull)
-    return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^32-1 pairs of groups");
-  if (!jobs.empty()) {
-    if ((rc = dev_upload(c, J.jobs.b, jobs.data(), jobs.size()))) return rc;
-    if ((rc = dev_upload(c, J.partners.b, partners.data(), partners.size()))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));           /* (the two vectors leave scope) */
-  }
-  EdParams &P = J.P;
-  P.jobs = J.jobs.b.p;
-  P.partners = J.partners.b.p;
-  P.njobs = (uint32_t)jobs.size();
   /* (the link sink's workgroups walk what lies behind them in their own group: as hm_setup, no segment longer than
      ED_LINK_SEGMENT references) */
-  P.segments = pairs_segments(c, c->edit_segments, blocks, nr_max, triangular ? ED_LINK_SEGMENT : 0u);
-  P.pk1 = A.pk.b.p; P.pk2 = B.pk.b.p;
-  P.ord1 = A.ord.b.p; P.ord2 = B.ord.b.p;
+  P.segments = pairs_segments(c, c->edit_segments, J.blocks, J.nr_max, triangular ? ED_LINK_SEGMENT : 0u);
   P.d = d;
   P.stage_refs = (uint32_t)c->edit_stage_refs;
   P.min_words = (uint32_t)c->edit_words;
@@ -509,13 +425,10 @@ int edit_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set_
     return rc;
   if (!matrix_out)
     return fail(c, CMPR_EINVAL, who + ": matrix_out is NULL");
-  auto t0 = std::chrono::steady_clock::now();
-  for (double &t : c->ed_ms)
-    t = 0;
   EdWork J;
-  if ((rc = ed_setup(c, who, set1, set2, differences, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->ed_ms, false,
+                              [&] { return ed_setup(c, who, set1, set2, differences, on_device, J); })))
     return rc;
-  c->ed_ms[0] = ms_since(t0);
   return pairs_matrix(c, J, J.P.sink, matrix_out, on_device, [&] { return ed_launch<SINK_MATRIX>(c, J); }, c->ed_ms, 3);
 }
 
@@ -526,21 +439,14 @@ int edit_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
   if (!c)
     return CMPR_EINVAL;
   const std::string who = "cmpr_edit_neighbors";
-  if (!n_edges_out)
-    return fail(c, CMPR_EINVAL, who + ": n_edges_out is NULL");
-  *n_edges_out = 0;
-  if (capacity && !hit_out)
-    return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
   int rc;
-  if ((rc = hm_refusals(c, who, set1, set2, differences, HM_NEIGHBORS, on_device, true)))
+  if ((rc = pairs_neighbors_args(c, who, capacity, hit_out, n_edges_out)) ||
+      (rc = hm_refusals(c, who, set1, set2, differences, HM_NEIGHBORS, on_device, true)))
     return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  for (double &t : c->ed_ms)
-    t = 0;
   EdWork J;
-  if ((rc = ed_setup(c, who, set1, set2, differences, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->ed_ms, false,
+                              [&] { return ed_setup(c, who, set1, set2, differences, on_device, J); })))
     return rc;
-  c->ed_ms[0] = ms_since(t0);
   /* the rows always (the row order reads them); the row order into ed_ms[2] */
   return pairs_neighbors(c, who, J, J.P.segments, J.P.sink, capacity, row_start_out, hit_out, dist_out, n_edges_out,
                          on_device, [&] { return ed_launch<SINK_CSR>(c, J); }, true, c->ed_ms, 2, 3);
@@ -560,15 +466,10 @@ int edit_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t differe
   int rc;
   if ((rc = hm_refusals(c, who, set, set, differences, HM_CLUSTERS, on_device, true)))
     return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  for (double &t : c->ed_ms)
-    t = 0;
-  if (T)
-    c->cl_ms[0] = c->cl_ms[1] = 0;
   EdWork J;
-  if ((rc = ed_setup(c, who, set, set, differences, on_device, J, ED_TRIANGULAR)))
+  if ((rc = pairs_timed_setup(c, c->ed_ms, T != nullptr,
+                              [&] { return ed_setup(c, who, set, set, differences, on_device, J, ED_TRIANGULAR); })))
     return rc;
-  c->ed_ms[0] = ms_since(t0);
   return pairs_clusters(c, *J.s1, c->edit_link_snapshot != 0, on_device, L, T, n_clusters_out,
                         [&](const PairLinks &K) {
                           J.P.link = K;
@@ -599,13 +500,10 @@ int edit_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_set
   if (other_rep && set2 != set1)
     return fail(c, CMPR_EINVAL, who + ": CMPR_NEAREST_OTHER_REPERTOIRE needs set2 == set1 (two sets have two numberings "
                                       "of their repertoires)");
-  auto t0 = std::chrono::steady_clock::now();
-  for (double &t : c->ed_ms)
-    t = 0;
   EdWork J;
-  if ((rc = ed_setup(c, who, set1, set2, max_distance, on_device, J, ED_BY_GAP)))
+  if ((rc = pairs_timed_setup(c, c->ed_ms, false,
+                              [&] { return ed_setup(c, who, set1, set2, max_distance, on_device, J, ED_BY_GAP); })))
     return rc;
-  c->ed_ms[0] = ms_since(t0);
   EdParams &P = J.P;
   P.sink.rep1 = J.s1->rep.b.p; P.sink.rep2 = J.s2->rep.b.p;
   P.floor = (uint32_t)std::min<int64_t>(min_distance, 0x10000);        /* (no distance is above 256) */

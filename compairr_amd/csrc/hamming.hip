@@ -69,11 +69,7 @@ struct HmParams {
   uint32_t        floor;           /* a candidate differs at this many positions or more */
   uint32_t        one_set;         /* 1: set 2 IS set 1, a query is no candidate of its own */
   uint32_t        other_rep;       /* 1: a candidate comes from another repertoire than the query */
-  uint32_t       *nn_nearest;      /* one segment: the three results, each may be NULL */
-  uint16_t       *nn_dist;
-  uint32_t       *nn_ties;
-  unsigned long long *nn_key;      /* several: [n1 x segments] (distance << 32 | number), all ones: none */
-  uint32_t       *nn_slot_ties;    /* ... and the references of the segment at that distance */
+  PairNearest     nn;              /* where the results or the (query, segment) slots go (allpairs.h) */
 };
 
 /* differing residues of two packed words.  Amino acids: a byte each, codes below 0x80, so neither the xor nor the
@@ -139,23 +135,8 @@ struct HmSink<SINK_NEAREST> {
   }
   __device__ __forceinline__ void end(bool active, uint32_t qorig, uint32_t seg) const
   {
-    if (!active)
-      return;
-    const bool none = best == HM_NONE;
-    const uint32_t id = none ? HM_NONE : ord2[bpos];
-    const uint32_t t = none ? 0u : ties;
-    if (P.segments == 1) {
-      if (P.nn_nearest)
-        P.nn_nearest[qorig] = id;
-      if (P.nn_dist)
-        P.nn_dist[qorig] = none ? (uint16_t)0xffffu : (uint16_t)best;
-      if (P.nn_ties)
-        P.nn_ties[qorig] = t;
-    } else {
-      const uint64_t slot = (uint64_t)qorig * P.segments + seg;
-      P.nn_key[slot] = (unsigned long long)best << 32 | id;
-      P.nn_slot_ties[slot] = t;
-    }
+    if (active)                                                         /* (bpos is 0 while nobody was found) */
+      pairs_nearest_end(P.nn, P.segments, qorig, seg, best, ord2[bpos], ties);
   }
 };
 
@@ -175,15 +156,15 @@ hm_compare_kernel(const HmParams P)
   const HmPair pr = pairs_entry_of(P.pairs, P.npairs, blk);
   const uint32_t stride = NW ? (uint32_t)NW : pr.stride;
   const PairQuery Q(pr, blk, P.ord1);
-  const uint32_t qi = Q.qi, qpos = Q.qpos, qorig = Q.qorig;
+  const uint32_t qi = Q.qi, qorig = Q.qorig;
   const bool active = Q.active();
   /* the segment of the set-2 group.  Link sink: set 2 IS set 1 and position order is number order (the stable
      sort), so an unordered pair is walked once, by the lane of its smaller position: the workgroup whose first
      query sits at position b walks the references behind b only, and its segments divide THAT range. */
   const uint32_t seg = blockIdx.y;
   const uint32_t w0 = SINK == SINK_LINK ? min((blk - pr.blk0) * PAIRS_WG + 1u, pr.nr) : 0u;
-  const uint32_t e0 = w0 + (uint32_t)((uint64_t)(pr.nr - w0) * seg / P.segments);
-  const uint32_t e1 = w0 + (uint32_t)((uint64_t)(pr.nr - w0) * (seg + 1) / P.segments);
+  uint32_t e0, e1;
+  pairs_segment(pr.nr, w0, seg, P.segments, e0, e1);
   /* ... and a wave skips the staged references at or below its first query: no lane of it wants them */
   const uint32_t wave_q0 = SINK == SINK_LINK
       ? (uint32_t)__builtin_amdgcn_readfirstlane((int)((blk - pr.blk0) * PAIRS_WG + (threadIdx.x & ~(WAVE - 1u)))) : 0u;
@@ -193,13 +174,9 @@ hm_compare_kernel(const HmParams P)
   HmSink<SINK> S(P, pr, qi, PairLds(st_id, st_rep, st_cnt, st_mat), st_root);
   S.zero_matrix();                                                      /* (a barrier follows before the first match) */
 
-  const uint32_t *const qw = P.pk1 + pr.pk1 + (uint64_t)(qpos - pr.q0) * stride;
-  uint32_t q[NW ? NW : 1];
-  if (NW) {
-#pragma unroll
-    for (int k = 0; k < NW; k++)
-      q[k] = qw[k];
-  }
+  const PairWords<NW> QW(P.pk1, pr, Q, stride);                        /* (register form: the stride IS NW) */
+  const uint32_t *const qw = QW.w;
+  const uint32_t (&q)[NW ? NW : 1] = QW.q;
 
   S.init(qorig, seg);
   /* sequence numbers, repertoires and counts of the references e .. e + n - 1 of the group */
@@ -218,9 +195,7 @@ hm_compare_kernel(const HmParams P)
 
   if (stride <= HM_LDS_WORDS) {
     /* whole references, R at a time */
-    uint32_t R = HM_LDS_WORDS / stride;
-    if (R > PAIRS_STAGE_MAX) R = PAIRS_STAGE_MAX;
-    if (P.stage_refs && P.stage_refs < R) R = P.stage_refs;
+    const uint32_t R = pairs_piece(HM_LDS_WORDS / stride, P.stage_refs);
     for (uint32_t e = e0; e < e1; e += R) {
       const uint32_t n = e1 - e < R ? e1 - e : R;
       __syncthreads();                                                  /* the previous piece has been read */
@@ -365,12 +340,10 @@ int hamming_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
     return rc;
   if (!matrix_out)
     return fail(c, CMPR_EINVAL, who + ": matrix_out is NULL");
-  auto t0 = std::chrono::steady_clock::now();
-  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
   HmJob J;
-  if ((rc = hm_setup(c, who, set1, set2, differences, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->hm_ms, false,
+                              [&] { return hm_setup(c, who, set1, set2, differences, on_device, J); })))
     return rc;
-  c->hm_ms[0] = ms_since(t0);
   return pairs_matrix(c, J, J.P.sink, matrix_out, on_device, [&] { return hm_launch<SINK_MATRIX>(c, J); }, c->hm_ms, 2);
 }
 
@@ -381,20 +354,14 @@ int hamming_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   if (!c)
     return CMPR_EINVAL;
   const std::string who = "cmpr_hamming_neighbors";
-  if (!n_edges_out)
-    return fail(c, CMPR_EINVAL, who + ": n_edges_out is NULL");
-  *n_edges_out = 0;
-  if (capacity && !hit_out)
-    return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
   int rc;
-  if ((rc = hm_refusals(c, who, set1, set2, differences, HM_NEIGHBORS, on_device)))
+  if ((rc = pairs_neighbors_args(c, who, capacity, hit_out, n_edges_out)) ||
+      (rc = hm_refusals(c, who, set1, set2, differences, HM_NEIGHBORS, on_device)))
     return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
   HmJob J;
-  if ((rc = hm_setup(c, who, set1, set2, differences, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->hm_ms, false,
+                              [&] { return hm_setup(c, who, set1, set2, differences, on_device, J); })))
     return rc;
-  c->hm_ms[0] = ms_since(t0);
   /* rows only when asked for, and in order as the walk leaves them: no row order step */
   return pairs_neighbors(c, who, J, J.P.segments, J.P.sink, capacity, row_start_out, hit_out, dist_out, n_edges_out,
                          on_device, [&] { return hm_launch<SINK_CSR>(c, J); }, false, c->hm_ms, -1, 2);
@@ -420,12 +387,9 @@ int hamming_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_
   if (other_rep && set2 != set1)
     return fail(c, CMPR_EINVAL, who + ": CMPR_NEAREST_OTHER_REPERTOIRE needs set2 == set1 (two sets have two numberings "
                                       "of their repertoires)");
-  auto t0 = std::chrono::steady_clock::now();
-  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
   HmJob J;
-  if ((rc = hm_setup(c, who, set1, set2, 0, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->hm_ms, false, [&] { return hm_setup(c, who, set1, set2, 0, on_device, J); })))
     return rc;
-  c->hm_ms[0] = ms_since(t0);
   HmParams &P = J.P;
   P.sink.rep1 = J.s1->rep.b.p; P.sink.rep2 = J.s2->rep.b.p;
   P.floor = (uint32_t)std::min<int64_t>(min_distance, 0x10000);        /* (no distance is above 65535) */
@@ -433,8 +397,7 @@ int hamming_nearest_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_
   P.other_rep = other_rep ? 1u : 0u;
   return pairs_nearest(c, J, P.segments, nearest_out, dist_out, ties_out, n_found_out, on_device,
                        [&](const PairNearest &N) {
-                         P.nn_nearest = N.nearest; P.nn_dist = N.dist; P.nn_ties = N.ties;
-                         P.nn_key = N.key; P.nn_slot_ties = N.slot_ties;
+                         P.nn = N;
                          return hm_launch<SINK_NEAREST>(c, J);
                        },
                        c->hm_ms, 2);
@@ -455,14 +418,10 @@ int hamming_cluster_impl(cmpr_context *c, const cmpr_set_view *set, int64_t diff
   int rc;
   if ((rc = hm_refusals(c, who, set, set, differences, HM_CLUSTERS, on_device)))
     return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  c->hm_ms[0] = c->hm_ms[1] = c->hm_ms[2] = 0;
-  if (table)
-    c->cl_ms[0] = c->cl_ms[1] = 0;
   HmJob J;
-  if ((rc = hm_setup(c, who, set, set, differences, on_device, J, true)))
+  if ((rc = pairs_timed_setup(c, c->hm_ms, table,
+                              [&] { return hm_setup(c, who, set, set, differences, on_device, J, true); })))
     return rc;
-  c->hm_ms[0] = ms_since(t0);
   return pairs_clusters(c, *J.s1, c->hamming_link_snapshot != 0, on_device, L, T, n_clusters_out,
                         [&](const PairLinks &K) {
                           J.P.link = K;

@@ -7,8 +7,9 @@
  *
  *   group    allpairs.h's: each set sorted by (length, V, J) -- the length alone with ignore_genes, (length, V) with a
  *            V table: any two V genes pair at the table's price and the J gene plays no part --, its residues packed a
- *            byte each in group order.  Sequences of more than TD_MAX_LEN = 256 residues are refused, as for edit.
- *   jobs     on the host, as edit.hip's: a set-1 group and its PARTNERS, the set-2 groups whose
+ *            byte each in group order.  Sequences of more than PAIRS_MAX_LEN = 256 residues are refused, as for edit.
+ *   jobs     allpairs.h's frame, the one edit.hip walks (PairJob, pairs_jobs; in the kernel PairWords, pairs_segment,
+ *            pairs_piece); this file's own is the partner rule: a set-1 group's PARTNERS are the set-2 groups whose
  *            base = |L - L'| x gap_penalty + V[v1][v2] (64 bits; the V term 0 without a table) is at most the cutoff:
  *            with a positive penalty that bounds the lengths, with 0 every length is a partner; with a table a partner
  *            can be any V at an admitted length.  Everything the alignment of a (job, partner) needs is uniform and
@@ -16,7 +17,7 @@
  *            sequence that pay W at the same position of the longer one (`diag`: [d0, d1)) and at position k + delta
  *            (`shift`: [s0, s1)), and the zone [lo, hi) of the gap positions SLIDING tries.  The kernel never touches
  *            genes.
- *   compare  td_compare_kernel, in the frame of ed_compare_kernel: a workgroup of four waves takes four 64-query tiles
+ *   compare  td_compare_kernel: a workgroup of four waves takes four 64-query tiles
  *            of one job and one segment (grid y) of EVERY partner, one partner after the other; the references are
  *            staged as they are packed, TD_STAGE_WORDS words at a time.  W lies in LDS TRANSPOSED, a row of TD_WT_ROW =
  *            32 bytes per REFERENCE residue: every lane of a wave meets the same reference residue at the same step
@@ -25,8 +26,8 @@
  *            hold.  The operand order never swaps: the cost is W[set-1 residue][set-2 residue] = Wt[reference][query],
  *            whichever of the two is shorter; only the positions that meet change.
  *            The query's packed words sit in registers (NW = 2, 4, 8, 16 words, the residues peeled by loops unrolled
- *            at compile time) while it has at most TD_REG_RESIDUES = 64 residues.  The loop runs over the positions k
- *            of the shorter sequence; a query that is the LONGER one meets the reference's position k with its own
+ *            at compile time) while it has at most PAIRS_REG_RESIDUES = 64 residues.  The loop runs over the positions
+ *            k of the shorter sequence; a query that is the LONGER one meets the reference's position k with its own
  *            positions k and k + delta, so per partner a second copy of its words is shifted down by delta residues --
  *            a logarithmic shifter over the words, each stage under a uniform condition, then a funnel shift of the
  *            bytes: compile-time register numbers only.  Which positions pay what is three uniform 64-bit masks per
@@ -52,8 +53,6 @@ using namespace cmpr;
 
 namespace {
 
-constexpr uint32_t TD_MAX_LEN = 256;           /* residues of the longest sequence */
-constexpr uint32_t TD_REG_RESIDUES = 64;       /* a query of more residues is read from global memory (NW = 0) */
 constexpr uint32_t TD_STAGE_WORDS = 4096;      /* packed words of references staged at a time (16 KiB) */
 constexpr uint32_t TD_ALPHABET = 20;
 constexpr uint32_t TD_WT_ROW = 32;             /* bytes of a row of the transposed table: 20 costs and the padding */
@@ -73,17 +72,8 @@ struct TdPartner {
   uint32_t pad[2];
 };
 
-/* a set-1 group and its partners */
-struct TdJob {
-  uint64_t pk1;                    /* first packed word of the group */
-  uint32_t q0, nq;                 /* positions in set 1's sorted order */
-  uint32_t len, stride;
-  uint32_t p0, np;                 /* its partners in the partner array */
-  uint32_t blk0, pad;              /* first workgroup (grid x) of the job */
-};
-
 struct TdParams {
-  const TdJob     *jobs;
+  const PairJob   *jobs;           /* a set-1 group and its partners (allpairs.h) */
   const TdPartner *partners;
   uint32_t        njobs, segments;
   const uint32_t *pk1, *pk2;       /* packed words */
@@ -115,9 +105,9 @@ td_compare_kernel(const TdParams P)
   __shared__ unsigned long long st_mat[SINK == SINK_MATRIX ? PAIRS_MAT_CELLS : 1];
 
   const uint32_t blk = P.blk_base + blockIdx.x;
-  const TdJob jb = pairs_entry_of(P.jobs, P.njobs, blk);
+  const PairJob jb = pairs_entry_of(P.jobs, P.njobs, blk);
   const PairQuery Q(jb, blk, P.ord1);
-  const uint32_t qpos = Q.qpos, qorig = Q.qorig;
+  const uint32_t qorig = Q.qorig;
   const bool active = Q.active();
   const uint32_t seg = blockIdx.y;
 
@@ -128,20 +118,16 @@ td_compare_kernel(const TdParams P)
   const Lds<uint8_t> wt = (Lds<uint8_t>)st_wt;
   const Lds<uint32_t> refs = (Lds<uint32_t>)st_ref;
 
-  const uint32_t *const qw = P.pk1 + jb.pk1 + (uint64_t)(qpos - jb.q0) * jb.stride;
-  uint32_t q[NW ? NW : 1];
-  if (NW) {
-#pragma unroll
-    for (int k = 0; k < NW; k++)
-      q[k] = (uint32_t)k < jb.stride ? qw[k] : 0u;
-  }
+  const PairWords<NW> QW(P.pk1, jb, Q, jb.stride);
+  const uint32_t *const qw = QW.w;
+  const uint32_t (&q)[NW ? NW : 1] = QW.q;
 
   S.init(qorig, seg);
 
   for (uint32_t p = jb.p0; p < jb.p0 + jb.np; p++) {
     const TdPartner pt = P.partners[p];
-    const uint32_t e0 = (uint32_t)((uint64_t)pt.nr * seg / P.segments);
-    const uint32_t e1 = (uint32_t)((uint64_t)pt.nr * (seg + 1) / P.segments);
+    uint32_t e0, e1;
+    pairs_segment(pt.nr, 0u, seg, P.segments, e0, e1);
     if (e0 >= e1)
       continue;                                                         /* (the whole workgroup) */
     const uint32_t stride = pt.stride;
@@ -170,9 +156,7 @@ td_compare_kernel(const TdParams P)
     }
     const unsigned long long mD = td_mask(pt.d0, pt.d1), mS = td_mask(pt.s0, pt.s1), mZ = td_mask(pt.lo, pt.hi);
 
-    uint32_t R = TD_STAGE_WORDS / stride;
-    if (R > PAIRS_STAGE_MAX) R = PAIRS_STAGE_MAX;
-    if (P.stage_refs && P.stage_refs < R) R = P.stage_refs;
+    const uint32_t R = pairs_piece(TD_STAGE_WORDS / stride, P.stage_refs);
     for (uint32_t e = e0; e < e1; e += R) {
       const uint32_t cnt = e1 - e < R ? e1 - e : R;
       __syncthreads();                                                  /* the previous piece has been read */
@@ -237,17 +221,6 @@ td_compare_kernel(const TdParams P)
 
 typedef void (*TdKernel)(const TdParams);
 
-/* the register form of a query of `len` residues in `stride` packed words: 2, 4, 8, 16, or 0 */
-uint32_t td_form_of(uint32_t len, uint32_t stride)
-{
-  if (len > TD_REG_RESIDUES)
-    return 0;
-  for (uint32_t f : {2u, 4u, 8u, 16u})
-    if (stride <= f)
-      return f;
-  return 0;
-}
-
 template <int SINK>
 TdKernel td_kernel_for(uint32_t nw)
 {
@@ -260,13 +233,10 @@ TdKernel td_kernel_for(uint32_t nw)
   }
 }
 
-/* what the entry points share: both sets on the device, the jobs, the table */
-struct TdWork : PairSets {
-  Tmp<TdJob>     jobs;
-  Tmp<TdPartner> partners;
+/* what the entry points share: both sets on the device, the jobs (allpairs.h), the table */
+struct TdWork : PairJobs<TdPartner> {
   Tmp<uint32_t>  wt;
   TdParams       P{};
-  PairRuns       runs;             /* form: td_form_of */
 };
 
 /* the alignment of a query of L residues with references of L2: the fields of the partner record behind `base` */
@@ -298,69 +268,41 @@ int td_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
 {
   const bool table = T.v_distance != nullptr;
   int rc;
-  if ((rc = pairs_stage(c, set1, set2, on_device, J, table ? HM_KEY_LENGTH_V : hm_key_mode(c), [&](const HmSet &H) {
-         return H.longest > TD_MAX_LEN ? fail(c, CMPR_EUNSUPPORTED, "cmpr_tcrdist: a sequence of more than 256 residues")
-                                       : CMPR_OK;
+  if ((rc = pairs_stage(c, set1, set2, on_device, J, table ? HM_KEY_LENGTH_V : hm_key_mode(c),
+                        pairs_length_check(c, "cmpr_tcrdist"))))
+    return rc;
+  const HmSet &B = *J.s2;
+  TdParams &P = J.P;
+
+  /* per set-1 group the set-2 groups whose base is within the cutoff: of its V and J by binary search of their key,
+     or with a table every V */
+  const uint64_t per = B.per_len, n_v = std::max<uint32_t>(1, c->opt.n_v_genes);
+  if ((rc = pairs_jobs(c, who, J, P, [&](const HmGroup &ga, uint64_t genes_of, const PairLengths &L2,
+                                         std::vector<TdPartner> &partners) {
+         for (size_t x = 0; x < L2.len.size(); x++) {
+           const uint32_t len2 = L2.len[x];
+           const uint64_t gap = (uint64_t)(ga.len > len2 ? ga.len - len2 : len2 - ga.len) * T.gap_penalty;
+           if (gap > (uint64_t)cutoff)
+             continue;
+           TdPartner pt{};
+           td_align(T, ga.len, len2, pt);
+           const auto add = [&](const HmGroup &gb, uint64_t base) {
+             pt.pk_off = gb.pk_off; pt.r0 = gb.start; pt.nr = gb.count; pt.stride = gb.stride;
+             pt.base = (uint32_t)base;
+             partners.push_back(pt);
+           };
+           if (table) {
+             for (size_t b = L2.first[x]; b < B.groups.size() && B.groups[b].len == len2; b++) {
+               const uint64_t base = gap + T.v_distance[genes_of * n_v + B.keys[b] % per];
+               if (base <= (uint64_t)cutoff)
+                 add(B.groups[b], base);
+             }
+           } else if (const HmGroup *gb = hm_group_of(B, (uint64_t)len2 * per + genes_of)) {
+             add(*gb, gap);
+           }
+         }
        })))
     return rc;
-  HmSet &A = *J.s1, &B = *J.s2;
-
-  /* the lengths set 2 has and the first group of each (the keys increase with the length); per set-1 group the set-2
-     groups whose base is within the cutoff: of its V and J by binary search of their key, or with a table every V */
-  const uint64_t per = std::max<uint64_t>(1, A.per_len), n_v = std::max<uint32_t>(1, c->opt.n_v_genes);
-  std::vector<uint32_t> lens2;
-  std::vector<size_t> first2;
-  for (size_t b = 0; b < B.groups.size(); b++)
-    if (lens2.empty() || lens2.back() != B.groups[b].len) {
-      lens2.push_back(B.groups[b].len);
-      first2.push_back(b);
-    }
-  std::vector<TdJob> jobs;
-  std::vector<TdPartner> partners;
-  uint64_t blocks = 0;
-  uint32_t nr_max = 0;
-  for (size_t a = 0; a < A.groups.size(); a++) {
-    const HmGroup &ga = A.groups[a];
-    const uint64_t genes_of = A.keys[a] % per;
-    const size_t p0 = partners.size();
-    for (size_t x = 0; x < lens2.size(); x++) {
-      const uint32_t L2 = lens2[x];
-      const uint64_t gap = (uint64_t)(ga.len > L2 ? ga.len - L2 : L2 - ga.len) * T.gap_penalty;
-      if (gap > (uint64_t)cutoff)
-        continue;
-      TdPartner pt{};
-      td_align(T, ga.len, L2, pt);
-      const auto add = [&](const HmGroup &gb, uint64_t base) {
-        pt.pk_off = gb.pk_off; pt.r0 = gb.start; pt.nr = gb.count; pt.stride = gb.stride;
-        pt.base = (uint32_t)base;
-        partners.push_back(pt);
-        nr_max = std::max(nr_max, gb.count);
-      };
-      if (table) {
-        for (size_t b = first2[x]; b < B.groups.size() && B.groups[b].len == L2; b++) {
-          const uint64_t base = gap + T.v_distance[genes_of * n_v + B.keys[b] % per];
-          if (base <= (uint64_t)cutoff)
-            add(B.groups[b], base);
-        }
-      } else {
-        const uint64_t key = (uint64_t)L2 * per + genes_of;
-        const auto k = std::lower_bound(B.keys.begin(), B.keys.end(), key);
-        if (k != B.keys.end() && *k == key)
-          add(B.groups[(size_t)(k - B.keys.begin())], gap);
-      }
-    }
-    if (partners.size() == p0)
-      continue;
-    if (partners.size() > 0xffffffffull)
-      return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^32-1 pairs of groups");
-    const uint32_t nb = blocks_for(ga.count, PAIRS_WG);
-    J.runs.add(td_form_of(ga.len, ga.stride), (uint32_t)blocks, nb);
-    jobs.push_back(TdJob{ga.pk_off, ga.start, ga.count, ga.len, ga.stride, (uint32_t)p0,
-                         (uint32_t)(partners.size() - p0), (uint32_t)blocks, 0u});
-    blocks += nb;
-    if (blocks > 0xffffffu)
-      return fail(c, CMPR_EUNSUPPORTED, who + ": more than 2^24 workgroups of queries");
-  }
 
   /* W transposed: a row per set-2 residue */
   std::vector<uint32_t> wt(TD_WT_WORDS, 0u);
@@ -369,18 +311,8 @@ int td_setup(cmpr_context *c, const std::string &who, const cmpr_set_view *set1,
     for (uint32_t a2 = 0; a2 < TD_ALPHABET; a2++)
       wb[a2 * TD_WT_ROW + a1] = T.substitution[a1 * TD_ALPHABET + a2];
   if ((rc = dev_upload(c, J.wt.b, wt.data(), wt.size()))) return rc;
-  if (!jobs.empty()) {
-    if ((rc = dev_upload(c, J.jobs.b, jobs.data(), jobs.size()))) return rc;
-    if ((rc = dev_upload(c, J.partners.b, partners.data(), partners.size()))) return rc;
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));             /* (the vectors leave scope) */
-  TdParams &P = J.P;
-  P.jobs = J.jobs.b.p;
-  P.partners = J.partners.b.p;
-  P.njobs = (uint32_t)jobs.size();
-  P.segments = pairs_segments(c, c->tcrdist_segments, blocks, nr_max);
-  P.pk1 = A.pk.b.p; P.pk2 = B.pk.b.p;
-  P.ord1 = A.ord.b.p; P.ord2 = B.ord.b.p;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));             /* (`wt` leaves scope) */
+  P.segments = pairs_segments(c, c->tcrdist_segments, J.blocks, J.nr_max);
   P.wt = J.wt.b.p;
   P.cutoff = (uint32_t)cutoff;
   P.stage_refs = (uint32_t)c->tcrdist_stage_refs;
@@ -430,13 +362,10 @@ int tcrdist_matrix_impl(cmpr_context *c, const cmpr_set_view *set1, const cmpr_s
     return rc;
   if (!matrix_out)
     return fail(c, CMPR_EINVAL, who + ": matrix_out is NULL");
-  auto t0 = std::chrono::steady_clock::now();
-  for (double &t : c->td_ms)
-    t = 0;
   TdWork J;
-  if ((rc = td_setup(c, who, set1, set2, *T, cutoff, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->td_ms, false,
+                              [&] { return td_setup(c, who, set1, set2, *T, cutoff, on_device, J); })))
     return rc;
-  c->td_ms[0] = ms_since(t0);
   return pairs_matrix(c, J, J.P.sink, matrix_out, on_device, [&] { return td_launch<SINK_MATRIX>(c, J); }, c->td_ms, 3);
 }
 
@@ -447,21 +376,14 @@ int tcrdist_neighbors_impl(cmpr_context *c, const cmpr_set_view *set1, const cmp
   if (!c)
     return CMPR_EINVAL;
   const std::string who = "cmpr_tcrdist_neighbors";
-  if (!n_edges_out)
-    return fail(c, CMPR_EINVAL, who + ": n_edges_out is NULL");
-  *n_edges_out = 0;
-  if (capacity && !hit_out)
-    return fail(c, CMPR_EINVAL, who + ": hit_out is NULL with a capacity");
   int rc;
-  if ((rc = td_refusals(c, who, set1, set2, T, cutoff, HM_NEIGHBORS, on_device)))
+  if ((rc = pairs_neighbors_args(c, who, capacity, hit_out, n_edges_out)) ||
+      (rc = td_refusals(c, who, set1, set2, T, cutoff, HM_NEIGHBORS, on_device)))
     return rc;
-  auto t0 = std::chrono::steady_clock::now();
-  for (double &t : c->td_ms)
-    t = 0;
   TdWork J;
-  if ((rc = td_setup(c, who, set1, set2, *T, cutoff, on_device, J)))
+  if ((rc = pairs_timed_setup(c, c->td_ms, false,
+                              [&] { return td_setup(c, who, set1, set2, *T, cutoff, on_device, J); })))
     return rc;
-  c->td_ms[0] = ms_since(t0);
   /* the rows always (the row order reads them); the row order into td_ms[2] */
   return pairs_neighbors(c, who, J, J.P.segments, J.P.sink, capacity, row_start_out, hit_out, dist_out, n_edges_out,
                          on_device, [&] { return td_launch<SINK_CSR>(c, J); }, true, c->td_ms, 2, 3);

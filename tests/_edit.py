@@ -11,7 +11,7 @@ import _neighbors
 from compairr_amd import Options, RepertoireSet, synth
 from compairr_amd.sets import AA, NT
 
-MAX_LEN = 256                  # ED_MAX_LEN of compairr_amd/csrc/edit.hip: four 64-bit words of the column
+MAX_LEN = 256                  # PAIRS_MAX_LEN of compairr_amd/csrc/allpairs.h: four 64-bit words of the column
 
 
 def options(**kw):

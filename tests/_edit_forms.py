@@ -34,8 +34,8 @@ from compairr_amd.sets import AA, NT
 
 # ---- the register form of a query ----
 
-REG_RESIDUES = 64              # ED_REG_RESIDUES of compairr_amd/csrc/edit.hip: a longer query is read from global memory
-FORMS = (2, 4, 8, 16)          # the forms ed_form_of of compairr_amd/csrc/edit.hip walks through
+REG_RESIDUES = 64              # PAIRS_REG_RESIDUES of compairr_amd/csrc/allpairs.h: a longer query is read from global memory
+FORMS = (2, 4, 8, 16)          # the forms pairs_form_of of compairr_amd/csrc/allpairs.hip walks through
 STRIDES = (1, 2, 3, 4, 5, 6, 8, 12, 16)    # the word counts of stride_of, compairr_amd/csrc/allpairs.hip
 PER_WORD = {False: 4, True: 16}            # residues per packed word: amino acids, nucleotides
 ALL_FORMS = {False: (2, 4, 8, 16, 0), True: (2, 4, 0)}
@@ -43,7 +43,7 @@ CROSSINGS = {False: (8, 16, 32, 64), True: (32, 64)}     # an edge crosses c: on
 
 
 def form_of(length, nucleotides):
-    """ed_form_of(len, stride_of(len, per_word)): 2, 4, 8, 16, or 0"""
+    """pairs_form_of(len, stride_of(len, per_word)): 2, 4, 8, 16, or 0"""
     if length > REG_RESIDUES:
         return 0
     words = max(1, -(-length // PER_WORD[nucleotides]))

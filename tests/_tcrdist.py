@@ -13,7 +13,7 @@ from compairr_amd import Options, RepertoireSet, synth
 from compairr_amd.sets import AA
 
 FIXED, SLIDING = 0, 1
-MAX_LEN = 256                  # TD_MAX_LEN of compairr_amd/csrc/tcrdist.hip
+MAX_LEN = 256                  # PAIRS_MAX_LEN of compairr_amd/csrc/allpairs.h
 
 
 def options(**kw):

@@ -19,7 +19,7 @@ from compairr_amd import HipOverlap, hip
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(HERE, "..", "include", "compairr_hip.h")
-SOURCE = os.path.join(HERE, "..", "compairr_amd", "csrc", "edit.hip")
+SOURCE = os.path.join(HERE, "..", "compairr_amd", "csrc", "allpairs.h")      # (the limit of edit.hip and tcrdist.hip)
 NAMES = ("cmpr_edit_neighbors", "cmpr_edit_neighbors_device", "cmpr_edit_matrix", "cmpr_edit_matrix_device")
 KEYS = list(_edit.EDGES)
 IDS = ["%s-d%d%s" % (k[0], k[1], "-g" if k[2] else "") for k in KEYS]
@@ -144,7 +144,7 @@ def test_sets_at_the_word_edges(nucleotides):
 def test_the_length_limit_of_the_helper_is_the_kernel_s():
     with open(SOURCE) as fh:
         text = fh.read()
-    assert re.search(r"constexpr uint32_t ED_MAX_LEN = (\d+);", text).group(1) == str(_edit.MAX_LEN)
+    assert re.search(r"constexpr uint32_t PAIRS_MAX_LEN = (\d+);", text).group(1) == str(_edit.MAX_LEN)
 
 
 def test_header_binding_and_library_carry_the_entry_points():

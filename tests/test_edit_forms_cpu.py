@@ -48,18 +48,17 @@ def test_shape_of_the_family_sets(nucleotides):
 
 
 def test_the_forms_of_the_helper_are_the_kernel_s():
-    with open(os.path.join(CSRC, "edit.hip")) as fh:
-        text = fh.read()
-    assert re.search(r"constexpr uint32_t ED_REG_RESIDUES = (\d+);", text).group(1) == str(ef.REG_RESIDUES)
-    forms = re.search(r"uint32_t ed_form_of\(uint32_t len, uint32_t stride\)\n\{\n  if \(len > ED_REG_RESIDUES\)\n"
-                      r"    return 0;\n  for \(uint32_t f : \{([0-9u, ]+)\}\)\n    if \(stride <= f\)\n      return f;\n"
-                      r"  return 0;\n\}", text)
-    assert tuple(int(f.strip(" u")) for f in forms.group(1).split(",")) == ef.FORMS
+    with open(os.path.join(CSRC, "allpairs.h")) as fh:
+        header = fh.read()
     with open(os.path.join(CSRC, "allpairs.hip")) as fh:
         text = fh.read()
+    assert re.search(r"constexpr uint32_t PAIRS_REG_RESIDUES = (\d+);", header).group(1) == str(ef.REG_RESIDUES)
+    forms = re.search(r"uint32_t cmpr::pairs_form_of\(uint32_t len, uint32_t stride\)\n\{\n"
+                      r"  if \(len > PAIRS_REG_RESIDUES\)\n    return 0;\n  for \(uint32_t f : \{([0-9u, ]+)\}\)\n"
+                      r"    if \(stride <= f\)\n      return f;\n  return 0;\n\}", text)
+    assert tuple(int(f.strip(" u")) for f in forms.group(1).split(",")) == ef.FORMS
     strides = re.search(r"static const uint32_t forms\[\] = \{([0-9, ]+), HAMMING_REG_WORDS\};", text).group(1)
-    with open(os.path.join(CSRC, "allpairs.h")) as fh:
-        reg_words = int(re.search(r"constexpr uint32_t HAMMING_REG_WORDS = (\d+);", fh.read()).group(1))
+    reg_words = int(re.search(r"constexpr uint32_t HAMMING_REG_WORDS = (\d+);", header).group(1))
     assert tuple(int(f) for f in strides.split(",")) + (reg_words,) == ef.STRIDES
     # the lengths at which the form changes
     for nucleotides, edges in ((False, {8: 2, 9: 4, 16: 4, 17: 8, 32: 8, 33: 16, 64: 16, 65: 0, 256: 0, 0: 2, 1: 2}),

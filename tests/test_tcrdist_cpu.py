@@ -16,7 +16,7 @@ from compairr_amd import HipOverlap, TcrdistParams, hip
 from conftest import ROOT
 
 HEADER = os.path.join(ROOT, "include", "compairr_hip.h")
-SOURCE = os.path.join(ROOT, "compairr_amd", "csrc", "tcrdist.hip")
+SOURCE = os.path.join(ROOT, "compairr_amd", "csrc", "allpairs.h")       # (the limit of edit.hip and tcrdist.hip)
 NAMES = ["cmpr_tcrdist_neighbors", "cmpr_tcrdist_neighbors_device", "cmpr_tcrdist_matrix", "cmpr_tcrdist_matrix_device"]
 
 # x, y: (trims (3, 2) FIXED, SLIDING, trims (0, 0) FIXED, SLIDING) with W[a][b] = |a - b| in sets.AA order, penalty 12
@@ -89,7 +89,7 @@ def test_the_inputs_reach_every_short_length():
 def test_the_length_limit_of_the_helper_is_the_kernel_s():
     with open(SOURCE) as fh:
         text = fh.read()
-    assert re.search(r"constexpr uint32_t TD_MAX_LEN = (\d+);", text).group(1) == str(_tcrdist.MAX_LEN)
+    assert re.search(r"constexpr uint32_t PAIRS_MAX_LEN = (\d+);", text).group(1) == str(_tcrdist.MAX_LEN)
 
 
 def test_header_binding_and_library_carry_the_entry_points():

@@ -1,9 +1,9 @@
 """cmpr_tcrdist_neighbors / cmpr_tcrdist_matrix and their _device variants on the GPU: the CSR and the matrix against
 the numpy brute force of the definition (tests/_tcrdist.py) on every input and case of the issue, an asymmetric table
 and its transpose law, agreement with cmpr_hamming_neighbors under unit weights, the V table, the lengths at which
-the query forms change, workgroups, staged pieces and long rows, the same bytes under every tunable, wrapping sums,
-the capacity protocol, the device entry points, empty sets, determinism, the resident state left alone and every
-refusal.  No expectation comes from the library."""
+the query forms change, workgroups, staged pieces and long rows, the job table with a skipped group, the same bytes
+under every tunable, wrapping sums, the capacity protocol, the device entry points, empty sets, determinism, the
+resident state left alone and every refusal.  No expectation comes from the library."""
 
 import ctypes as C
 
@@ -274,6 +274,55 @@ def test_one_large_group():
             with pytest.raises(HipError) as e:
                 h.set_tunable(name, bad)
             assert e.value.code == CMPR_EINVAL
+
+
+def job_table_sets():
+    """one stem of 70 residues over two letters that cost 1 against each other under table(); every sequence a prefix
+    of it with two residues replaced at random, the rows shuffled.  (length, count) per set: at gap penalty 4 and cutoff
+    7 a length pairs with itself and its neighbours only, so set 1's length 11 has no partner in set 2"""
+    W = _tcrdist.table()
+    rng = np.random.default_rng(2600)
+    stem = np.array([0, int(np.nonzero(W[0] == 1)[0][0])], dtype=np.uint8)[rng.integers(0, 2, size=70)]
+
+    def rows(shape):
+        out = []
+        for n, count in shape:
+            for _ in range(count):
+                r = stem[:n].copy()
+                r[rng.integers(0, n, size=2)] = rng.integers(0, 20, size=2, dtype=np.uint8)
+                out.append(r)
+        return [out[k] for k in rng.permutation(len(out))]
+    return (_tcrdist.hand_set(rows(((8, 40), (11, 30), (14, 600), (20, 50), (70, 20))), 261),
+            _tcrdist.hand_set(rows(((8, 30), (9, 30), (14, 300), (15, 40), (20, 40), (70, 20))), 262))
+
+
+@pytest.mark.parametrize("mode", [FIXED, SLIDING], ids=["fixed", "sliding"])
+def test_the_job_table(mode):
+    """in one call: a set-1 group without partners (length 11) between two jobs, a job of three workgroups (length 14)
+    that is not the first, and runs of the forms 2, 4, 8 and generic (lengths 8, 14, 20, 70) -- what the job table, its
+    runs and the search of a workgroup's job must get right together"""
+    s1, s2 = job_table_sets()
+    cutoff = 7
+    want = _tcrdist.brute_csr(s1, s2, _tcrdist.table(), 3, 2, 4, mode, cutoff)
+    q, hits = _edit.queries_of(want[0]), want[1].astype(np.int64)
+    la, lb = s1.lengths[q].astype(np.int64), s2.lengths[hits].astype(np.int64)
+    print("job table, mode %d: %d edges of %d pairs, per set-1 length %s, %d across lengths" % (
+        mode, len(hits), s1.n * s2.n, {n: int((la == n).sum()) for n in (8, 11, 14, 20, 70)}, int((la != lb).sum())))
+    for n in (8, 14, 20, 70):
+        assert (la == n).any(), n
+    assert not (la == 11).any() and (s1.lengths == 11).any()
+    assert (la != lb).any() and len(hits) < s1.n * s2.n
+    opt = Options(device=0)
+    p = TcrdistParams(_tcrdist.table(), 4, 3, 2, mode)
+    m_want = _edit.matrix_of(s1, s2, want[0], want[1], opt)
+    with HipOverlap(opt) as h:
+        assert_equal_edges(h.tcrdist_neighbors(s1, s2, p, cutoff), want, s1.n)
+        assert np.array_equal(h.tcrdist_matrix(s1, s2, p, cutoff), m_want)
+        h.set_tunable("tcrdist_segments", 3)
+        h.set_tunable("tcrdist_stage_refs", 65)
+        for g, w in zip(h.tcrdist_neighbors(s1, s2, p, cutoff), want):
+            assert g.tobytes() == w.tobytes()
+        assert h.tcrdist_matrix(s1, s2, p, cutoff).tobytes() == m_want.tobytes()
 
 
 @pytest.mark.parametrize("key", [("tiny", 1, True), ("mid", 2, False), ("tiny", 3, True)], ids=["tiny", "mid", "gap0"])

@@ -5,7 +5,7 @@
 #   tools/kernel_resources.sh 1 8        variant 1, 8 waves per workgroup
 #   tools/kernel_resources.sh all        every object of the library that holds a probe or resolve kernel (the
 #                                        Makefile's TU_OBJS), the two files of the row sorters (csr_rows.h) and the
-#                                        three of the all-against-all calls (allpairs.h), one "== object ==" block each, JOBS (default 8) compilations side by side
+#                                        four of the all-against-all calls (allpairs.h), one "== object ==" block each, JOBS (default 8) compilations side by side
 cd "$(dirname "$0")/.." || exit 1
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -c -Rpass-analysis=kernel-resource-usage -o /dev/null"
 run() {
@@ -42,6 +42,7 @@ if [ "$1" = all ]; then
   one allpairs compairr_amd/csrc/allpairs.hip
   one hamming compairr_amd/csrc/hamming.hip
   one edit compairr_amd/csrc/edit.hip
+  one tcrdist compairr_amd/csrc/tcrdist.hip
   wait
   cat "$tmp"/* | grep -v 'rocprim::'          # (the library's own kernels: hipcub's instantiations are hundreds)
 elif [ -n "$1" ]; then

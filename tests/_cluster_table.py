@@ -31,6 +31,25 @@ def table_of(label, count):
     return cluster_of.astype(np.uint32), cluster_start, members.astype(np.uint32), cluster_count
 
 
+TABLE_NAMES = ("cluster_of", "cluster_start", "members", "count")
+TABLE_DTYPES = (np.uint32, np.uint64, np.uint32, np.uint64)
+
+
+def assert_partition(got, label):
+    """(label, size, n_clusters) as a cluster call gives them against the partition `label`"""
+    assert len(got) == 3 and got[0].dtype == np.uint32 and got[1].dtype == np.uint32
+    assert np.array_equal(got[0], label)
+    assert np.array_equal(got[1], _cluster.sizes_of_labels(label))
+    assert got[2] == int((label == np.arange(len(label))).sum())
+
+
+def assert_table(got, want):
+    """the four arrays of a cluster-table call against table_of()"""
+    for name, dtype, g, w in zip(TABLE_NAMES, TABLE_DTYPES, got, want):
+        assert g.dtype == dtype, name
+        assert g.shape == w.shape and np.array_equal(g, w), name
+
+
 def printed(case, keys):
     """(cluster_no int64[n], cluster_size int64[n], rows): the reference's print-out of `case` per INPUT row, and
     the input numbers of its output rows in the order printed"""

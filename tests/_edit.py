@@ -87,14 +87,17 @@ def histogram(dist, d):
 
 def matrix_of(set1, set2, row_start, hits, opt):
     """uint64 cells summed from a pair list as cmpr_hamming_matrix documents them: product, min, max, count1 + count2
-    for the mean, 1 per pair with ignore_counts; n1 rows with `existence`.  uint64 arithmetic, wrapping."""
+    for the mean, the product sum for MH and the min sum for Jaccard (cmpr_overlap_matrix's integer sums, as
+    tests/_existence.py has them), 1 per pair with ignore_counts; n1 rows with `existence`.  uint64 arithmetic,
+    wrapping."""
     q, h = queries_of(row_start), np.asarray(hits).astype(np.int64)
     f, g = set1.count[q].astype(np.uint64), set2.count[h].astype(np.uint64)
     if opt.ignore_counts:
         v = np.ones(len(q), dtype=np.uint64)
     else:
-        v = {"product": lambda: f * g, "min": lambda: np.minimum(f, g), "max": lambda: np.maximum(f, g),
-             "mean": lambda: f + g}[opt.score.lower()]()
+        with np.errstate(over="ignore"):
+            v = {"product": lambda: f * g, "min": lambda: np.minimum(f, g), "max": lambda: np.maximum(f, g),
+                 "mean": lambda: f + g, "mh": lambda: f * g, "jaccard": lambda: np.minimum(f, g)}[opt.score.lower()]()
     rows = q if opt.existence else set1.repertoire[q].astype(np.int64)
     m = np.zeros((set1.n if opt.existence else set1.n_repertoires, set2.n_repertoires), dtype=np.uint64)
     with np.errstate(over="ignore"):

@@ -15,7 +15,7 @@ import _edit
 import _edit_cluster as ec
 import _neighbors
 import compairr_amd
-from _cluster_table import table_of
+from _cluster_table import TABLE_DTYPES, TABLE_NAMES, assert_partition, assert_table, table_of
 from compairr_amd import HipError, HipOverlap, Options, RepertoireSet
 from compairr_amd.hip import _view
 from compairr_amd.sets import AA
@@ -24,22 +24,7 @@ pytestmark = pytest.mark.gpu
 
 CMPR_OK, CMPR_EINVAL, CMPR_EUNSUPPORTED = 0, 1, 4
 POISON32, POISON64 = 0x25A5A5A5, 0x25A5A5A525A5A5A5
-TABLE_NAMES = ("cluster_of", "cluster_start", "members", "count")
-TABLE_DTYPES = (np.uint32, np.uint64, np.uint32, np.uint64)
 HAMMING_TIMERS = ("hamming_group_us", "hamming_compare_us", "hamming_copy_us")
-
-
-def assert_partition(got, label):
-    assert len(got) == 3 and got[0].dtype == np.uint32 and got[1].dtype == np.uint32
-    assert np.array_equal(got[0], label)
-    assert np.array_equal(got[1], _cluster.sizes_of_labels(label))
-    assert got[2] == int((label == np.arange(len(label))).sum())
-
-
-def assert_table(got, want):
-    for name, dtype, g, w in zip(TABLE_NAMES, TABLE_DTYPES, got, want):
-        assert g.dtype == dtype, name
-        assert g.shape == w.shape and np.array_equal(g, w), name
 
 
 def assert_everything(s, opt_kw, d, label, tunables=None):
